@@ -7,7 +7,16 @@ sums of ``of_weight(2, dim=3)`` in EXTENDED mode (W = 15 words, K = 18 sums) of 
 reference's ``(K, N, T)`` tensor (BASELINE.json configs[1]).  Prints ONE JSON
 line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs when asked and prints
+the line: ``ms_per_step`` is the wall time of one timed step, and ``roofline`` holds only
+figures derived from that timed region.  ``--dump-outputs DIR`` writes what the last timed
+step computed as ``DIR/iss_knt_sample.npy`` (float64): the ``(K, N, T)`` tensor at a fixed,
+seeded sample of 256 of the N series (38 MB of the 302 MB); the input batch is seeded, so two
+builds can be compared output for output.  Everything described below besides the headline
+(the batch statistics, the check against numpy, the secondary measurements, the word-sharded
+config 4 and the CPU baseline) runs with ``--full`` only.
 
 N > 1 is launched by the driver through torch.distributed.run, one rank per GPU.
 Two things are then measured:
@@ -15,7 +24,7 @@ Two things are then measured:
 * the headline ``value``: every rank processes its own batch of the workload above
   (the path is independent per series: weak scaling, no data-path collective), the
   timed region is bracketed by barrier + synchronize, the slowest rank counts;
-* ``word_sharded_config4``: north_star's multi-GPU split through the PRODUCT entry
+* ``word_sharded_config4`` (``--full``): north_star's multi-GPU split through the PRODUCT entry
   ``fruits_amd.parallel.transform_sharded`` - BASELINE configs[3], the ``fruit_general``
   word set ``of_weight(6, 2)`` + ``Indices`` on ``(8192, 3, 1024)``: the batch exists on rank 0
   only and is broadcast device to device, the fruit is fitted on rank 0, every rank computes
@@ -23,7 +32,7 @@ Two things are then measured:
   gather assemble the reference's ``(N, F)`` on every rank; checked against the unsharded
   transform on rank 0.
 
-N = 1 adds, INSIDE the ``roofline`` object (the driver's record keeps it verbatim):
+N = 1 with ``--full`` adds, INSIDE the ``roofline`` object (the driver's record keeps it verbatim):
 ``secondary`` - the metric's 48-word reading, of_weight(4,2) materialised (K = 115), what the box
 copies, and the fused pipelines of configs[2..4] on one GPU (us, fraction; for the fused ones the
 VALU issue fraction of the last committed profile) - and ``sweep_N_T_static_interp``; ``extras``
@@ -48,6 +57,8 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 N_SERIES, N_DIMS, N_STEPS_T = 2048, 3, 1024
+# --dump-outputs: the (K, N, T) tensor is 302 MB; these many series of it, drawn with this seed
+DUMP_SERIES, DUMP_SEED = 256, 20251016
 
 
 # --------------------------------------------------------------------------- CPU baselines
@@ -568,12 +579,18 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (a seeded sample) as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beside the headline (see the docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no secondary measurements")
     ap.add_argument("--quick-extras", action="store_true", help="skip the config 4 / 5 extras")
-    ap.add_argument("--no-word-shard", action="store_true")
+    ap.add_argument("--no-word-shard", action="store_true", help="with --full: no word-sharded config 4")
     ap.add_argument("--groups", type=int, default=0)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import fruits_amd as fr
@@ -645,12 +662,20 @@ def main() -> None:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
 
-    # sanity: the timed kernel really produced the tensor (one row against numpy)
-    row0 = out[0, :4].cpu().numpy()
-    assert np.allclose(row0, np.cumsum(X[:4, 0] ** 2, axis=1), rtol=1e-9)
+    # what the last timed step wrote, before anything else runs on `out`
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(N_SERIES, DUMP_SERIES, replace=False))
+        sample = out.index_select(1, torch.from_numpy(pick).to(dev)).cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, "iss_knt_sample.npy"), sample)
 
-    # distribution of the per-launch time: median / min / max over >= 50 event-timed batches
-    batches = _batch_stats_us(torch, step) if rank == 0 else None
+    batches = None
+    if args.full:
+        # sanity: the timed kernel really produced the tensor (one row against numpy)
+        row0 = out[0, :4].cpu().numpy()
+        assert np.allclose(row0, np.cumsum(X[:4, 0] ** 2, axis=1), rtol=1e-9)
+        # distribution of the per-launch time: median / min / max over >= 50 event-timed batches
+        batches = _batch_stats_us(torch, step) if rank == 0 else None
 
     elements = N_SERIES * K * N_STEPS_T
     value = elements * args.steps * world / elapsed
@@ -689,7 +714,7 @@ def main() -> None:
             "N": N_SERIES, "D": N_DIMS, "T": N_STEPS_T, "words": len(words), "K": K,
             "sharding": "series (one batch per GPU), no data-path collective; the word-sharded "
                         "RCCL all-gather split of configs[3] is measured beside it for n_gpus > 1 "
-                        "(word_sharded_config4)",
+                        "with --full (word_sharded_config4)",
         },
         "roofline": {
             "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -697,21 +722,22 @@ def main() -> None:
             "kernel": "iss_walk_static_kernel (of_weight(2,3) program, one group per series)", "algorithmic_bytes_per_launch": b_alg,
             "kernel_avg_us": kernel_avg_s * 1e6,
             "timing": "one HIP event pair around the `steps` launches of the timed region / steps",
-            "batches": batches,
         },
     }
+    if batches is not None:
+        res["roofline"]["batches"] = batches
     del out
-    if distributed and not args.no_word_shard:
+    if args.full and distributed and not args.no_word_shard:
         ws = word_sharded_config4(torch, fr, nat, dist, rank, world, backend)
         if rank == 0:
             res["word_sharded_config4"] = ws
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         sec, sweep_rows, det = extras(torch, fr, nat, dev, quick=args.quick_extras)
         # (inside the roofline object: the driver's record keeps that verbatim)
         res["roofline"]["secondary"] = sec
         res["roofline"]["sweep_N_T_static_interp"] = sweep_rows
         res["extras"] = det
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(words)
     if distributed:
         dist.barrier()

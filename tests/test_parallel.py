@@ -240,10 +240,11 @@ def _sharded_worker(rank, world, port, out_dir):
 
         def block(slc, iss, Xb, cache, indices, depths, per_sum):
             # the oracle stands in for the HIP pipeline; what is under test is what surrounds it:
-            # only the root handed the batch in, every rank sees it here
+            # only the root handed the batch in, every rank sees it here (on the device where
+            # there is one)
             seen["shape"] = tuple(Xb.shape)
             strings = [str(w) for w in iss.words]
-            return _oracle_block(Xb.numpy(), strings, depths, indices, 0.0)
+            return _oracle_block(Xb.cpu().numpy(), strings, depths, indices, 0.0).to(Xb.device)
         full = par.transform_sharded(fruit, X, block=block)
         assert seen["shape"] == (5, 3, 40)
         dev = par.transform_sharded(fruit, X, block=block, on_device=True)
