@@ -463,7 +463,7 @@ extern "C" {
 
 const char *fr_last_error(void) { return g_err.c_str(); }
 
-int fr_version(void) { return 133; }
+int fr_version(void) { return 134; }
 
 int fr_device_count(void) {
   int n = 0;
@@ -750,6 +750,7 @@ struct fr_pipeline {
   void *d_npi_pairs = nullptr;
   std::vector<PipeSieve> sieves;
   std::vector<int32_t> mpi_cols;   // columns inside one iterated sum's block
+  std::vector<int32_t> key_cols;   // MAX columns (~column: MIN) inside one iterated sum's block
   // Arctic argmax (fr_pipeline_set_argmax): the OUTPUT rows are the L + L (L + 1) / 2 rows of every
   // word (running maxima and back-tracked positions, fruits/iss/semiring.py:239-284), not the
   // plan's; (n_words, 4) {first plan row, letters, first output row, 0}
@@ -759,6 +760,7 @@ struct fr_pipeline {
   int rows() const { return argmax_words.empty() ? plan->p->K : argmax_rows; }   // output rows
   void *d_ops = nullptr;           // (rows, n_ops_padded) FeatOp
   void *d_mpi_cols = nullptr;
+  void *d_key_cols = nullptr;
   bool have_quantiles = false;
   // per-series cut table (fr_pipeline_set_series_cuts): device (cuts_N, cut_slots) int32, owned
   // by the caller; cut_slots_needed = 1 + the highest slot a sieve names
@@ -1560,8 +1562,13 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
     sv.Q1 = Q1[i];
     const int c1 = C1[i];
     std::string bad;
-    if (sv.kind < 0 || sv.kind > 2 || c1 < 2) bad = "bad sieve " + std::to_string(i);
     int code = FR_E_ARG;
+    if (sv.kind < 0 || sv.kind > FR_SIEVE_LPI || c1 < 2) bad = "bad sieve " + std::to_string(i);
+    else if (sv.kind == FR_SIEVE_LPI) {
+      // (a run crosses lanes, waves and time chunks: the window has no carry for it)
+      bad = "LPI is not fused";
+      code = FR_E_LIMIT;
+    }
     if (bad.empty() && sv.kind != FR_SIEVE_END) {
       if (sv.Q1 < 2) bad = "a band sieve needs >= 2 thresholds";
       else if (sv.inc < -8 || sv.inc > 8) {
@@ -1600,8 +1607,12 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
     const int nf = sv.kind == FR_SIEVE_END ? c1 - 1 : (c1 - 1) * (sv.Q1 - 1);
     sv.col = col;
     sv.q_off = qoff;
-    if (sv.kind == FR_SIEVE_MPI)
+    // (XPI is MPI of the positions: sum and population, divided by mpi_finalize_kernel)
+    if (sv.kind == FR_SIEVE_MPI || sv.kind == FR_SIEVE_XPI)
       for (int f = 0; f < nf; ++f) pl->mpi_cols.push_back(col + f);
+    // (MAX / MIN leave band keys, walk_types.h: band_key_finalize_kernel makes them values)
+    if (sv.kind == FR_SIEVE_MAX || sv.kind == FR_SIEVE_MIN)
+      for (int f = 0; f < nf; ++f) pl->key_cols.push_back(sv.kind == FR_SIEVE_MIN ? ~(col + f) : col + f);
     if (sv.kind != FR_SIEVE_END) qoff += sv.Q1;
     col += nf;
     n_ops += nf;
@@ -1625,6 +1636,7 @@ void fr_pipeline_destroy(fr_pipeline_t *pl) {
   }
   if (pl->d_ops) (void)hipFree(pl->d_ops);
   if (pl->d_mpi_cols) (void)hipFree(pl->d_mpi_cols);
+  if (pl->d_key_cols) (void)hipFree(pl->d_key_cols);
   if (pl->d_npi_pairs) (void)hipFree(pl->d_npi_pairs);
   if (pl->d_prep) (void)hipFree(pl->d_prep);
   if (pl->d_argmax_words) (void)hipFree(pl->d_argmax_words);
@@ -1801,9 +1813,12 @@ int fr_pipeline_set_argmax(fr_pipeline_t *pl, int32_t n_words, const int32_t *le
                               " rows, the words' prefixes are " + std::to_string(v0));
   if (o0 > 0x7fffffffLL / std::max(1, pl->per_sum) || n_words > 65535)
     return fail(FR_E_LIMIT, "fr_pipeline_set_argmax: too many rows");
-  for (const PipeSieve &sv : pl->sieves)
+  for (const PipeSieve &sv : pl->sieves) {
     if (sv.kind != FR_SIEVE_END && (sv.inc < 0 || sv.inc > 2))
       return fail(FR_E_LIMIT, "fr_pipeline_set_argmax: differencing orders 0 to 2");
+    if (sv.kind > FR_SIEVE_END)
+      return fail(FR_E_LIMIT, "fr_pipeline_set_argmax: NPI, MPI and END only");
+  }
   if (pl->T > 65535 || fr::argmax_sieve_lds(pl->T, max_len) > fr::kArgmaxSieveLds)
     return fail(FR_E_LIMIT, "fr_pipeline_set_argmax: a row of maxima and the positions of a word's "
                             "prefixes must fit a workgroup's LDS");
@@ -1851,6 +1866,11 @@ int fr_pipeline_set_quantiles(fr_pipeline_t *pl, const double *h_quant) {
   if (!pl->mpi_cols.empty() && !pl->d_mpi_cols) {
     HIP_TRY(hipMalloc(&pl->d_mpi_cols, pl->mpi_cols.size() * 4));
     HIP_TRY(hipMemcpy(pl->d_mpi_cols, pl->mpi_cols.data(), pl->mpi_cols.size() * 4,
+                      hipMemcpyHostToDevice));
+  }
+  if (!pl->key_cols.empty() && !pl->d_key_cols) {
+    HIP_TRY(hipMalloc(&pl->d_key_cols, pl->key_cols.size() * 4));
+    HIP_TRY(hipMemcpy(pl->d_key_cols, pl->key_cols.data(), pl->key_cols.size() * 4,
                       hipMemcpyHostToDevice));
   }
   pl->have_quantiles = true;
@@ -2239,6 +2259,12 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
                                              (int)pl->npi_pairs.size() / 2, pl->per_sum, p.K, st);
       if (e != hipSuccess) return hip_fail(e, "mpi_finalize launch");
     }
+    if (!pl->key_cols.empty()) {
+      hipError_t e = fr::launch_band_key_finalize(fu.walk_feats, N, F,
+                                                  static_cast<const int32_t *>(pl->d_key_cols),
+                                                  (int)pl->key_cols.size(), pl->per_sum, p.K, st);
+      if (e != hipSuccess) return hip_fail(e, "band_key_finalize launch");
+    }
     hipError_t e = fr::launch_gather_row_blocks(fu.walk_feats, d_feats, N, F, feat_stride, p.K,
                                                 pl->per_sum, walk_of_row, st);
     if (e != hipSuccess) return hip_fail(e, "gather_row_blocks launch");
@@ -2251,6 +2277,12 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
                                            static_cast<const int32_t *>(pl->d_npi_pairs),
                                            (int)pl->npi_pairs.size() / 2, pl->per_sum, p.K, st);
     if (e != hipSuccess) return hip_fail(e, "mpi_finalize launch");
+  }
+  if (!pl->key_cols.empty()) {
+    hipError_t e = fr::launch_band_key_finalize(d_feats, N, feat_stride,
+                                                static_cast<const int32_t *>(pl->d_key_cols),
+                                                (int)pl->key_cols.size(), pl->per_sum, p.K, st);
+    if (e != hipSuccess) return hip_fail(e, "band_key_finalize launch");
   }
   return FR_OK;
 }
@@ -2327,7 +2359,7 @@ int fr_pathlen_lookup(const double *d_X, int64_t N, int64_t D, int64_t T, int32_
 int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride, int32_t inc,
              const int64_t *d_cuts, int64_t cut_rows, int32_t C1, const double *d_q, int32_t Q1,
              double *d_out, int64_t out_stride, void *stream) {
-  if (kind < 0 || kind > 2) return fail(FR_E_ARG, "fr_sieve: unknown kind");
+  if (kind < 0 || kind > FR_SIEVE_LPI) return fail(FR_E_ARG, "fr_sieve: unknown kind");
   if (N < 0 || T < 1 || C1 < 2 || (cut_rows != 1 && cut_rows != N))
     return fail(FR_E_ARG, "fr_sieve: bad shape");
   if (kind != FR_SIEVE_END && (Q1 < 2 || !d_q)) return fail(FR_E_ARG, "fr_sieve: bad quantiles");

@@ -17,6 +17,8 @@ hipError_t launch_iss_walk(IssArgs &a, int levels, hipStream_t st);
 hipError_t launch_mpi_finalize(double *feats, const double *cnt, int64_t N, int64_t stride,
                                const int32_t *cols, int n_cols, const int32_t *pairs, int n_pairs,
                                int per_sum, int K, hipStream_t st);
+hipError_t launch_band_key_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
+                                    int n_cols, int per_sum, int K, hipStream_t st);
 hipError_t launch_gather_row_blocks(const double *src, double *dst, int64_t N, int64_t src_stride,
                                     int64_t dst_stride, int K, int per_sum, const int32_t *walk_of_row,
                                     hipStream_t st);

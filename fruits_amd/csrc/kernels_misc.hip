@@ -263,6 +263,139 @@ __global__ __launch_bounds__(256) void sieve_kernel(int kind, const double *__re
   }
 }
 
+// MAX / MIN / XPI / LPI (segment.py:107-200, increment.py:166-239) on the same (N,T) rows:
+// one workgroup per series, every (segment, band) in turn.  MAX / MIN reduce band_key()s (an
+// order-preserving integer form of the value, walk_types.h: 0 = empty), XPI sums the in-band
+// positions relative to the segment start (integers: exact in any order) and their count.
+// LPI gives every thread a CONTIGUOUS tile of the segment and merges (leading run, trailing
+// run, longest run, length, all in band) summaries in thread order, then in wave order.
+struct RunSummary {
+  int64_t pre, suf, best, len;   // (all in band  <=>  pre == len)
+};
+__device__ __forceinline__ RunSummary run_merge(const RunSummary &a, const RunSummary &b) {
+  RunSummary r;
+  r.pre = a.pre == a.len ? a.len + b.pre : a.pre;
+  r.suf = b.suf == b.len ? b.len + a.suf : b.suf;
+  r.best = a.best > b.best ? a.best : b.best;
+  if (a.suf + b.pre > r.best) r.best = a.suf + b.pre;
+  r.len = a.len + b.len;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void band_sieve_kernel(int kind, const double *__restrict__ A,
+                                                         int64_t T, int64_t a_stride, int inc,
+                                                         const int64_t *__restrict__ cuts,
+                                                         int64_t cut_rows, int C1,
+                                                         const double *__restrict__ q, int Q1,
+                                                         double *__restrict__ out,
+                                                         int64_t out_stride) {
+  __shared__ unsigned long long sm_key[4];
+  __shared__ double sm_sum[4], sm_cnt[4];
+  __shared__ RunSummary sm_run[4];
+  const int64_t n = blockIdx.x;
+  const double *row = A + n * a_stride;
+  const int64_t *cut = cuts + (cut_rows == 1 ? 0 : n * C1);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Q = Q1 - 1;
+  for (int j = 0; j < C1 - 1; ++j) {
+    int64_t lo = cut[j], hi = cut[j + 1];
+    if (lo < 0) lo = 0;
+    if (hi > T) hi = T;
+    for (int k = 0; k < Q; ++k) {
+      const double qlo = q[k], qhi = q[k + 1];
+      double res = 0.0;
+      if (kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K) {
+        unsigned long long key = 0;
+        for (int64_t t = lo + tid; t < hi; t += blockDim.x) {
+          const double v = diff_at(row, t, inc);
+          if (qlo < v && v <= qhi) {
+            const unsigned long long kv = band_key(v, kind == FR_SIEVE_MIN_K);
+            key = kv > key ? kv : key;
+          }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+          const unsigned long long w = __shfl_xor(key, o);
+          key = w > key ? w : key;
+        }
+        __syncthreads();
+        if (lane == 0) sm_key[wave] = key;
+        __syncthreads();
+        if (tid == 0) {
+          for (int w = 0; w < 4; ++w) key = sm_key[w] > key ? sm_key[w] : key;
+          res = band_key_value(key, kind == FR_SIEVE_MIN_K);
+        }
+      } else if (kind == FR_SIEVE_XPI_K) {
+        double sum = 0.0, cnt = 0.0;
+        for (int64_t t = lo + tid; t < hi; t += blockDim.x) {
+          const double v = diff_at(row, t, inc);
+          if (qlo < v && v <= qhi) {
+            sum += (double)(t - lo);
+            cnt += 1.0;
+          }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+          sum += __shfl_xor(sum, o);
+          cnt += __shfl_xor(cnt, o);
+        }
+        __syncthreads();
+        if (lane == 0) {
+          sm_sum[wave] = sum;
+          sm_cnt[wave] = cnt;
+        }
+        __syncthreads();
+        if (tid == 0) {
+          double s = 0.0, c = 0.0;
+          for (int w = 0; w < 4; ++w) {
+            s += sm_sum[w];
+            c += sm_cnt[w];
+          }
+          res = c > 0.0 ? s / c : 0.0;
+        }
+      } else {   // LPI
+        const int64_t len = hi > lo ? hi - lo : 0;
+        const int64_t tile = (len + blockDim.x - 1) / blockDim.x;
+        int64_t a = lo + tid * tile, b = a + tile;
+        if (a > hi) a = hi;
+        if (b > hi) b = hi;
+        RunSummary r{0, 0, 0, b - a};
+        int64_t cur = 0;
+        bool lead = true;
+        for (int64_t t = a; t < b; ++t) {
+          const double v = diff_at(row, t, inc);
+          if (qlo < v && v <= qhi) {
+            ++cur;
+            if (cur > r.best) r.best = cur;
+          } else {
+            if (lead) r.pre = cur;
+            lead = false;
+            cur = 0;
+          }
+        }
+        r.pre = lead ? r.len : r.pre;
+        r.suf = cur;
+        // lane order: lane l takes lane l + o's summary from its right
+        for (int o = 1; o < 64; o <<= 1) {
+          RunSummary s;
+          s.pre = __shfl_down(r.pre, o);
+          s.suf = __shfl_down(r.suf, o);
+          s.best = __shfl_down(r.best, o);
+          s.len = __shfl_down(r.len, o);
+          if ((lane & (2 * o - 1)) == 0) r = run_merge(r, s);
+        }
+        __syncthreads();
+        if (lane == 0) sm_run[wave] = r;
+        __syncthreads();
+        if (tid == 0) {
+          r = sm_run[0];
+          for (int w = 1; w < 4; ++w) r = run_merge(r, sm_run[w]);
+          res = (double)r.best;
+        }
+      }
+      if (tid == 0) out[n * out_stride + j * Q + k] = res;
+    }
+  }
+}
+
 // IncrementSieve._pre_transform (inc >= 0) materialised: out[n,t] = D_inc[n,t]
 __global__ void pre_transform_kernel(const double *__restrict__ A, int64_t N, int64_t T,
                                      int64_t a_stride, int inc, double *__restrict__ out) {
@@ -1632,6 +1765,35 @@ hipError_t launch_mpi_finalize(double *feats, const double *cnt, int64_t N, int6
   return hipGetLastError();
 }
 
+// MAX / MIN features of the fused walk: the band keys (walk_types.h) it left as the columns' bits
+// become values, key 0 (an empty band or segment) 0.0.  cols: the MAX columns inside one
+// iterated sum's block, ~column for MIN.
+__global__ void band_key_finalize_kernel(double *__restrict__ feats, int64_t N, int64_t stride,
+                                         const int32_t *__restrict__ cols, int n_cols, int per_sum,
+                                         int K) {
+  const int64_t per_n = (int64_t)K * n_cols;
+  const int64_t total = N * per_n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t n = i / per_n, r = i % per_n;
+    const int64_t k = r / n_cols;
+    const int c = cols[r % n_cols];
+    double *f = feats + n * stride + k * per_sum + (c < 0 ? ~c : c);
+    *f = band_key_value(__builtin_bit_cast(uint64_t, *f), c < 0);
+  }
+}
+
+hipError_t launch_band_key_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
+                                    int n_cols, int per_sum, int K, hipStream_t st) {
+  const int64_t total = N * (int64_t)K * n_cols;
+  if (total <= 0) return hipSuccess;
+  int64_t blocks = (total + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(band_key_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, feats, N,
+                     stride, cols, n_cols, per_sum, K);
+  return hipGetLastError();
+}
+
 // A plan in pieces leaves its features in WALK order (plan.h, PiecedProgram): the blocks of
 // `per_sum` columns of one iterated sum back into the reference's row order,
 // dst[n, k * per_sum + j] = src[n, walk_of_row[k] * per_sum + j].  Writes are coalesced, reads
@@ -1698,8 +1860,12 @@ hipError_t launch_sieve(int kind, const double *A, int64_t N, int64_t T, int64_t
                         const int64_t *cuts, int64_t cut_rows, int C1, const double *q, int Q1,
                         double *out, int64_t out_stride, hipStream_t st) {
   if (N <= 0) return hipSuccess;
-  hipLaunchKernelGGL(sieve_kernel, dim3((unsigned)N), dim3(256), 0, st, kind, A, T, a_stride, inc,
-                     cuts, cut_rows, C1, q, Q1, out, out_stride);
+  if (kind >= FR_SIEVE_MAX_K)
+    hipLaunchKernelGGL(band_sieve_kernel, dim3((unsigned)N), dim3(256), 0, st, kind, A, T, a_stride,
+                       inc, cuts, cut_rows, C1, q, Q1, out, out_stride);
+  else
+    hipLaunchKernelGGL(sieve_kernel, dim3((unsigned)N), dim3(256), 0, st, kind, A, T, a_stride, inc,
+                       cuts, cut_rows, C1, q, Q1, out, out_stride);
   return hipGetLastError();
 }
 

@@ -519,9 +519,11 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
   const int kind = w[0] & 0xff, inc = (int)(int8_t)((w[0] >> 8) & 0xff), col = w[1];   // inc: signed
   // per-series cuts (coquantile positions): lo / hi name slots of the series' cut row
   const bool series_cuts = (w[0] >> 16) & 1;
+  const bool keyed = kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K;
   if constexpr (C::TEAM != 1) {
-    // (the flush needs the column of every slot, also of one no lane adds to)
-    if (cx.wave == 0 && cx.lane == 0) cx.fl_col[slot] = col;
+    // (the flush needs the column of every slot, also of one no lane adds to; ~col: a MAX / MIN
+    // slot, combined by maximum of keys)
+    if (cx.wave == 0 && cx.lane == 0) cx.fl_col[slot] = keyed ? ~col : col;
   }
   if (kind == FR_SIEVE_END_K) {
     int pick = w[2];                    // index of the value to pick
@@ -614,6 +616,27 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
       }
     }
   }
+  if (keyed) {
+    // MAX / MIN: the largest band_key (walk_types.h) of the wave, one ds_max_u64 per wave
+    uint64_t key = 0;
+#pragma unroll
+    for (int h = 0; h < P; ++h)
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int t = t_first + h * C::PIECE + e;
+        const double v = d[h * E + e];
+        const uint64_t kv = band_key(v, kind == FR_SIEVE_MIN_K);
+        if (t >= lo && t < hi && qlo < v && v <= qhi && kv > key) key = kv;
+      }
+    key = wave_max_u64(key);
+    if (cx.lane == 0) {
+      if constexpr (C::TEAM != 1) lds_max_u64(cx.fl_val + slot, key);
+      else cx.feat_row[col] = __builtin_bit_cast(double, key);
+    }
+    return;
+  }
+  // XPI: the sum of MPI is one of positions relative to the segment start (integers: exact)
+  const bool mpi = kind == FR_SIEVE_MPI_K || kind == FR_SIEVE_XPI_K;
   int cnt = 0;
   double sum = 0.0;
 #pragma unroll
@@ -625,15 +648,16 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
       const bool in = t >= lo && t < hi && qlo < v && v <= qhi;
       cnt += __popcll(__ballot(in));
       if (kind == FR_SIEVE_MPI_K) sum += in ? v : 0.0;
+      else if (kind == FR_SIEVE_XPI_K) sum += in ? (double)(t - lo) : 0.0;
     }
   // every op leaves its result, zero counts included: every feature column is written exactly
   // once per series and the feature tensor needs no clearing
-  if (kind == FR_SIEVE_MPI_K)
+  if (mpi)
     sum = wave_last_lane(wave_inclusive_scan<0>(sum));  // wave total by DPP (no LDS permutes)
   if (cx.lane == 0) {
     if constexpr (C::TEAM != 1) {
       // one LDS add per wave (ds_add_f64, nothing returned)
-      if (kind == FR_SIEVE_MPI_K) {
+      if (mpi) {
         lds_add(cx.fl_val + slot, sum);
         lds_add(cx.fl_cnt + slot, (double)cnt);
       } else {
@@ -641,7 +665,7 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
       }
     } else {
       // wave-per-unit kernels: the wave holds the whole (single-chunk) row
-      if (kind == FR_SIEVE_MPI_K) {
+      if (mpi) {
         cx.feat_row[col] = sum;
         cx.cnt_row[col] = (double)cnt;
       } else {
@@ -672,16 +696,29 @@ __device__ __forceinline__ void feat_flush(WalkCtx &cx, bool add) {
   const int n_ops = ap->n_ops;
   for (int sl = cx.tid; sl < cx.fused_used; sl += kWalkThreads) {
     int col;
+    bool keyed;   // a MAX / MIN slot (band keys, walk_types.h)
     if constexpr (TABLE) {
       const int r = sl / n_ops, i = sl - r * n_ops;
       // (a plan in pieces numbers its output rows in walk order: no table)
       const int64_t k = ap->slot_rows != nullptr ? as_const(ap->slot_rows)[cx.frow0 + r] : cx.frow0 + r;
-      col = as_const(ap->ops)[k * ap->n_ops_padded + i].col;
+      cptr<FeatOp> op = as_const(ap->ops) + k * ap->n_ops_padded + i;
+      col = op->col;
+      const int kind = op->kind_inc & 0xff;
+      keyed = kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K;
     } else {
       col = cx.fl_col[sl];
+      keyed = col < 0;   // (fused_op: ~col)
+      col = keyed ? ~col : col;
     }
     double v = cx.fl_val[sl];
-    if (add) v = feat_row[col] + v;
+    if (add) {
+      const double before = feat_row[col];
+      if (keyed) {   // MAX / MIN keys: the larger one (the window's 0.0 is key 0, the identity)
+        if (__builtin_bit_cast(uint64_t, before) > __builtin_bit_cast(uint64_t, v)) v = before;
+      } else {
+        v = before + v;
+      }
+    }
     feat_row[col] = v;
     cx.fl_val[sl] = 0.0;
     if (mpi) {

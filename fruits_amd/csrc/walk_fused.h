@@ -418,8 +418,25 @@ __device__ __forceinline__ void fop(WalkCtx &cx, const int32_t *w, int slot, con
       }
     }
   }
-  const bool mpi = kind == FR_SIEVE_MPI_K;
   const int t_first = (int)cx.t0 + cx.wave * C::SPAN + cx.lane * E;
+  if (kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K) {
+    // the largest band key of the wave (walk_types.h), one ds_max_u64; the flush combines a
+    // window's keys with the row's by maximum (walk_device.h, feat_flush)
+    uint64_t key = 0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int t = t_first + e;
+      const double v = d[e];
+      const uint64_t kv = band_key(v, kind == FR_SIEVE_MIN_K);
+      if (t >= lo && t < hi && qlo < v && v <= qhi && kv > key) key = kv;
+    }
+    key = wave_max_u64(key);
+    if (cx.lane == 0) lds_max_u64(cx.fl_val + slot, key);
+    return;
+  }
+  // XPI: MPI of the positions relative to the segment start (integer sums: exact in any order)
+  const bool xpi = kind == FR_SIEVE_XPI_K;
+  const bool mpi = kind == FR_SIEVE_MPI_K || xpi;
   int cnt = 0;
   double sum = 0.0;
 #pragma unroll
@@ -430,7 +447,7 @@ __device__ __forceinline__ void fop(WalkCtx &cx, const int32_t *w, int slot, con
     if (mpi) {
       const bool in = in_t && qlo < v && v <= qhi;
       cnt += __popcll(__ballot(in));
-      sum += in ? v : 0.0;
+      sum += in ? (xpi ? (double)(t - lo) : v) : 0.0;
     } else {
       // (the AND of the compare masks: as one predicate it goes through a vector register)
       cnt += __popcll(__ballot(in_t) & __ballot(qlo < v) & __ballot(v <= qhi));

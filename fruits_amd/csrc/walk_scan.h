@@ -92,6 +92,34 @@ __device__ __forceinline__ double wave_shift_right1(double v) {
   return dpp_fetch<0x138, 0xf, SEMI>(v);  // wave_shr:1, lane 0 gets the identity
 }
 
+// Largest unsigned 64-bit value of the wave (band keys of MAX / MIN, walk_types.h) as a
+// wave-uniform value: the steps of wave_inclusive_scan with max, 0 - the identity - where a
+// lane has no source.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long dpp_fetch_u64(unsigned long long v) {
+  constexpr bool all_rows = ROW_MASK == 0xf;
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, ROW_MASK, 0xf, all_rows);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, 0xf, all_rows);
+  return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+  unsigned long long w;
+  w = dpp_fetch_u64<0x111, 0xf>(v); v = w > v ? w : v;   // row_shr:1
+  w = dpp_fetch_u64<0x112, 0xf>(v); v = w > v ? w : v;   // row_shr:2
+  w = dpp_fetch_u64<0x114, 0xf>(v); v = w > v ? w : v;   // row_shr:4
+  w = dpp_fetch_u64<0x118, 0xf>(v); v = w > v ? w : v;   // row_shr:8
+  w = dpp_fetch_u64<0x142, 0xa>(v); v = w > v ? w : v;   // row_bcast:15 -> rows 1,3
+  w = dpp_fetch_u64<0x143, 0xc>(v); v = w > v ? w : v;   // row_bcast:31 -> rows 2,3
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+  return ((unsigned long long)hi << 32) | lo;
+}
+// ds_max_u64 on a window slot (the slot's 0.0 is key 0)
+__device__ __forceinline__ void lds_max_u64(lds_f64 *p, unsigned long long v) {
+  typedef unsigned long long __attribute__((address_space(3))) lds_u64;
+  (void)__hip_atomic_fetch_max((lds_u64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 __device__ __forceinline__ double wave_last_lane(double v) {
   // lane 63's value as a wave-uniform (scalar) double
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);

@@ -92,6 +92,33 @@ constexpr uint64_t feat_window_bytes(int slots, bool mpi, bool cols = true) {
 constexpr int FR_SIEVE_NPI_K = 0;
 constexpr int FR_SIEVE_MPI_K = 1;
 constexpr int FR_SIEVE_END_K = 2;
+constexpr int FR_SIEVE_MAX_K = 3;
+constexpr int FR_SIEVE_MIN_K = 4;
+constexpr int FR_SIEVE_XPI_K = 5;
+constexpr int FR_SIEVE_LPI_K = 6;
+
+#if defined(__HIP__) || defined(__HIPCC_RTC__)
+#define FR_HOST_DEVICE __host__ __device__
+#else
+#define FR_HOST_DEVICE
+#endif
+// MAX / MIN in integers: an order-preserving 64-bit key of the value (its bits with the sign bit
+// flipped, or all bits flipped for a negative value), complemented for MIN - so that both are a
+// MAXIMUM of keys, and key 0 (a NaN's, which never is in a band) is the empty band.  The
+// reductions (wave shuffles, ds_max_u64 into the fused walk's window, the flush onto the feature
+// row) are then exact and independent of order.
+FR_HOST_DEVICE inline uint64_t band_key(double v, bool is_min) {
+  const uint64_t b = __builtin_bit_cast(uint64_t, v);
+  const uint64_t k = (b >> 63) ? ~b : (b | (1ull << 63));
+  return is_min ? ~k : k;
+}
+// ... and back; the empty band is 0.0 (the reference's empty-segment value)
+FR_HOST_DEVICE inline double band_key_value(uint64_t k, bool is_min) {
+  if (is_min) k = ~k;
+  if (k == 0 || k == ~0ull) return 0.0;
+  const uint64_t b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+  return __builtin_bit_cast(double, b);
+}
 
 // One feature of one iterated sum, everything resolved on the host (32 bytes, read
 // with one scalar load): END picks the value at index `lo`; NPI / MPI look at

@@ -515,8 +515,8 @@ class FruitSlice:
 
     # ---- fused ISS + sieves (one launch, no (K, N, T) tensor) --------------------
     def _fusable(self) -> bool:
-        from .sieving.increment import MPI, NPI
-        from .sieving.segment import END
+        from .sieving.increment import MPI, NPI, XPI
+        from .sieving.segment import END, MAX, MIN
         # (a chain of ISS: the LAST one fuses with the sieves, once per row of the chain in front
         # of it - fruits/fruit.py:440-454 feeds every row of an ISS to the next one)
         if os.environ.get("FRUITS_AMD_FUSED", "1") == "0" or not self._iss:
@@ -529,6 +529,8 @@ class FruitSlice:
             if len(self._iss) != 1 or os.environ.get("FRUITS_AMD_FUSED_ARGMAX", "1") == "0":
                 return False
             for sv in self._sieves:
+                if type(sv) not in (NPI, MPI, END):
+                    return False     # (the argmax kernel forms NPI / MPI / END only)
                 if type(sv) in (NPI, MPI) and not 0 <= sv._inc <= 2:
                     return False
         if type(last) is not ISS:
@@ -540,7 +542,8 @@ class FruitSlice:
                 return False     # (every (word, frequency) reads its own transformed input:
                                  # fused word by word, _transform_ffn_fused - single ISS only)
         for sv in self._sieves:
-            if type(sv) not in (NPI, MPI, END):
+            # (LPI is not fused: a run crosses lanes, waves and time chunks - DESIGN 4.3)
+            if type(sv) not in (NPI, MPI, XPI, MAX, MIN, END):
                 return False
             if type(sv) is not END and not -8 <= sv._inc <= 8:
                 return False     # (cumulated rows: series of one time chunk; the pipeline says if not)

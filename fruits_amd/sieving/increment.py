@@ -1,4 +1,4 @@
-"""Increment sieves (mirrors IncrementSieve / NPI / MPI of
+"""Increment sieves (mirrors IncrementSieve / NPI / MPI / XPI / LPI of
 fruits/sieving/increment.py): statistics of the ``inc``-times differenced
 iterated sum inside quantile bands ``q_k < x <= q_{k+1}``, per cut segment.
 The differencing is fused into the HIP kernel's load (``fr_sieve``)."""
@@ -12,7 +12,7 @@ import numpy as np
 from .. import _native as nat
 from .segment import SegmentSieve
 
-__all__ = ["NPI", "MPI"]
+__all__ = ["NPI", "MPI", "XPI", "LPI"]
 
 
 class IncrementSieve(SegmentSieve):
@@ -85,3 +85,15 @@ class MPI(IncrementSieve):
     """Mean of the increments inside each band, 0 for an empty band
     (fruits/sieving/increment.py:132-163)."""
     _kind = nat.FR_SIEVE_MPI
+
+
+class XPI(IncrementSieve):
+    """Mean of the positions, relative to the segment start, of the increments inside each
+    band, 0 for an empty band (fruits/sieving/increment.py:166-198)."""
+    _kind = nat.FR_SIEVE_XPI
+
+
+class LPI(IncrementSieve):
+    """Length of the longest run of consecutive increments inside each band, 0 for an empty
+    band (fruits/sieving/increment.py:201-239)."""
+    _kind = nat.FR_SIEVE_LPI

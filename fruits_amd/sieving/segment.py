@@ -18,7 +18,7 @@ from .. import _native as nat
 from ..cache import CacheType
 from .abstract import FeatureSieve
 
-__all__ = ["END"]
+__all__ = ["MAX", "MIN", "END"]
 
 
 class SegmentSieve(FeatureSieve, ABC):
@@ -169,6 +169,19 @@ class SegmentSieve(FeatureSieve, ABC):
         for x in self._cut:
             text += f"\n   > {x}"
         return text
+
+
+class MAX(SegmentSieve):
+    """Largest value inside each band ``q_k < x <= q_{k+1}`` of every segment, 0 for an
+    empty segment (fruits/sieving/segment.py:107-153).  An empty band of a non-empty segment
+    is 0 as well - the reference raises ValueError there (np.max of an empty array)."""
+    _kind = nat.FR_SIEVE_MAX
+
+
+class MIN(SegmentSieve):
+    """Smallest value inside each band of every segment, 0 for an empty segment or band
+    (fruits/sieving/segment.py:155-200; the reference raises ValueError for an empty band)."""
+    _kind = nat.FR_SIEVE_MIN
 
 
 class END(SegmentSieve):

@@ -85,6 +85,10 @@ extern "C" {
 #define FR_SIEVE_NPI 0 /* fruits/sieving/increment.py:101-129 */
 #define FR_SIEVE_MPI 1 /* fruits/sieving/increment.py:132-163 */
 #define FR_SIEVE_END 2 /* fruits/sieving/segment.py:203-225   */
+#define FR_SIEVE_MAX 3 /* fruits/sieving/segment.py:107-153   */
+#define FR_SIEVE_MIN 4 /* fruits/sieving/segment.py:155-200   */
+#define FR_SIEVE_XPI 5 /* fruits/sieving/increment.py:166-198 */
+#define FR_SIEVE_LPI 6 /* fruits/sieving/increment.py:201-239 */
 /* OR-ed into a sieve's kind at fr_pipeline_create: its cuts are PER SERIES (coquantile
  * cuts, fruits/sieving/segment.py:51-64) - the sieve's `cuts` entries then name columns
  * ("slots") of the table given to fr_pipeline_set_series_cuts */
@@ -239,9 +243,11 @@ int fr_pathlen_lookup(const double *d_X, int64_t N, int64_t D, int64_t T,
                       double *d_out /* (N,T) */, void *stream);
 
 /* ------------------------------------------------------------------ sieves
- * Replace IncrementSieve._pre_transform + NPI/MPI._backend
- * (fruits/sieving/increment.py:63-71, 107-129, 138-163) and END._transform
- * (fruits/sieving/segment.py:210-219) on a materialised (N, T) iterated sum.
+ * Replace IncrementSieve._pre_transform + NPI/MPI/XPI/LPI._backend
+ * (fruits/sieving/increment.py:63-71, 107-129, 138-163, 172-198, 207-239), MAX/MIN._backend
+ * (fruits/sieving/segment.py:113-153, 161-200) and END._transform (segment.py:210-219) on a
+ * materialised (N, T) iterated sum.  MAX / MIN: 0 for an empty segment AND for an empty band
+ * (the reference raises ValueError there); XPI / LPI: 0 for an empty band.
  *
  *   d_A      (N, T) f64, row stride a_stride elements
  *   inc      >= 0: number of increment passes fused into the load
@@ -260,8 +266,8 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
  * ISS + sieves in ONE launch: replaces the loop of FruitSlice.transform
  * (fruits/fruit.py:538-550) - for every iterated sum, for every sieve,
  * sieve.transform(itsum) - without ever materialising the (K, N, T) tensor.
- * Sieves: NPI / MPI with inc in {0, 1, 2} and END, integer cuts (the same for all
- * series).  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
+ * Sieves: NPI / MPI / XPI with inc -8 to 8, MAX / MIN (inc 0) and END; integer cuts or
+ * per-series cuts (FR_SIEVE_SERIES_CUTS).  LPI is not fused (FR_E_LIMIT).  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
  * column order (iterated sum, then sieve, then segment, then band).
  *
  *   kinds/incs/C1/Q1   per sieve; Q1 is ignored for END
