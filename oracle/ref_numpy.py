@@ -650,18 +650,98 @@ def end_transform(A, cuts):
     return out
 
 
+def longest_run(mask):
+    """Length of the longest run of True in a 1-d boolean array (0 for none): the distance
+    between a rising and the next falling edge of the mask padded with False."""
+    m = np.concatenate([[False], np.asarray(mask, dtype=bool), [False]])
+    edges = np.flatnonzero(m[1:] != m[:-1])
+    return int((edges[1::2] - edges[::2]).max()) if edges.size else 0
+
+
+def band_value(kind, seg, inside):
+    """The statistic of sieve ``kind`` over the elements of segment ``seg`` that ``inside``
+    marks: what each backend below computes per (segment, band).  An empty band (an empty
+    segment included) gives 0.0 for every kind."""
+    if kind == "NPI":
+        return float(np.sum(inside))
+    if not inside.any():
+        return 0.0
+    if kind == "MPI":
+        return float(np.mean(seg[inside]))
+    if kind == "MAX":
+        return float(np.max(seg[inside]))
+    if kind == "MIN":
+        return float(np.min(seg[inside]))
+    if kind == "XPI":
+        return float(np.mean(np.nonzero(inside)[0]))
+    if kind == "LPI":
+        return float(longest_run(inside))
+    raise ValueError("not a band sieve: %r" % (kind,))
+
+
+def _band_backend(kind, A, cuts, quantiles):
+    # the loop nest every band sieve of the reference shares: series, segment, band; the band
+    # is q_lo < v <= q_hi (NaN is in none)
+    N = A.shape[0]
+    C, Q = cuts.shape[1] - 1, len(quantiles) - 1
+    out = np.zeros((N, C * Q))
+    for i in range(N):
+        for j in range(C):
+            seg = A[i, cuts[i, j]:cuts[i, j + 1]]
+            for k in range(Q):
+                inside = np.logical_and(quantiles[k] < seg, seg <= quantiles[k + 1])
+                out[i, j * Q + k] = band_value(kind, seg, inside)
+    return out
+
+
+def max_backend(A, cuts, quantiles):
+    """fruits/sieving/segment.py:107-146 (MAX._backend): the largest in-band value of the
+    segment.  An empty segment gives 0.0 as in the reference; an empty band of a non-empty
+    segment gives 0.0 too, where the reference raises (np.max of an empty array) - the
+    project's documented departure (fruits_amd/sieving/segment.py)."""
+    return _band_backend("MAX", A, cuts, quantiles)
+
+
+def min_backend(A, cuts, quantiles):
+    """fruits/sieving/segment.py:155-194 (MIN._backend): the smallest in-band value; empty
+    segment or empty band 0.0 (the latter the same departure as in max_backend)."""
+    return _band_backend("MIN", A, cuts, quantiles)
+
+
+def xpi_backend(A, cuts, quantiles):
+    """fruits/sieving/increment.py:166-198 (XPI._backend): the mean of the in-band indices,
+    counted from the segment start; an empty band gives 0.0."""
+    return _band_backend("XPI", A, cuts, quantiles)
+
+
+def lpi_backend(A, cuts, quantiles):
+    """fruits/sieving/increment.py:201-239 (LPI._backend): the length of the longest run of
+    consecutive in-band elements of the segment; an empty band gives 0.0."""
+    return _band_backend("LPI", A, cuts, quantiles)
+
+
+BACKENDS = {"NPI": npi_backend, "MPI": mpi_backend, "MAX": max_backend, "MIN": min_backend,
+            "XPI": xpi_backend, "LPI": lpi_backend}
+INCREMENT_KINDS = ("NPI", "MPI", "XPI", "LPI")
+SEGMENT_KINDS = ("MAX", "MIN", "END")
+
+
 class SieveOracle:
-    """One sieve (NPI / MPI / END) with the reference's fit/transform contract
-    (fruits/sieving/segment.py:14-104, increment.py:14-98)."""
+    """One sieve with the reference's fit/transform contract (fruits/sieving/segment.py:14-104,
+    increment.py:14-98): the increment sieves NPI / MPI / XPI / LPI (default band (0, 1], the
+    row differenced ``inc`` times for fit and transform) and the segment sieves MAX / MIN / END
+    (default band (-inf, inf], no differencing)."""
 
     def __init__(self, kind, cut=-1, q=None, inc=1, coquantile_norm="L2"):
+        if kind not in INCREMENT_KINDS + SEGMENT_KINDS:
+            raise ValueError("unknown sieve kind: %r" % (kind,))
         self.kind = kind
         self.cut = tuple(cut) if isinstance(cut, (list, tuple)) else (cut,)
-        if kind in ("NPI", "MPI"):
+        if kind in INCREMENT_KINDS:
             self.q = tuple(q) if q is not None else (0.0, 1.0)
         else:
             self.q = tuple(q) if q is not None else (-1.0, 1.0)
-        self.inc = inc if kind in ("NPI", "MPI") else 0
+        self.inc = inc if kind in INCREMENT_KINDS else 0
         self.norm = coquantile_norm
         self.quantiles = None
 
@@ -691,11 +771,11 @@ class SieveOracle:
         arr = pre_transform(A, self.inc)
         cuts = transformed_cuts(A.shape[0], A.shape[1], self.cut, X_raw,
                                 self.norm)
-        fn = npi_backend if self.kind == "NPI" else mpi_backend
-        return fn(arr, cuts, self.quantiles)
+        return BACKENDS[self.kind](arr, cuts, self.quantiles)
 
 
-    def exposure(self, A, X_raw=None, rel=1e-10, tight=False, means=None, robust_zeros=False):
+    def exposure(self, A, X_raw=None, rel=1e-10, tight=False, means=None, robust_zeros=False,
+                 candidates=None):
         """Test helper (not part of the reference): for every feature the number of
         elements of its cut segment that lie so close to one of the band's finite thresholds
         that a band test ``q_lo < v <= q_hi`` may come out differently under a re-associated
@@ -712,11 +792,15 @@ class SieveOracle:
         the sieve looks at - the second term because an increment of a scan inherits the
         rounding of the running sum it is taken from, however small the increment.
 
-        ``means`` (a dict, MPI only): filled with ``{(series, feature): candidate means}`` for
-        the exposed entries of at most 4 exposed elements - the band means after moving any
-        subset of the exposed elements across the threshold; a mean computed from values that
-        differ in the last bits must be one of them.  ``robust_zeros``: the rows are SUMS (see
-        the comment at its use)."""
+        ``candidates`` (a dict; MPI, MAX, MIN, XPI, LPI - a count needs none): filled with
+        ``{(series, feature): candidate values}`` for the exposed entries of at most 4 exposed
+        elements - the feature recomputed after moving every subset of the exposed elements
+        across the threshold (band_value); a feature computed from values that differ in the
+        last bits must be one of them.  ``means`` is the older name of the same dict (its callers
+        look up MPI columns only).  ``robust_zeros``: the rows are SUMS (see the comment at its
+        use)."""
+        if candidates is None:
+            candidates = means
         out = np.zeros((A.shape[0], self.nfeatures()), dtype=np.int64)
         if self.kind == "END":
             return out
@@ -752,7 +836,7 @@ class SieveOracle:
                         near[0] = False
                     n_near = int(near.sum())
                     out[i, j * Q + k] = n_near
-                    if means is not None and self.kind == "MPI" and 0 < n_near <= 4:
+                    if candidates is not None and self.kind != "NPI" and 0 < n_near <= 4:
                         inside = np.logical_and(self.quantiles[k] < seg, seg <= self.quantiles[k + 1])
                         where = np.nonzero(near)[0]
                         cands = []
@@ -761,8 +845,8 @@ class SieveOracle:
                             for b, pos in enumerate(where):
                                 if bits >> b & 1:
                                     m[pos] = not m[pos]
-                            cands.append(0.0 if not m.any() else float(np.mean(seg[m])))
-                        means[(i, j * Q + k)] = cands
+                            cands.append(band_value(self.kind, seg, m))
+                        candidates[(i, j * Q + k)] = cands
         return out
 
 
@@ -884,8 +968,9 @@ def fruit_transform(spec, fitted, X):
 def fruit_transform_exposure(spec, fitted, X, rel=1e-10, tight=False, means=None):
     """fruit_transform and, from the same iterated sums, the (N, F) near-threshold element
     counts of every feature (SieveOracle.exposure, a test helper) in the same column order.
-    ``means``: a dict filled with {(series, column): candidate band means} of the exposed MPI
-    entries (see SieveOracle.exposure)."""
+    ``means``: a dict filled with {(series, column): candidate values} of the exposed entries of
+    the band sieves but NPI (the candidate band means of MPI, extremes of MAX / MIN, positions of
+    XPI, runs of LPI; see SieveOracle.exposure)."""
     feats, expos = [], []
     col0 = 0
     for sl, (sieves, ext) in zip(spec["slices"], fitted):

@@ -397,6 +397,91 @@ def test_random_fruit_differential(fr, seed, monkeypatch):
                             what=f"random fruit {seed} ({semiring})")
 
 
+@pytest.mark.parametrize("seed", range(int(os.environ.get("FRUITS_TEST_RANDOM_CASES", "40"))))
+def test_random_band_fruit_differential(fr, seed, monkeypatch):
+    """test_random_fruit_differential with MAX / MIN / XPI / LPI: random single-slice fruits
+    whose sieves are drawn mostly from the four newer kinds (int and coquantile cuts, empty
+    segments, bands with and without fitted thresholds, differencing orders -3 to 8), over
+    Reals, Arctic and CosWISS, on the packed short-series kernels, one cooperative chunk and
+    several (HIGHORD carries from 2100 on), with word lists that flush the feature window
+    repeatedly - against the numpy oracle, end to end and with the oracle's thresholds."""
+    rng = np.random.default_rng(7000 + seed)
+    if seed % 3 == 2:      # a third of the cases through the materialising sieve kernels
+        monkeypatch.setenv("FRUITS_AMD_FUSED", "0")
+    knob = {1: "packed=0", 4: "groups=2"}.get(seed % 6)
+    if knob:               # (documented never to change a result)
+        monkeypatch.setenv("FRUITS_HIP_DEBUG", knob)
+    T = int(rng.choice([24, 100, 300, 384, 700, 1024, 1500, 2100, 2600]))
+    N = int(rng.integers(3, 8)) if T > 1024 else int(rng.integers(6, 16))
+    D = int(rng.integers(1, 4))
+    cos = rng.random() < 0.15
+    if seed % 20 == 7:
+        # weight-4 words in three dimensions: a plan in pieces once compiled (pieces that
+        # compile in seconds, as in test_large_plan_in_pieces)
+        monkeypatch.setenv("FRUITS_AMD_AUTO_PREPARE", "all")
+        monkeypatch.setenv("FRUITS_HIP_DEBUG", ",".join(k for k in (knob, "piece_nodes=40") if k))
+        D, T, N, cos = 3, 256, 4, False
+        words = [str(w) for w in fr.words.of_weight(4, dim=3)]
+    elif not cos and rng.random() < 0.25:
+        D = 2                # 82 words, many times the feature window: repeated flushes
+        words = [str(w) for w in fr.words.of_weight(4, dim=2)]
+    else:
+        words = sorted({_random_word(rng, D).replace("-", "") for _ in range(int(rng.integers(1, 10)))})
+    preps = [[{"kind": "INC"}], [], [{"kind": "STD"}]][int(rng.integers(0, 3))]
+    if cos:
+        words = words[:4]
+        iss = {"kind": "CosWISS", "words": words, "freqs": [0.5, 2.0]}
+        semiring = "CosWISS"
+    else:
+        semiring = str(rng.choice(["Reals", "Reals", "Arctic"]))
+        weighting = [None, None, {"kind": "Indices", "scale": 2.0}, {"kind": "L1", "scale": 2.0},
+                     {"kind": "Indices", "scale": 2.0, "total": True}][int(rng.integers(0, 5))]
+        iss = {"words": words, "mode": str(rng.choice(["EXTENDED", "SINGLE"])), "semiring": semiring,
+               "weighting": weighting}
+    kinds = ["NPI", "MPI", "END", "MAX", "MIN", "XPI", "LPI"]
+    sieves = []
+    for _ in range(int(rng.integers(1, 6))):
+        kind = str(rng.choice(kinds, p=[0.08, 0.08, 0.08, 0.19, 0.19, 0.19, 0.19]))
+        cut = sorted({int(c) for c in rng.integers(1, T, size=int(rng.integers(0, 3)))}) + [-1]
+        u = rng.random()
+        if u < 0.3:        # float cuts: per-series coquantile positions
+            cut = [float(c) for c in rng.choice([0.2, 0.35, 0.5, 0.8], size=int(rng.integers(1, 3)),
+                                                replace=False)] + cut[:int(rng.integers(0, 2))]
+        elif u < 0.5:      # an empty segment
+            c = int(rng.integers(1, T))
+            cut = [c, c] + cut
+        s = {"kind": kind, "cut": cut}
+        if kind != "END":
+            s["q"] = [[-1.0, 0.0, 1.0], [-1.0, 0.3, 0.7, 1.0], [0.5, 1.0], [0.25, 0.5, 0.75, 1.0],
+                      [0.0, 1.0], [-1.0, 1.0]][int(rng.integers(0, 6))]
+        if kind in ("NPI", "MPI"):
+            s["inc"] = int(rng.integers(0, 3))
+        elif kind in ("XPI", "LPI"):
+            s["inc"] = int(rng.integers(-3, 9))
+        sieves.append(s)
+    if T >= 2100:          # a differencing order >= 3 on several chunks: the HIGHORD carries
+        sieves.append({"kind": "XPI", "cut": [T // 3, -1], "q": [-1.0, 0.0, 1.0],
+                       "inc": int(rng.integers(3, 9))})
+    spec = {"slices": [{"preps": preps, "iss": [iss], "sieves": sieves, "fit_sample_size": 1.0}]}
+    X = rng.standard_normal((N, D, T)).cumsum(axis=2) / np.sqrt(T)
+    fruit = build_fruit(fr, spec)
+    np.random.seed(seed)
+    fruit.fit(X)
+    slc = fruit.get_slice()
+    fusable = seed % 3 != 2 and not any(s["kind"] == "LPI" for s in sieves)
+    assert slc._fusable() == fusable
+    if fusable:
+        # (no silent fall-back: a fusable slice runs as one fused launch)
+        assert slc._fused(T) is not None
+    got = fruit.transform(X)
+    ref, expo = oracle_features(spec, X, X, np_seed=seed)
+    labels = [fruit.label(i) for i in range(fruit.nfeatures())]
+    assert got.shape == ref.shape
+    what = f"random band fruit {seed} ({semiring}, T={T})"
+    compare_features(got, ref, labels, expo, what=what)
+    strict_transform_parity(fruit, spec, X, X, labels, np_seed=seed, what=what)
+
+
 def test_plateaus_and_custom_weightings(fr):
     # host-built lookups (fruits/iss/weighting.py:41-66,213-256) consumed by the same kernel
     rng = np.random.default_rng(21)
@@ -1027,6 +1112,40 @@ def build_fruit(fr, spec):
     return fruit
 
 
+BAND_KINDS = ("MAX", "MIN", "XPI", "LPI")
+
+
+def sieve_kinds(labels):
+    """Per feature label the kind of its sieve: the first three letters of the label's last
+    part ("INC | [11] | NPI[inc=1]!-1![0.5, 1.0]" -> "NPI")."""
+    return np.array([lb.rsplit(" | ", 1)[-1][:3] for lb in labels])
+
+
+def _band_off(got, ref, kinds, rtol=RTOL, equal=False):
+    """Per entry of the MAX / MIN / XPI / LPI columns ``kinds``: does it disagree?  XPI (a mean
+    of integer positions: its sum and its count are exact) and LPI (a run length) must be
+    bit-equal, MAX / MIN (a data value) within the tolerance of END - or equal as well with
+    ``equal`` (max-plus rows, bit-equal to the reference's: so are their extremes)."""
+    if equal:
+        return got != ref
+    exact = np.isin(kinds, ("XPI", "LPI"))[None, :]
+    return np.where(exact, got != ref, ~np.isclose(got, ref, rtol=rtol, atol=1e-9))
+
+
+def _band_record(got, ref, kinds, expo, what, rtol=RTOL, equal=False):
+    """The parity record of the MAX / MIN / XPI / LPI columns (the keys of the counting
+    records): "differ" counts the entries that disagree (_band_off), "max_d" is the largest
+    difference of an LPI run length."""
+    off = _band_off(got, ref, kinds, rtol, equal)
+    lpi = kinds == "LPI"
+    d = np.abs(got[:, lpi] - ref[:, lpi])
+    return {"what": (what or os.environ.get("PYTEST_CURRENT_TEST", "?").split("::")[-1])
+                    + " [MAX/MIN/XPI/LPI]",
+            "entries": int(off.size), "exposed": int((expo > 0).sum()), "differ": int(off.sum()),
+            "differ_unexposed": int((off & (expo == 0)).sum()),
+            "max_d": float(d.max()) if d.size else 0.0, "band": True}
+
+
 def compare_features(got, ref, labels, expo=None, rtol=RTOL, what="", count_frac=0.01,
                      mean_rel=0.25, min_off=0, count_max=1):
     """Features against the oracle's.
@@ -1038,14 +1157,20 @@ def compare_features(got, ref, labels, expo=None, rtol=RTOL, what="", count_frac
     element is exposed and may differ by at most the number of exposed elements elsewhere;
     band means (MPI) must agree to rtol where nothing is exposed (one element entering or
     leaving a band moves its mean arbitrarily); value features (END) always to rtol.
+    MAX / MIN / XPI / LPI wherever nothing is exposed: LPI and XPI bit-equal, MAX / MIN to
+    the tolerance of END (one element entering or leaving a band moves any of them freely -
+    it may join two runs, or be the extreme).
     The observed numbers go to the parity report printed at the end of the run.
 
     Without ``expo`` (comparisons of two GPU paths, no oracle at hand): counts may differ
-    by ``count_max`` on at most ``count_frac`` of the entries."""
+    by ``count_max`` on at most ``count_frac`` of the entries; MAX / MIN / XPI / LPI get no
+    such latitude - XPI and LPI equal, MAX / MIN to rtol, every entry."""
     assert got.shape == ref.shape
-    is_count = np.array(["NPI" in lb for lb in labels])
-    is_mean = np.array(["MPI" in lb for lb in labels])
-    val = ~is_count & ~is_mean
+    kinds = sieve_kinds(labels)
+    is_count = kinds == "NPI"
+    is_mean = kinds == "MPI"
+    is_band = np.isin(kinds, BAND_KINDS)
+    val = ~is_count & ~is_mean & ~is_band
     if val.any():
         # atol: END of e.g. <[1]> on standardised data is an exact-zero sum, i.e.
         # pure rounding noise (1e-15) in the reference and here
@@ -1068,7 +1193,16 @@ def compare_features(got, ref, labels, expo=None, rtol=RTOL, what="", count_frac
             tight = em == 0
             off = np.abs(g - r) > rtol * np.abs(r) + 1e-9
             assert not (off & tight).any(), (int((off & tight).sum()), what)
+        if is_band.any():
+            brec = _band_record(got[:, is_band], ref[:, is_band], kinds[is_band], expo[:, is_band],
+                                what, rtol)
+            PARITY_REPORT.append(brec)
+            print(f"[parity] {brec}")
+            assert brec["differ_unexposed"] == 0, brec
         return rec
+    if is_band.any():
+        off = _band_off(got[:, is_band], ref[:, is_band], kinds[is_band], rtol)
+        assert not off.any(), (int(off.sum()), what)
     if is_mean.any():
         # a band mean inherits the count's sensitivity: when one on-threshold element
         # enters or leaves the band the mean moves by ~1/population
@@ -1149,16 +1283,22 @@ def compare_strict(got, ref, labels, expo, means, rtol=RTOL, what="", max_plus=N
     the tight exposure (SieveOracle.exposure, tight=True): counts equal wherever nothing is
     exposed, within the number of exposed elements elsewhere; band means to rtol where nothing
     is exposed, and ONE OF the candidate means (exposed elements moved across the threshold)
-    where up to four elements are; values (END) to rtol.  ``max_plus``: per column, see
-    _max_plus_columns - the two classes are recorded (and barred) separately."""
+    where up to four elements are; values (END) to rtol.  MAX / MIN / XPI / LPI: as in
+    compare_features where nothing is exposed, and ONE OF the oracle's candidate values where
+    up to four elements are (``means`` holds them for every band kind) - bit-equal for XPI and
+    LPI, to rtol for MAX / MIN.  ``max_plus``: per column, see _max_plus_columns - the two
+    classes are recorded (and barred) separately; on max-plus columns the four kinds must be
+    EQUAL, like the counts."""
     from conftest import STRICT_REPORT
     assert got.shape == ref.shape == expo.shape
     labels = np.asarray(labels)
     if max_plus is None:
         max_plus = np.zeros(got.shape[1], dtype=bool)
-    is_count = np.array(["NPI" in lb for lb in labels])
-    is_mean = np.array(["MPI" in lb for lb in labels])
-    val = ~is_count & ~is_mean
+    kinds = sieve_kinds(labels)
+    is_count = kinds == "NPI"
+    is_mean = kinds == "MPI"
+    is_band = np.isin(kinds, BAND_KINDS)
+    val = ~is_count & ~is_mean & ~is_band
     if val.any():
         np.testing.assert_allclose(got[:, val], ref[:, val], rtol=rtol, atol=1e-9)
     recs = []
@@ -1186,6 +1326,37 @@ def compare_strict(got, ref, labels, expo, means, rtol=RTOL, what="", max_plus=N
             # STD in numpy's summation order, csrc/pairwise.h): plateau ties fall the same
             # way on both sides - the counts are EQUAL
             assert rec["differ"] == 0, rec
+    count_recs = list(recs)
+    for cls, cols in (("sum", is_band & ~max_plus), ("max-plus", is_band & max_plus)):
+        if not cols.any():
+            continue
+        idx = np.nonzero(cols)[0]
+        g, r, e, k = got[:, cols], ref[:, cols], expo[:, cols], kinds[cols]
+        rec = _band_record(g, r, k, e, what, rtol, equal=cls == "max-plus")
+        rec.update(means_checked=0, exposed_elements=int(e.sum()), series=int(got.shape[0]), cls=cls)
+        STRICT_REPORT.append(rec)
+        recs.append(rec)
+        print(f"[strict] {rec}")
+        assert rec["differ_unexposed"] == 0, rec
+        if cls == "max-plus":
+            # the max-plus rows are bit-equal to the reference's (see above): so are their
+            # extremes, in-band positions and runs - every entry EQUAL (differ: got != ref)
+            assert rec["differ"] == 0, rec
+            np.testing.assert_array_equal(g, r, err_msg=what)
+            continue
+        checked = 0
+        for n, jj in zip(*np.nonzero(e > 0)):
+            cands = means.get((int(n), int(idx[jj])))
+            if cands is None:
+                continue          # more than four exposed elements
+            c = np.asarray(cands)
+            if k[jj] in ("XPI", "LPI"):
+                ok = np.any(g[n, jj] == c)
+            else:
+                ok = np.any(np.abs(g[n, jj] - c) <= rtol * np.abs(c) + 1e-9)
+            assert ok, (what, k[jj], n, idx[jj], g[n, jj], cands)
+            checked += 1
+        rec["means_checked"] = checked
     if is_mean.any():
         cols = np.nonzero(is_mean)[0]
         g, r, em = got[:, is_mean], ref[:, is_mean], expo[:, is_mean]
@@ -1199,8 +1370,8 @@ def compare_strict(got, ref, labels, expo, means, rtol=RTOL, what="", max_plus=N
             c = np.asarray(cands)
             assert np.any(np.abs(g[n, jj] - c) <= rtol * np.abs(c) + 1e-9), (what, n, cols[jj], g[n, jj], cands)
             checked += 1
-        if recs:
-            recs[0]["means_checked"] = checked
+        if count_recs:
+            count_recs[0]["means_checked"] = checked
     return recs
 
 
@@ -2662,7 +2833,7 @@ def test_zz_parity_bars():
     two thirds of the entries are exposed) - and are formed exactly like the reference's, from
     bit-equal inputs: no entry may differ at all."""
     from conftest import STRICT_REPORT
-    sums = [r for r in STRICT_REPORT if r["cls"] == "sum"]
+    sums = [r for r in STRICT_REPORT if r["cls"] == "sum" and not r.get("band")]
     if len(sums) < 20:
         pytest.skip("only part of the suite ran")
     entries = sum(r["entries"] for r in sums)
