@@ -72,6 +72,7 @@ int env_int(const char *name, int dflt) {
 //   persist=P   1 / 0: persistent grid / one workgroup per unit for the materialising walk
 //   packed=0    cooperative kernels also for short series (the wave-per-series ones are default)
 //   stamps=M    the diagnostic timing build's mask (IssArgs::debug), dbg_bytes=B its stamp buffer
+//   wt=0        static programs keep plain output stores (no write-through instance)
 // Nothing here changes a result; the product reads none of them in normal operation.
 int debug_knob(const char *name, int dflt) {
   const char *v = std::getenv("FRUITS_HIP_DEBUG");
@@ -463,7 +464,7 @@ extern "C" {
 
 const char *fr_last_error(void) { return g_err.c_str(); }
 
-int fr_version(void) { return 134; }
+int fr_version(void) { return 135; }
 
 int fr_device_count(void) {
   int n = 0;
@@ -1220,6 +1221,7 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   const int64_t resident = auto_groups ? query_resident(p, N, T, fu != nullptr, vec_ok_pre) : 0;
   fr::GroupedProgram *gpp = nullptr;
   int static_lds_pad = 0;
+  int static_wt = 0;                        // 1: the ahead-of-time program's write-through instance
   int static_prog = 0;                      // > 0: ahead-of-time program, -1: run-time compiled
   const fr::JitProgram *jit_prog = nullptr;
   {
@@ -1285,6 +1287,18 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
           }
         }
       }
+      // Cache policy of the output stores (walk_static_inst.hip: sc1 for one group, nt sc1 for
+      // three).  A plain store leaves its line dirty in the XCD's 4 MiB L2 and the launch ends
+      // with a write-back of up to 32 MiB that nothing overlaps; a write-through store sends the
+      // bytes out during the body.  Measured (of_weight(2,3), T = 1024, back-to-back us, plain ->
+      // policy, same box, three rounds): one group + nt input, N = 1536 40.5 -> 39.4, 2048
+      // 57.4 -> 54.8 (nt sc1 there: 64.8); three groups, N = 3072 93.5 -> 79.3, 8192 248 -> 193
+      // (sc1 there: 91.4, 245; at N = 2048 three groups + nt sc1 reach 61.3, behind one group).
+      // So: one group in the cache-sized window, three groups where the batch streams through
+      // HBM; small batches (unmeasured) and two-group programs keep plain stores.
+      // FRUITS_HIP_DEBUG wt=0 turns it off (A/B of one build).
+      if (static_prog > 0 && debug_knob("wt", 1) != 0)
+        static_wt = (static_groups == 1 && cache_sized) || (static_groups == 3 && static_lds_pad != 0);
     }
     const int G = static_prog ? static_groups
                               : (auto_groups ? choose_groups_walk(p, N, T, resident, fu != nullptr) : shape.G);
@@ -1404,6 +1418,7 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   }
   a.static_prog = static_prog > 0 ? static_prog : 0;
   a.lds_pad = static_lds_pad;
+  a.wt = static_wt;
   // Materialising launches of the interpreter's plans run through the fused walk's node loop with
   // a store epilogue (walk_fused.h, MODE 2: half the instructions per node) whenever that walk
   // covers the plan: chunk carries in LDS, no letter sums (Arctic argmax).

@@ -25,7 +25,7 @@ namespace fr {
 // (E = 2: 1 KiB per instruction) and only NW wave totals cross waves.
 template <int E_, int P_, int MAXLV_, int MULTI_, bool VEC_, bool WEIGHTED_, int TEAM_ = 4,
           int MODE_ = 0, int SEMI_ = 0, bool NT_ = false, bool TOTALINC_ = false,
-          bool HIGHORD_ = false>
+          bool HIGHORD_ = false, int WT_ = 0>
 struct WalkCfg {
   // TOTALINC: fused epilogue of a TOTALLY weighted plan with differencing sieves - the
   // increments need the weight one step to the left (previous_weighted).  Its own
@@ -39,6 +39,11 @@ struct WalkCfg {
   // NT: the rows of X are staged with non-temporal loads (load_input; the host asks for it
   // when every row is read once per launch and the batch is about the size of the cache)
   static constexpr bool NT = NT_;
+  // WT: cache policy of the full-chunk 16-byte stores of the (K,N,T) tensor (emit_store): 0 a
+  // plain global store; otherwise the policy operand of a buffer store (kStoreSc1 = write-through,
+  // the line is not kept dirty in the XCD's L2; kStoreNtSc1 = the same, non-temporal).  Ragged
+  // chunks keep plain 8- and 16-byte stores; feature rows of the fused walk never use it.
+  static constexpr int WT = WT_;
   // SEMI 0: Reals (+, x) with an exclusive shift between letters; SEMI 1: Arctic
   // (max, +), letters add el * x and children continue from the INCLUSIVE maximum;
   // SEMI 2: Bayesian (max, x): the letters and weights of Reals, the scan of Arctic
@@ -270,6 +275,21 @@ __device__ __forceinline__ void block_scan(WalkCtx &cx, const double (&s)[C::EP]
   STAMP(cx, 4);  // cross-wave prefix + final adds
 }
 
+// Cache-policy operands of a gfx950 buffer store (WalkCfg::WT): sc1 writes through the XCD's L2
+// instead of leaving the line dirty there; nt sc1 also marks it non-temporal
+constexpr int kStorePlain = 0, kStoreSc1 = 16, kStoreNtSc1 = 18;
+
+typedef unsigned int vu4 __attribute__((ext_vector_type(4)));
+
+// 16 bytes of output with the cache policy WT: `rs` is a wave-uniform descriptor of the output
+// bytes, `off` the lane's byte offset in them
+template <int WT>
+__device__ __forceinline__ void store_policy(__amdgpu_buffer_rsrc_t rs, uint32_t off, vd2 v) {
+  vu4 bits;
+  __builtin_memcpy(&bits, &v, 16);
+  __builtin_amdgcn_raw_buffer_store_b128(bits, rs, off, 0, WT);
+}
+
 template <class C>
 __device__ __forceinline__ void emit_store(const WalkCtx &cx, const double (&v)[C::EP],
                                            double *dst) {
@@ -283,6 +303,20 @@ __device__ __forceinline__ void emit_store(const WalkCtx &cx, const double (&v)[
     if (cx.full_chunk) {
       // the common case, decided once per chunk: no per-lane bounds checks (each would
       // cost an exec-mask save / branch / restore around every store)
+      if constexpr (C::WT != kStorePlain) {
+        // one descriptor per row: `dst` is wave-uniform and the chunk's CHUNK elements are in
+        // bounds (stride 0, size in bytes; 0x20000: dword 3 of a raw gfx9 buffer, 32-bit format)
+        const __amdgpu_buffer_rsrc_t rs =
+            __builtin_amdgcn_make_buffer_rsrc(dst, 0, C::CHUNK * (int)sizeof(double), 0x00020000);
+#pragma unroll
+        for (int h = 0; h < P; ++h) {
+          const int idx = cx.wave * C::SPAN + h * C::PIECE + cx.lane * E;
+#pragma unroll
+          for (int e = 0; e < E; e += 2)
+            store_policy<C::WT>(rs, (uint32_t)(idx + e) * 8u, vd2{v[h * E + e], v[h * E + e + 1]});
+        }
+        return;
+      }
 #pragma unroll
       for (int h = 0; h < P; ++h) {
         const int idx = cx.wave * C::SPAN + h * C::PIECE + cx.lane * E;

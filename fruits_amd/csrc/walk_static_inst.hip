@@ -49,9 +49,23 @@ hipError_t walk_static_launch(const IssArgs &a, hipStream_t st) {
   return kStaticTable[a.static_prog - 1].launch(a, st);
 }
 #else
+// Two instances per program: plain output stores, and the cache policy that the program's group
+// count was measured to gain from in the window where the host asks for it (IssArgs::wt,
+// capi.cpp run_walk): one group (cache-sized batches, non-temporal input) writes through the L2
+// (sc1); three groups (batches that stream through HBM, plain input loads shared by the sibling
+// groups) write through and non-temporal (nt sc1).  Two-group programs keep plain stores only.
+template <int G>
+constexpr int static_store_policy() {
+  return G == 1 ? kStoreSc1 : (G == 3 ? kStoreNtSc1 : kStorePlain);
+}
+
 hipError_t SP_CAT(walk_static_launch_, STATIC_PROG)(const IssArgs &a, hipStream_t st) {
-  return launch_walk_static<WalkCfg<2, 2, 2, 0, true, false, 4, 0, 0>,
-                            SP_CAT(StaticProg, STATIC_PROG)>(a, st);
+  using PG = SP_CAT(StaticProg, STATIC_PROG);
+  constexpr int wt = static_store_policy<PG::groups>();
+  if constexpr (wt != kStorePlain) {
+    if (a.wt) return launch_walk_static<WalkCfg<2, 2, 2, 0, true, false, 4, 0, 0, false, false, false, wt>, PG>(a, st);
+  }
+  return launch_walk_static<WalkCfg<2, 2, 2, 0, true, false, 4, 0, 0>, PG>(a, st);
 }
 #endif
 

@@ -1,9 +1,10 @@
-"""Diagnostic (timing build): per-segment s_memtime shares of the walk kernel."""
+"""Diagnostic (timing build): per-segment s_memtime shares of the walk kernel.  DBG_KNOBS: further
+FRUITS_HIP_DEBUG knobs, e.g. ",wt=0"."""
 import os, sys
 import numpy as np
 sys.path.insert(0, '.')
 os.environ["FRUITS_HIP_DEBUG"] = (f"stamps={16 | int(os.environ.get('DBG_EXTRA', '0'))},dbg_bytes={1 << 22},"
-                                  f"persist={os.environ.get('DBG_PERSIST', '1')}")
+                                  f"persist={os.environ.get('DBG_PERSIST', '1')}" + os.environ.get("DBG_KNOBS", ""))
 import torch
 import fruits_amd as fr
 from fruits_amd import _native as nat
