@@ -39,6 +39,7 @@ EXPORTS = [
     "fr_plan_prepare", "fr_pipeline_prepare", "fr_pipeline_compile_plan", "fr_pipeline_prepare_cached", "fr_pipeline_bundle", "fr_plan_fits", "fr_release_scratch",
     "fr_pipeline_set_preparation", "fr_pipeline_set_series_cuts", "fr_pipeline_set_argmax", "fr_arctic_argmax", "fr_coswiss_set_dropout",
     "fr_coswiss_set_input_stride", "fr_coswiss_ffn",
+    "fr_prep_fir", "fr_prep_project", "fr_prep_normalize", "fr_prep_leadlag",
 ]
 
 _lib = None
@@ -872,4 +873,101 @@ def arctic_argmax(Vd, word_lengths) -> "object":
     check(lib().fr_arctic_argmax(dptr(Vd), C.c_int64(rows), C.c_int64(N), C.c_int64(T),
                                  C.c_int32(len(jobs)), dptr(jd), dptr(P), dptr(out), stream_ptr()),
           "fr_arctic_argmax")
+    return out
+
+
+# ----------------------------------------------------------------------- preparateurs
+def _rows3(Xd):
+    t = torch()
+    if Xd.dtype != t.float64 or Xd.dim() != 3 or not Xd.is_contiguous():
+        raise TypeError("X must be a contiguous float64 (N, D, T) device tensor")
+    return (int(v) for v in Xd.shape)
+
+
+def _prep_out(out, shape, like):
+    """The output tensor of a preparateur entry: ``out`` if given (checked), else a new one."""
+    t = torch()
+    if out is None:
+        return t.empty(shape, dtype=like.dtype, device=like.device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or not out.is_contiguous() \
+            or out.device != like.device:
+        raise TypeError(f"out must be a contiguous float64 device tensor of shape {tuple(shape)}")
+    return out
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+
+
+def prep_fir(Xd, kernel_d, w: int, ndim_d, dims_d, ndim_h, dims_h, adaptive: bool = False,
+             out=None):
+    """fr_prep_fir, mode 0 (RIN): ``kernel_d`` (J, w), ``ndim_d`` (O) and ``dims_d`` (J) device
+    tensors, ``ndim_h`` / ``dims_h`` the same tables as int32 host arrays (checked by the
+    library).  Returns (N, O, T)."""
+    N, D, T = _rows3(Xd)
+    nh = np.ascontiguousarray(ndim_h, dtype=np.int32)
+    dh = np.ascontiguousarray(dims_h, dtype=np.int32)
+    out = _prep_out(out, (N, nh.size, T), Xd)
+    check(lib().fr_prep_fir(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(kernel_d),
+                            C.c_int32(dh.size), C.c_int32(int(w)), dptr(ndim_d), C.c_int32(nh.size),
+                            dptr(dims_d), _i32p(nh), _i32p(dh), C.c_int32(0),
+                            C.c_int32(1 if adaptive else 0), dptr(out), stream_ptr()), "fr_prep_fir")
+    return out
+
+
+def prep_moving_average(Xd, w: int, out=None):
+    """fr_prep_fir, mode 1 (MAV): 1 <= w <= T."""
+    N, D, T = _rows3(Xd)
+    out = _prep_out(out, (N, D, T), Xd)
+    check(lib().fr_prep_fir(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), None, C.c_int32(0),
+                            C.c_int32(int(w)), None, C.c_int32(0), None, None, None, C.c_int32(1),
+                            C.c_int32(0), dptr(out), stream_ptr()), "fr_prep_fir")
+    return out
+
+
+def prep_project(Xd, kernel_d, bias_d, ndim_d, dims_d, ndim_h, dims_h, out=None):
+    """fr_prep_project without a hidden layer (JLD); tables as in ``prep_fir``."""
+    N, D, T = _rows3(Xd)
+    nh = np.ascontiguousarray(ndim_h, dtype=np.int32)
+    dh = np.ascontiguousarray(dims_h, dtype=np.int32)
+    out = _prep_out(out, (N, nh.size, T), Xd)
+    check(lib().fr_prep_project(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(kernel_d),
+                                dptr(bias_d), dptr(ndim_d), C.c_int32(nh.size), dptr(dims_d),
+                                C.c_int32(dh.size), _i32p(nh), _i32p(dh), None, None, None,
+                                C.c_int32(0), C.c_int32(0), dptr(out), stream_ptr()),
+          "fr_prep_project")
+    return out
+
+
+def prep_ffn(Xd, W1_d, b1_d, W2_d, center: bool, relu_out: bool, out=None):
+    """fr_prep_project with a hidden layer (FFN): ``W1_d`` (hidden, D), ``b1_d`` (hidden),
+    ``W2_d`` (O, hidden) device tensors."""
+    N, D, T = _rows3(Xd)
+    hidden, O = int(W1_d.shape[0]), int(W2_d.shape[0])
+    if tuple(W1_d.shape) != (hidden, D) or tuple(b1_d.shape) != (hidden,) \
+            or tuple(W2_d.shape) != (O, hidden) or hidden < 1:
+        raise ValueError("FFN weights do not match the input dimensions")
+    out = _prep_out(out, (N, O, T), Xd)
+    check(lib().fr_prep_project(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), None, None, None,
+                                C.c_int32(O), None, C.c_int32(0), None, None, dptr(W1_d), dptr(b1_d),
+                                dptr(W2_d), C.c_int32(hidden),
+                                C.c_int32((1 if center else 0) | (2 if relu_out else 0)), dptr(out),
+                                stream_ptr()), "fr_prep_project")
+    return out
+
+
+def prep_normalize(Xd, scale_dim: bool, out=None):
+    N, D, T = _rows3(Xd)
+    out = _prep_out(out, (N, D, T), Xd)
+    check(lib().fr_prep_normalize(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
+                                  C.c_int32(1 if scale_dim else 0), dptr(out), stream_ptr()),
+          "fr_prep_normalize")
+    return out
+
+
+def prep_leadlag(Xd, out=None):
+    N, D, T = _rows3(Xd)
+    out = _prep_out(out, (N, 2 * D, 2 * T - 1), Xd)
+    check(lib().fr_prep_leadlag(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(out),
+                                stream_ptr()), "fr_prep_leadlag")
     return out

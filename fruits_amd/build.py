@@ -23,12 +23,15 @@ HEADERS = ["kernels.h", "plan.h", "jit.h", "walk.h", "walk_device.h", "walk_fuse
 
 
 # headers that only some units include: {header: unit names}
-LOCAL_HEADERS = {"pairwise.h": ("kernels_misc",)}
+LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep")}
 
 
 def units():
     """(object name, source, extra flags)"""
-    out = [("kernels_misc", "kernels_misc.hip", []), ("plan", "plan.cpp", []),
+    out = [("kernels_misc", "kernels_misc.hip", []),
+           # the preparateurs: no contraction either - NRM and LAG are compared bit for bit, and
+           # the sums of RIN / MAV / JLD / FFN round every product like the reference
+           ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
            ("capi", "capi.cpp", []), ("jit", "jit.cpp", []),
            ("walk_static_reg", "walk_static_inst.hip", ["-DSTATIC_REGISTRY"])]
     # The walks: no a*b+c contraction - the reference rounds a letter's product before the

@@ -2769,4 +2769,116 @@ int fr_coswiss_combine(const double *d_terms, int64_t n_terms, int64_t N, int64_
   return FR_OK;
 }
 
+// ---------------------------------------------------------------- preparateurs (kernels_prep.hip)
+namespace {
+// the grouping tables of RIN / JLD on the host: every entry is checked before a kernel reads
+// the device copies
+int check_groups(const char *who, const int32_t *h_ndim, int32_t O, const int32_t *h_dims,
+                 int32_t J, int64_t D) {
+  const std::string w(who);
+  if (!h_ndim || !h_dims) return fail(FR_E_ARG, w + ": null host table");
+  int64_t total = 0;
+  for (int32_t o = 0; o < O; ++o) {
+    if (h_ndim[o] < 0) return fail(FR_E_ARG, w + ": negative group size");
+    total += h_ndim[o];
+  }
+  if (total != J) return fail(FR_E_ARG, w + ": the group sizes do not add up to the number of slots");
+  for (int32_t j = 0; j < J; ++j)
+    if (h_dims[j] < 0 || h_dims[j] >= D)
+      return fail(FR_E_DIM, w + ": slot " + std::to_string(j) + " names dimension " +
+                                std::to_string(h_dims[j]) + " of " + std::to_string(D));
+  return FR_OK;
+}
+}  // namespace
+
+int fr_prep_fir(const double *d_X, int64_t N, int64_t D, int64_t T, const double *d_kernel,
+                int32_t J, int32_t w, const int32_t *d_ndim, int32_t O, const int32_t *d_dims,
+                const int32_t *h_ndim, const int32_t *h_dims, int32_t mode, int32_t adaptive,
+                double *d_out, void *stream) {
+  if (N < 0 || D < 1 || T < 1 || w < 0 || (mode != 0 && mode != 1))
+    return fail(FR_E_ARG, "fr_prep_fir: bad shape");
+  if (mode == 1) {
+    if (w < 1 || w > T) return fail(FR_E_ARG, "fr_prep_fir: a moving average wider than the series");
+    O = (int32_t)D;
+    if (D > 0x7fffffffLL) return fail(FR_E_LIMIT, "fr_prep_fir: too many dimensions");
+  } else {
+    if (J < 1 || O < 1 || J > D)
+      return fail(FR_E_ARG, "fr_prep_fir: 1 <= slots <= D (slot j adds dimension j itself)");
+    if (!adaptive && w >= T) return fail(FR_E_ARG, "fr_prep_fir: the kernel must be shorter than the series");
+    const int rc = check_groups("fr_prep_fir", h_ndim, O, h_dims, J, D);
+    if (rc != FR_OK) return rc;
+    if ((w > 0 && !d_kernel) || !d_ndim || !d_dims)
+      return fail(FR_E_ARG, "fr_prep_fir: null device pointer");
+  }
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || d_X == d_out) return fail(FR_E_ARG, "fr_prep_fir: null or aliased device pointer");
+  hipError_t e = fr::launch_prep_fir(d_X, N, D, T, d_kernel, w, d_ndim, O, d_dims, mode,
+                                     adaptive ? 1 : 0, d_out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(FR_E_LIMIT, "fr_prep_fir: grid too large");
+  }
+  if (e != hipSuccess) return hip_fail(e, "prep fir launch");
+  return FR_OK;
+}
+
+int fr_prep_project(const double *d_X, int64_t N, int64_t D, int64_t T, const double *d_kernel,
+                    const double *d_bias, const int32_t *d_ndim, int32_t O, const int32_t *d_dims,
+                    int32_t J, const int32_t *h_ndim, const int32_t *h_dims, const double *d_W1,
+                    const double *d_b1, const double *d_W2, int32_t hidden, int32_t flags,
+                    double *d_out, void *stream) {
+  if (N < 0 || D < 1 || T < 1 || O < 1 || hidden < 0 || D > 0x7fffffffLL)
+    return fail(FR_E_ARG, "fr_prep_project: bad shape");
+  if (hidden == 0) {
+    if (J < 0) return fail(FR_E_ARG, "fr_prep_project: bad shape");
+    const int rc = check_groups("fr_prep_project", h_ndim, O, h_dims, J, D);
+    if (rc != FR_OK) return rc;
+    if (!d_kernel || !d_bias || !d_ndim || !d_dims)
+      return fail(FR_E_ARG, "fr_prep_project: null device pointer");
+  } else {
+    if (D > 16 || O > 16)
+      return fail(FR_E_LIMIT, "fr_prep_project: a hidden layer between at most 16 input and 16 output dimensions");
+    if (!d_W1 || !d_b1 || !d_W2) return fail(FR_E_ARG, "fr_prep_project: null device pointer");
+  }
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || d_X == d_out) return fail(FR_E_ARG, "fr_prep_project: null or aliased device pointer");
+  hipError_t e = fr::launch_prep_project(d_X, N, D, T, d_kernel, d_bias, d_ndim, O, d_dims, d_W1, d_b1,
+                                         d_W2, hidden, flags, d_out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(FR_E_LIMIT, "fr_prep_project: grid too large");
+  }
+  if (e != hipSuccess) return hip_fail(e, "prep project launch");
+  return FR_OK;
+}
+
+int fr_prep_normalize(const double *d_X, int64_t N, int64_t D, int64_t T, int32_t scale_dim,
+                      double *d_out, void *stream) {
+  if (N < 0 || D < 1 || T < 1) return fail(FR_E_ARG, "fr_prep_normalize: bad shape");
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || d_X == d_out) return fail(FR_E_ARG, "fr_prep_normalize: null or aliased device pointer");
+  hipError_t e = scale_dim ? fr::launch_prep_normalize(d_X, N, D * T, d_out, (hipStream_t)stream)
+                           : fr::launch_prep_normalize(d_X, N * D, T, d_out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(FR_E_LIMIT, "fr_prep_normalize: grid too large");
+  }
+  if (e != hipSuccess) return hip_fail(e, "prep normalize launch");
+  return FR_OK;
+}
+
+int fr_prep_leadlag(const double *d_X, int64_t N, int64_t D, int64_t T, double *d_out,
+                    void *stream) {
+  if (N < 0 || D < 1 || T < 1) return fail(FR_E_ARG, "fr_prep_leadlag: bad shape");
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || d_X == d_out) return fail(FR_E_ARG, "fr_prep_leadlag: null or aliased device pointer");
+  hipError_t e = fr::launch_prep_leadlag(d_X, N * D, T, d_out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(FR_E_LIMIT, "fr_prep_leadlag: grid too large");
+  }
+  if (e != hipSuccess) return hip_fail(e, "prep leadlag launch");
+  return FR_OK;
+}
+
 }  // extern "C"

@@ -75,5 +75,19 @@ hipError_t launch_arctic_argmax(const double *V, int64_t rows, int64_t N, int64_
                                 const int32_t *jobs, double *P, double *out, hipStream_t st);
 hipError_t launch_row_stats(const double *X, int64_t N, int64_t D, int64_t T, const int32_t *prep,
                             int n_prep, int div_std, double eps, double *stats, hipStream_t st);
+// the preparateurs of kernels_prep.hip (RIN / MAV, JLD / FFN, NRM, LAG); hipErrorInvalidValue:
+// a grid limit, or an FFN of more than 16 input / output dimensions
+hipError_t launch_prep_fir(const double *X, int64_t N, int64_t D, int64_t T, const double *taps,
+                           int w, const int32_t *ndim, int O, const int32_t *dims, int mode,
+                           int adaptive, double *out, hipStream_t st);
+hipError_t launch_prep_project(const double *X, int64_t N, int64_t D, int64_t T,
+                               const double *kernel, const double *bias, const int32_t *ndim, int O,
+                               const int32_t *dims, const double *W1, const double *b1,
+                               const double *W2, int hidden, int flags, double *out,
+                               hipStream_t st);
+hipError_t launch_prep_normalize(const double *X, int64_t rows, int64_t len, double *out,
+                                 hipStream_t st);
+hipError_t launch_prep_leadlag(const double *X, int64_t rows, int64_t T, double *out,
+                               hipStream_t st);
 
 }  // namespace fr

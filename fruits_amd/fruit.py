@@ -409,7 +409,12 @@ class FruitSlice:
         for prep in self._preparateurs:
             prep._cache = cache
             if fit_on is not None:
-                prep.fit(nat.to_host(Xd) if prep._fit_needs_data() else fit_on)
+                if prep._fit_needs_data():
+                    prep.fit(nat.to_host(Xd))
+                elif prep._fit_needs_shape():
+                    prep.fit(np.broadcast_to(0.0, tuple(int(v) for v in Xd.shape)))
+                else:
+                    prep.fit(fit_on)
             Xd = prep._transform_device(Xd)
             for cb in callbacks:
                 cb.on_preparateur(nat.to_host(Xd))

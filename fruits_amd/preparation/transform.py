@@ -1,16 +1,22 @@
-"""Preparateurs on the MI355X path (mirrors the INC / STD part of
+"""Preparateurs on the MI355X path (mirrors INC, STD, NRM, MAV, LAG, FFN, RIN and JLD of
 fruits/preparation/transform.py).  Each runs as a HIP kernel on device
-tensors; the numpy-facing ``transform`` uploads, runs and downloads."""
+tensors; the numpy-facing ``transform`` uploads, runs and downloads.
+
+The fitted preparateurs (MAV, FFN, RIN, JLD) draw their state in ``_fit`` from numpy's GLOBAL
+generator with the reference's calls in the reference's order, so ``np.random.seed(s)`` followed
+by ``fit`` gives the reference's state bit for bit.  Their fits look at ``X.shape`` only
+(``_fit_needs_shape``): a fruit hands them a zero-copy stand-in of the prepared shape instead of
+downloading the prepared fit sample."""
 from __future__ import annotations
 
-from typing import Any, Callable, Union
+from typing import Any, Callable, Optional, Union
 
 import numpy as np
 
 from .. import _native as nat
 from .abstract import Preparateur
 
-__all__ = ["INC", "STD"]
+__all__ = ["INC", "STD", "NRM", "MAV", "LAG", "FFN", "RIN", "JLD"]
 
 
 class INC(Preparateur):
@@ -107,3 +113,350 @@ class STD(Preparateur):
 
     def __str__(self) -> str:
         return f"STD({self._separately}, {self._div_std})"
+
+
+class _ShapeFitted(Preparateur):
+    """A preparateur whose ``fit`` reads ``X.shape`` alone and whose fitted tables live on the
+    device once per fit (``_programs``: dropped when pickled, like a plan)."""
+
+    def _fit_needs_data(self) -> bool:
+        return False
+
+    def _fit_needs_shape(self) -> bool:
+        return True
+
+    def fit(self, X: np.ndarray) -> None:
+        super().fit(X)
+        self._programs = {}
+
+    def _fresh_transients(self) -> None:
+        self._programs = {}
+
+    def _device_tables(self, Xd, *host, ints: int = 0):
+        """Device copies of the fitted host arrays ``host`` (float64; the last ``ints`` of them
+        int32), uploaded once per device for as long as the preparateur holds these very arrays
+        (state assigned after a fit is seen)."""
+        progs = self.__dict__.setdefault("_programs", {})
+        key = str(Xd.device)
+        held = progs.get(key)
+        if held is None or len(held[0]) != len(host) or any(a is not b for a, b in zip(held[0], host)):
+            kinds = [np.float64] * (len(host) - ints) + [np.int32] * ints
+            held = progs[key] = (host, tuple(
+                nat.to_device(np.ascontiguousarray(a, dtype=k), dtype=k)
+                for a, k in zip(host, kinds)))
+        return held[1]
+
+
+class NRM(Preparateur):
+    """Normalisation ``(x - min) / (max - min)`` per series and dimension, or with
+    ``scale_dim=True`` per series over all its dimensions; constant rows become 0
+    (fruits/preparation/transform.py:161-209)."""
+
+    def __init__(self, scale_dim: bool = False) -> None:
+        self._scale_dim = scale_dim
+
+    @property
+    def requires_fitting(self) -> bool:
+        return False
+
+    def _transform_device(self, Xd):
+        return nat.prep_normalize(Xd, bool(self._scale_dim))
+
+    def _copy(self) -> "NRM":
+        return NRM(scale_dim=self._scale_dim)
+
+    def __eq__(self, other: Any) -> bool:
+        return isinstance(other, NRM) and self._scale_dim == other._scale_dim
+
+    def __str__(self) -> str:
+        return f"NRM({self._scale_dim})"
+
+
+class MAV(_ShapeFitted):
+    """Moving average over ``width`` time steps, a float being a fraction of the series
+    length (fruits/preparation/transform.py:212-274)."""
+
+    def __init__(self, width: Union[int, float] = 5) -> None:
+        if isinstance(width, float) and not 0.0 < width < 1.0:
+            raise ValueError("If width is a float, it has to be in (0,1)")
+        self._w_given = width
+
+    def _fit(self, X: np.ndarray) -> None:
+        given = self._w_given
+        if isinstance(given, float):       # a fraction of the series length, at least one step
+            self._w = max(int(given * X.shape[2]), 1)
+        elif given > 0:
+            self._w = given
+        # width -1 never gets a width here (transform.py:250-256): transform then raises
+
+    def _check_fitted(self) -> None:
+        if not hasattr(self, "_w"):
+            raise RuntimeError("Missing call of self.fit()")
+
+    def _transform_device(self, Xd):
+        self._check_fitted()
+        if int(self._w) > int(Xd.shape[2]):      # no window fits the series: all zeros (:237)
+            return nat.torch().zeros_like(Xd)
+        return nat.prep_moving_average(Xd, int(self._w))
+
+    def _copy(self) -> "MAV":
+        return MAV(self._w_given)
+
+    def __eq__(self, other: Any) -> bool:
+        return isinstance(other, MAV) and self._w_given == other._w_given
+
+    def __str__(self) -> str:
+        return f"MAV({self._w_given})"
+
+
+class LAG(Preparateur):
+    """Lead-lag transform: every dimension ``[x_1, ..., x_n]`` becomes the two dimensions
+    ``[x_1, x_2, x_2, ..., x_n]`` and ``[x_1, x_1, x_2, ..., x_n]`` of length ``2n - 1``
+    (fruits/preparation/transform.py:277-309)."""
+
+    @property
+    def requires_fitting(self) -> bool:
+        return False
+
+    def _transform_device(self, Xd):
+        return nat.prep_leadlag(Xd)
+
+    def _copy(self) -> "LAG":
+        return LAG()
+
+    def __eq__(self, other: Any) -> bool:
+        return isinstance(other, LAG)
+
+    def __str__(self) -> str:
+        return "LAG()"
+
+
+class FFN(_ShapeFitted):
+    """Two-layer feed-forward network with gaussian weights applied to every time step:
+    ``W2 relu(W1 (x - mean) + b)`` (fruits/preparation/transform.py:312-388).
+
+    Args:
+        d_out: number of output dimensions.
+        d_hidden: nodes of the hidden layer, ``2 * input dimensions`` if None.
+        center: subtract every dimension's mean over time first.
+        relu_out: a ReLU on the output too.
+    """
+
+    def __init__(self, d_out: int = 1, d_hidden: Optional[int] = None, center: bool = True,
+                 relu_out: bool = False) -> None:
+        self._d_hidden = d_hidden
+        self._d_out = d_out
+        self._center = center
+        self._relu_out = relu_out
+
+    def _fit(self, X: np.ndarray) -> None:
+        n_in = X.shape[1]
+        hidden = 2 * n_in if self._d_hidden is None else self._d_hidden
+        # three gaussian draws in the reference's order: first layer, its biases, second layer
+        # (transform.py:346-360)
+        shapes = ((hidden, n_in), (hidden, ), (self._d_out, hidden))
+        self._weights1, self._biases, self._weights2 = (
+            np.random.normal(loc=0, scale=1.0, size=shape) for shape in shapes)
+
+    def _check_fitted(self) -> None:
+        if not hasattr(self, "_weights1"):
+            raise RuntimeError("FFN was not fitted")
+
+    def _transform_device(self, Xd):
+        self._check_fitted()
+        W1, b, W2 = self._device_tables(Xd, self._weights1, self._biases, self._weights2)
+        return nat.prep_ffn(Xd, W1, b, W2, bool(self._center), bool(self._relu_out))
+
+    def _copy(self) -> "FFN":
+        return FFN(d_out=self._d_out, d_hidden=self._d_hidden, center=self._center,
+                   relu_out=self._relu_out)
+
+    def __str__(self) -> str:
+        return f"FFN({self._d_out}, {self._d_hidden}, {self._center}, {self._relu_out})"
+
+
+def _spread(n_in: int, n_out: int) -> np.ndarray:
+    """Sizes of ``n_out`` groups that share ``n_in`` slots as evenly as possible, the larger
+    groups first (transform.py:495-504, 694-703); more groups than slots is an error."""
+    if n_out > n_in:
+        raise ValueError(f"Output dimensions ({n_out}) should be <= input dimensions ({n_in})")
+    small, larger = divmod(n_in, n_out)
+    sizes = np.full(n_out, small, dtype=np.int32)
+    sizes[:larger] += 1
+    return sizes
+
+
+def _shuffled_dims(n_in: int) -> np.ndarray:
+    """A random order of the input dimensions: one ``np.random.choice`` without replacement,
+    the reference's call (transform.py:505-507, 704-706)."""
+    return np.random.choice(n_in, size=n_in, replace=False).astype(np.int32)
+
+
+def _draw_centred(rows: int, width: int) -> np.ndarray:
+    """Standard-normal weights, every row shifted to mean zero."""
+    weights = np.random.normal(size=(rows, width))
+    return weights - weights.mean(axis=1, keepdims=True)
+
+
+def _draw_sum_one(rows: int, width: int) -> np.ndarray:
+    """Uniform weights on [-1, 1] pushed so that every row sums to one without leaving the
+    interval: what a row lacks is handed out in proportion to each weight's distance from the
+    border, so weights near zero move most.  A draw with a row that has (almost) no room left is
+    thrown away and drawn again."""
+    while True:
+        weights = np.random.uniform(-1., 1., size=(rows, width))
+        room = 1.0 - np.abs(weights)
+        row_room = np.sum(room, axis=1)
+        if not np.any(row_room < 1e-5):
+            lacking = 1.0 - np.sum(weights, axis=1)
+            return weights + room * (lacking / row_room)[:, np.newaxis]
+
+
+class RIN(_ShapeFitted):
+    """Random increments ``y_i = x_i - (k_w x_{i-1} + ... + k_1 x_{i-w})`` with a kernel drawn
+    in ``fit`` (fruits/preparation/transform.py:391-568).
+
+    Args:
+        width: kernel length (shortened to ``T - 1``), or a callable of the series length.
+        adaptive_width: the input counts as padded with ``width`` zeros, so the first outputs
+            use a truncated kernel instead of being zero.
+        out_dim: number of output dimensions (<= input dimensions), each convolving a nearly
+            equal share of randomly chosen input dimensions; -1: as many as the input has.
+        force_sum_one: uniform weights on [-1, 1] forced to sum to one instead of centred
+            gaussian weights.
+        kernel: a fixed ``(D, w)`` kernel; everything but ``adaptive_width`` is then ignored.
+    """
+
+    def __init__(self, width: Union[int, Callable[[int], int]] = 1, adaptive_width: bool = False,
+                 out_dim: int = -1, force_sum_one: bool = False,
+                 kernel: Optional[np.ndarray] = None) -> None:
+        self._width = width
+        self._adaptive_width = adaptive_width
+        self._out_dim = out_dim
+        self._force_sum_one = force_sum_one
+        self._const_kernel = kernel
+
+    def _fit(self, X: np.ndarray) -> None:
+        n_in, length = int(X.shape[1]), int(X.shape[2])
+        if self._const_kernel is not None:
+            # a given kernel: one slot per dimension, in order; everything but adaptive_width
+            # is ignored and nothing is drawn (transform.py:485-489)
+            self._kernel = self._const_kernel.copy()
+            self._ndim_per_kernel = np.ones(n_in, dtype=np.int32)
+            self._dims_per_kernel = np.arange(n_in, dtype=np.int32)
+            return
+        if callable(self._width):
+            width = self._width(length)
+        else:
+            width = min(self._width, length - 1)      # (shortened to T - 1)
+        self._ndim_per_kernel = _spread(n_in, self._out_dim if self._out_dim > 0 else n_in)
+        # the reference's draws in its order: the dimension order, then the weights
+        # (transform.py:505-523)
+        self._dims_per_kernel = _shuffled_dims(n_in)
+        draw = _draw_sum_one if self._force_sum_one else _draw_centred
+        self._kernel = draw(n_in, width)
+
+    def _check_fitted(self) -> None:
+        if not hasattr(self, "_kernel"):
+            raise RuntimeError("RIN preparateur misses a .fit() call")
+
+    def _transform_device(self, Xd):
+        self._check_fitted()
+        t = nat.torch()
+        N, D, T = (int(v) for v in Xd.shape)
+        kernel = np.ascontiguousarray(self._kernel, dtype=np.float64)
+        ndim = np.ascontiguousarray(self._ndim_per_kernel, dtype=np.int32)
+        dims = np.ascontiguousarray(self._dims_per_kernel, dtype=np.int32)
+        if kernel.ndim != 2 or kernel.shape[0] < dims.size:
+            raise ValueError("RIN kernel has to be a (dimensions, width) array")
+        w = int(kernel.shape[1])
+        if not self._adaptive_width and w >= T:
+            # no output index reaches the kernel's width (transform.py:460): all zeros
+            return t.zeros((N, ndim.size, T), dtype=Xd.dtype, device=Xd.device)
+        kd, nd, dd = self._device_tables(Xd, self._kernel, self._ndim_per_kernel,
+                                         self._dims_per_kernel, ints=2)
+        return nat.prep_fir(Xd, kd, w, nd, dd, ndim, dims, bool(self._adaptive_width))
+
+    def _copy(self) -> "RIN":
+        return RIN(width=self._width, adaptive_width=self._adaptive_width, out_dim=self._out_dim,
+                   force_sum_one=self._force_sum_one, kernel=self._const_kernel)
+
+    def _settings(self) -> tuple:
+        return (self._width, self._adaptive_width, self._out_dim, self._force_sum_one)
+
+    def __eq__(self, other: Any) -> bool:
+        if not isinstance(other, RIN) or self._settings() != other._settings():
+            return False
+        # (two given kernel arrays of several weights: the truth value of their ``==`` raises
+        # ValueError, as in the reference - transform.py:560)
+        return bool(self._const_kernel == other._const_kernel)
+
+    def __str__(self) -> str:
+        return (f"RIN({self._width}, {self._adaptive_width}, "
+                f"{self._out_dim}, {self._force_sum_one}, {self._const_kernel})")
+
+
+class JLD(_ShapeFitted):
+    """Johnson-Lindenstrauss dimensionality reduction: every time step is multiplied with
+    random gaussian vectors (fruits/preparation/transform.py:616-746).
+
+    Args:
+        dim: number of output dimensions; a float ``f`` in (0, 1) stands for the smallest
+            integer ``>= 24 log(d) / (3 f^2 - 2 f^3)``.
+        distribute: every output dimension combines only its own nearly equal share of the
+            input dimensions (needs ``input_dim >= output_dim``).
+        bias: add a gaussian bias to every projected dimension.
+    """
+
+    def __init__(self, dim: Union[int, float] = 0.99, distribute: bool = False,
+                 bias: bool = False) -> None:
+        if isinstance(dim, float) and not (0 < dim < 1):
+            raise ValueError("'dim' has to be an integer or a float in (0, 1)")
+        self._d = dim
+        self._distribute = distribute
+        self._bias = bias
+
+    def _output_dims(self, n_in: int) -> int:
+        if not isinstance(self._d, float):
+            return self._d
+        f = self._d       # smallest integer >= 24 log(d) / (3 f^2 - 2 f^3)  (transform.py:688-690)
+        return int(24 * np.log(n_in) / (3 * f**2 - 2 * f**3)) + 1
+
+    def _fit(self, X: np.ndarray) -> None:
+        n_in = int(X.shape[1])
+        n_out = self._output_dims(n_in)
+        # draws in the reference's order: the dimension order when distributing, the weights,
+        # then the bias (transform.py:693-722)
+        if self._distribute:
+            self._ndim_per_kernel = _spread(n_in, n_out)
+            self._dims_per_kernel = _shuffled_dims(n_in)
+            n_weights = n_in
+        else:       # every output dimension reads every input dimension
+            self._ndim_per_kernel = np.full(n_out, n_in, dtype=np.int32)
+            self._dims_per_kernel = np.tile(np.arange(n_in, dtype=np.int32), n_out)
+            n_weights = n_in * n_out
+        self._kernel = np.random.standard_normal(n_weights)
+        self._bias_weights = (np.random.standard_normal(n_out) if self._bias
+                              else np.zeros(n_out, dtype=np.float64))
+
+    def _check_fitted(self) -> None:
+        self._kernel      # (the reference has no check of its own: AttributeError, transform.py:725-727)
+
+    def _transform_device(self, Xd):
+        self._check_fitted()
+        ndim = np.ascontiguousarray(self._ndim_per_kernel, dtype=np.int32)
+        dims = np.ascontiguousarray(self._dims_per_kernel, dtype=np.int32)
+        kd, bd, nd, dd = self._device_tables(Xd, self._kernel, self._bias_weights,
+                                             self._ndim_per_kernel, self._dims_per_kernel,
+                                             ints=2)
+        return nat.prep_project(Xd, kd, bd, nd, dd, ndim, dims)
+
+    def _copy(self) -> "JLD":
+        return JLD(dim=self._d, distribute=self._distribute, bias=self._bias)
+
+    def __eq__(self, other: Any) -> bool:
+        return (isinstance(other, JLD) and self._d == other._d
+                and self._distribute == other._distribute and self._bias == other._bias)
+
+    def __str__(self) -> str:
+        return f"JLD({self._d}, {self._distribute}, {self._bias})"

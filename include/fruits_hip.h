@@ -480,6 +480,52 @@ int fr_arctic_argmax(const double *d_V, int64_t rows, int64_t N, int64_t T, int3
  * of maxima and the positions of a word's prefixes (8 T + 2 L T bytes) exceed 60 KB of LDS. */
 int fr_pipeline_set_argmax(fr_pipeline_t *pipeline, int32_t n_words, const int32_t *lengths);
 
+/* ------------------------------------------------------------------ preparateurs
+ * RIN / MAV, JLD / FFN, NRM and LAG of fruits/preparation/transform.py on (N, D, T) device
+ * rows; each enqueues ONE kernel, allocates nothing and never writes d_X (d_out must be another
+ * buffer).  T >= 1.  The grouping tables of RIN / JLD are given twice: d_ndim (O) / d_dims (J)
+ * for the kernel and the same values on the host (h_ndim / h_dims), which are checked here -
+ * group sizes that do not add up to J fail with FR_E_ARG, a dimension outside [0, D) with
+ * FR_E_DIM - so no kernel ever reads outside its input. */
+
+/* Grouped causal FIR.  mode 0 = RIN._backend (transform.py:447-468): output dimension o owns
+ * the slots j in [start_o, end_o) (prefix sums of ndim), d_kernel is (J, w), J <= D and
+ *   out[n,o,k] = sum_j ( X[n,j,k] - sum_{l<w} X[n,dims[j],k-w+l] * kernel[j,l] )  for k >= w,
+ * 0 for k < w (the self term is dimension j, not dims[j]: transform.py:465); 0 <= w < T
+ * (w = 0, the kernel of a series of length 1: the self terms alone).
+ * adaptive != 0 (transform.py:536-543): the input counts as padded with w leading zeros and
+ * the first w outputs are dropped (any w).
+ * mode 1 = MAV._backend (transform.py:233-239): out[n,d,k-1] = sum(X[n,d,k-w:k]) / w for
+ * k = w .. T, 0 in front; 1 <= w <= T; the tables and J, O are ignored.  d_out (N, O, T). */
+int fr_prep_fir(const double *d_X, int64_t N, int64_t D, int64_t T, const double *d_kernel,
+                int32_t J, int32_t w, const int32_t *d_ndim, int32_t O, const int32_t *d_dims,
+                const int32_t *h_ndim, const int32_t *h_dims, int32_t mode, int32_t adaptive,
+                double *d_out, void *stream);
+
+/* Per-time-step map across dimensions.  hidden == 0 = JLD._backend (transform.py:651-670):
+ *   out[n,o,t] = sum_{j in group o} ( X[n,dims[j],t] * kernel[j] + bias[o] )
+ * (the bias inside the sum, like the reference).  hidden > 0 = FFN._transform
+ * (transform.py:362-376): out = W2 relu(W1 (x - mean) + b1) with d_W1 (hidden, D), d_b1
+ * (hidden), d_W2 (O, hidden); flags & 1: centre every row by its np.mean over time (numpy's
+ * summation order), flags & 2: relu on the output; relu(v) = v * (v > 0).  The JLD tables are
+ * then ignored; FR_E_LIMIT beyond 16 input or 16 output dimensions.  d_out (N, O, T). */
+int fr_prep_project(const double *d_X, int64_t N, int64_t D, int64_t T, const double *d_kernel,
+                    const double *d_bias, const int32_t *d_ndim, int32_t O, const int32_t *d_dims,
+                    int32_t J, const int32_t *h_ndim, const int32_t *h_dims, const double *d_W1,
+                    const double *d_b1, const double *d_W2, int32_t hidden, int32_t flags,
+                    double *d_out, void *stream);
+
+/* NRM._transform (transform.py:184-198): (x - min) / (max - min) per (series, dimension) row,
+ * or per series over all its dimensions (scale_dim != 0); rows with min == max become 0.
+ * Bit-identical to the reference.  d_out (N, D, T). */
+int fr_prep_normalize(const double *d_X, int64_t N, int64_t D, int64_t T, int32_t scale_dim,
+                      double *d_out, void *stream);
+
+/* LAG._transform (transform.py:291-298): d_out (N, 2D, 2T - 1), row 2i = x_i[(s + 1) / 2]
+ * (lead), row 2i + 1 = x_i[s / 2] (lag). */
+int fr_prep_leadlag(const double *d_X, int64_t N, int64_t D, int64_t T, double *d_out,
+                    void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest
