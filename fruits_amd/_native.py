@@ -24,7 +24,7 @@ FR_SIEVE_MAX, FR_SIEVE_MIN, FR_SIEVE_XPI, FR_SIEVE_LPI = 3, 4, 5, 6
 FR_SIEVE_SERIES_CUTS = 0x100   # OR-ed into a kind: the sieve's cuts are slots of a per-series table
 (FR_INFO_ROWS, FR_INFO_NODES, FR_INFO_LEVELS, FR_INFO_DIMS_USED, FR_INFO_MAX_DIM,
  FR_INFO_ALPHAS, FR_INFO_GROUPS, FR_INFO_SHARED, FR_INFO_STAGED_ROWS, FR_INFO_JIT_PROGRAMS,
- FR_INFO_AOT_PROGRAM) = range(11)
+ FR_INFO_AOT_PROGRAM, FR_INFO_STATIC_TAIL) = range(12)
 FR_E_ARG, FR_E_DIM, FR_E_HIP, FR_E_NOMEM, FR_E_LIMIT, FR_E_INDEX = -1, -2, -3, -4, -5, -6
 
 EXPORTS = [
@@ -331,6 +331,11 @@ class Plan:
     def static_program_index(self, groups: int = 1) -> int:
         """1 + index of the pre-compiled static program this plan's records equal (0: none)."""
         return int(lib().fr_plan_info(self._h, FR_INFO_AOT_PROGRAM))
+
+    def static_tail_series(self) -> int:
+        """Series that the most recent ``run`` launched as the finer units of the static program's
+        tail program, behind the whole-series units (0: no mixed launch)."""
+        return int(lib().fr_plan_info(self._h, FR_INFO_STATIC_TAIL))
 
     def jit_loaded(self) -> int:
         """Number of run-time compiled static programs this plan holds on the device."""

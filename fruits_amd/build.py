@@ -33,7 +33,9 @@ def units():
            # the sums of RIN / MAV / JLD / FFN round every product like the reference
            ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
            ("capi", "capi.cpp", []), ("jit", "jit.cpp", []),
-           ("walk_static_reg", "walk_static_inst.hip", ["-DSTATIC_REGISTRY"])]
+           # (the registry also holds the mixed kernels of the one-group programs and their
+           # tail programs: no contraction, like the programs' own units below)
+           ("walk_static_reg", "walk_static_inst.hip", ["-DSTATIC_REGISTRY", "-ffp-contract=off"])]
     # The walks: no a*b+c contraction - the reference rounds a letter's product before the
     # cumulative sum adds it (fruits/iss/semiring.py:143-149) - in EVERY unit, so that the record
     # interpreter (mode 0), the lean materialising walk (mode 2), the fused walk (mode 1), the

@@ -73,6 +73,9 @@ int env_int(const char *name, int dflt) {
 //   packed=0    cooperative kernels also for short series (the wave-per-series ones are default)
 //   stamps=M    the diagnostic timing build's mask (IssArgs::debug), dbg_bytes=B its stamp buffer
 //   wt=0        static programs keep plain output stores (no write-through instance)
+//   tail=S      ahead-of-time static programs with a tail program (the same plan in finer units):
+//               0 - never the mixed launch; S > 0 - the last min(S, N) series as finer units at
+//               any N; unset / -1 - run_walk's rule
 // Nothing here changes a result; the product reads none of them in normal operation.
 int debug_knob(const char *name, int dflt) {
   const char *v = std::getenv("FRUITS_HIP_DEBUG");
@@ -588,6 +591,11 @@ int64_t fr_plan_info(const fr_plan_t *plan, int32_t what) {
     }
     case FR_INFO_JIT_PROGRAMS:
       return p.jit ? (int64_t)static_cast<const JitState *>(p.jit)->progs.size() : 0;
+    case FR_INFO_STATIC_TAIL: {
+      fr::Plan &q = *plan->p;
+      std::lock_guard<std::mutex> lock(q.mu);
+      return q.last_tail_series;
+    }
     default: return fail(FR_E_ARG, "fr_plan_info: unknown selector");
   }
 }
@@ -1223,6 +1231,8 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   int static_lds_pad = 0;
   int static_wt = 0;                        // 1: the ahead-of-time program's write-through instance
   int static_prog = 0;                      // > 0: ahead-of-time program, -1: run-time compiled
+  bool static_tail_window = false;          // one group per series, chosen by the cache-sized window
+  const int tail_knob = debug_knob("tail", -1);
   const fr::JitProgram *jit_prog = nullptr;
   {
     std::lock_guard<std::mutex> lock(p.mu);
@@ -1265,6 +1275,9 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
       const bool cache_sized = N >= kStaticSplitBelow &&
                                footprint <= 0.01 * debug_knob("static_cache_x100", 140) * 256.0 * 1024.0 * 1024.0;
       static_groups = asked > 0 ? asked : (cache_sized ? 1 : gmax);
+      // (tail=S: the one-group program with its tail program at any N - see the mixed launch below)
+      if (tail_knob > 0 && asked <= 0 && aot && fr::static_program_tail_groups(p.static_prog[1]) > 0)
+        static_groups = 1;
       // Batches that stream through HBM (beyond twice the cache): FOUR resident workgroups per
       // CU instead of six - fewer concurrent write streams suit the memory system better
       // (N = 4096 / 8192 / 16384: 134 -> 122, 263 -> 241, 525 -> 493 us); 16 KB of unused LDS
@@ -1299,6 +1312,7 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
       // FRUITS_HIP_DEBUG wt=0 turns it off (A/B of one build).
       if (static_prog > 0 && debug_knob("wt", 1) != 0)
         static_wt = (static_groups == 1 && cache_sized) || (static_groups == 3 && static_lds_pad != 0);
+      static_tail_window = static_prog > 0 && static_groups == 1 && cache_sized && static_wt != 0;
     }
     const int G = static_prog ? static_groups
                               : (auto_groups ? choose_groups_walk(p, N, T, resident, fu != nullptr) : shape.G);
@@ -1314,6 +1328,7 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   a.X = d_X;
   a.out = d_out;
   a.N = N;
+  a.n_whole = (int32_t)std::min<int64_t>(N, 0x7fffffff);   // (no finer tail units)
   a.D = D;
   a.T = T;
   a.out_k_stride = out_k_stride;
@@ -1451,6 +1466,36 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   // static programs of several groups run one short-lived workgroup per unit: the hardware
   // dispatcher balances them and keeps the write front compact
   if (static_prog) a.persistent = 0;
+  // The mixed launch (walk_device.h, iss_walk_static_kernel<C, PG, PGT>): a batch of between one
+  // and two resident rounds R of whole-series workgroups ends in a partial round whose workgroups
+  // live as long as those of the full one, on a chip that empties around them (DESIGN.md 4.1:
+  // N = 2048, R = 1536 - the second half of the span at a third of the occupancy).  The first R
+  // series run as whole-series units as before; the other N - R run as the finer units of the
+  // plan's multi-group program, at the end of the grid.  R is what the launcher reports for the
+  // mixed instance on this device.  Ahead-of-time programs in the cache-sized window only.
+  // NOT MEASURED YET (DESIGN.md 4.1 says how): expected from the node cost, 54.7 -> 39-47 us at
+  // N = 2048 unless the drain of the Infinity Cache (about 48 us for 302 MB) caps it.
+  // FRUITS_HIP_DEBUG tail=0 turns it off (A/B of one build); tail=S runs the last min(S, N)
+  // series as finer units at any N (tests at small shapes).
+  int64_t tail_series = 0;
+  if (static_prog > 0 && a.G == 1 && !a.persistent && tail_knob != 0 &&
+      fr::static_program_tail_groups(static_prog) > 0 && N <= 0x7fffffff) {
+    if (tail_knob > 0) {
+      tail_series = std::min<int64_t>(tail_knob, N);
+    } else if (static_tail_window) {
+      fr::IssArgs b = a;
+      int32_t R = 0;
+      b.resident_out = &R;
+      b.n_whole = 0;   // (asks the mixed instance)
+      if (fr::launch_iss_walk(b, p.levels, nullptr) != hipSuccess) (void)hipGetLastError();
+      else if (R > 0 && R < N && N < 2 * (int64_t)R) tail_series = N - R;
+    }
+    a.n_whole = (int32_t)(N - tail_series);
+  }
+  {
+    std::lock_guard<std::mutex> lock(p.mu);
+    p.last_tail_series = tail_series;
+  }
   if (fu && fu->pl && !packed && fu->walk_feats != nullptr && fu->walk_of_row != nullptr) {
     // a large plan in pieces (plan.h, PiecedProgram): one launch per piece type, each over
     // (series x the type's units); the features leave in walk order

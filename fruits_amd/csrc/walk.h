@@ -85,15 +85,24 @@ static hipError_t launch_fused_cfg(const IssArgs &a, hipStream_t st) {
   return launch_fused_mode<E, LV, MULTI, W, SEMI, false, false, MODE, HO>(a, st);
 }
 
-// launch of a static program: same persistent grid as the interpreter's
-template <class C, class PG>
+// launch of a static program: same persistent grid as the interpreter's.  With a tail program
+// PGT (walk_device.h) the mixed form: a.n_whole whole-series units, then PGT::groups finer units
+// for each of the other series - one workgroup per unit.
+template <class C, class PG, class PGT = void>
 static hipError_t launch_walk_static(const IssArgs &a, hipStream_t st) {
-  const size_t lds = ((size_t)PG::rows * C::CHUNK + 4 * C::NW) * sizeof(double) + (size_t)a.lds_pad;
+  constexpr bool mixed = StaticTail<PGT>::on;
+  int rows = PG::rows, tail_groups = 1;
+  if constexpr (mixed) {
+    rows = PG::rows > PGT::rows ? PG::rows : PGT::rows;   // (equal: the same plan)
+    tail_groups = PGT::groups;
+  }
+  const size_t lds = ((size_t)rows * C::CHUNK + 4 * C::NW) * sizeof(double) + (size_t)a.lds_pad;
   static LaunchCache cache;
   int per_cu = 1;
-  hipError_t e = cache.facts(iss_walk_static_kernel<C, PG>, kWalkThreads, lds, &per_cu);
+  hipError_t e = cache.facts(iss_walk_static_kernel<C, PG, PGT>, kWalkThreads, lds, &per_cu);
   if (e != hipSuccess) return e;
-  const int64_t units = a.N * PG::groups;
+  if (mixed && (a.n_whole < 0 || a.n_whole > a.N)) return hipErrorInvalidValue;
+  const int64_t units = mixed ? a.n_whole + tail_groups * (a.N - a.n_whole) : a.N * PG::groups;
   if (units > 0x7fffffffLL || a.G != PG::groups) return hipErrorInvalidValue;
   if (a.persistent > 1 && per_cu > a.persistent) per_cu = a.persistent;  // experiments: cap per CU
   int64_t resident = (int64_t)per_cu * device_cu_count();
@@ -103,8 +112,9 @@ static hipError_t launch_walk_static(const IssArgs &a, hipStream_t st) {
     *a.resident_out = (int32_t)resident;
     return hipSuccess;
   }
+  if (mixed && a.persistent) return hipErrorInvalidValue;
   const int64_t blocks = (units < resident || !a.persistent) ? units : resident;
-  hipLaunchKernelGGL((iss_walk_static_kernel<C, PG>), dim3((unsigned)blocks), dim3(kWalkThreads),
+  hipLaunchKernelGGL((iss_walk_static_kernel<C, PG, PGT>), dim3((unsigned)blocks), dim3(kWalkThreads),
                      lds, st, a);
   return hipGetLastError();
 }

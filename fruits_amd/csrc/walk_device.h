@@ -1111,13 +1111,42 @@ __device__ __forceinline__ void static_run_group(WalkCtx &cx, StaticRegs<C> &rg,
   }
 }
 
+// PGT of iss_walk_static_kernel: void = no tail program
+template <class PGT>
+struct StaticTail {
+  static constexpr bool on = true;
+};
+template <>
+struct StaticTail<void> {
+  static constexpr bool on = false;
+};
+template <class PG, class PGT>
+constexpr bool static_same_rows() {   // both programs stage the same rows of X
+  if (PG::n_src != PGT::n_src || PG::rows != PGT::rows) return false;
+  for (int r = 0; r < PG::rows; ++r)
+    if (PG::row_src[r] != PGT::row_src[r]) return false;
+  return true;
+}
+
 // Materialising walk of a static program: one aligned time chunk (MULTI = 0, VEC), a unit is
 // (series, group of the schedule), at most kStaticMaxRows staged rows, all of them rows of X.
-template <class C, class PG>
+//
+// With a tail program PGT (the same plan scheduled for several groups per series) ONE launch
+// holds both granularities, one unit per workgroup: workgroup b < a.n_whole runs series b with
+// the one-group program PG, the workgroups behind run the last N - n_whole series as
+// (series, group) units of PGT.  The finer units sit at the end of the grid: they start as the
+// first round of whole-series workgroups ends and fill the partial last round in pieces of a
+// third of the length (speed only - no result depends on the order of dispatch).
+template <class C, class PG, class PGT = void>
 __global__ __launch_bounds__(kWalkThreads) void iss_walk_static_kernel(const IssArgs a) {
   static_assert(C::MODE == 0 && C::MULTI == 0 && C::VEC && C::TEAM == 4 && !C::WEIGHTED,
                 "static programs: materialising, single chunk, aligned, unweighted");
   static_assert(PG::rows <= kStaticMaxRows && PG::frames <= kStaticMaxFrames, "static program too wide");
+  if constexpr (StaticTail<PGT>::on) {
+    static_assert(PG::groups == 1 && PGT::groups > 1, "whole series in front, finer units behind");
+    static_assert(PGT::rows <= kStaticMaxRows && PGT::frames <= kStaticMaxFrames, "static program too wide");
+    static_assert(static_same_rows<PG, PGT>(), "the tail program is another schedule of the same plan");
+  }
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   WalkCtx cx;
@@ -1143,35 +1172,67 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_static_kernel(const Iss
   // ahead of their use and in front of most of that unit's stores (vmcnt counts in order: a
   // load issued behind a store waits for it).
   cx.have_rows = false;
-  bool first_unit = true;
-  constexpr int G = PG::groups;
-  const int u_end = (int)(a.N * G);
 #ifdef FRUITS_HIP_TIMING_BUILD
   unsigned long long t_unit[4] = {0, 0, 0, 0};
   int n_unit = 0;
   const unsigned long long real_begin = __builtin_amdgcn_s_memrealtime();
 #endif
-  for (int u = blockIdx.x; u < u_end; u += gridDim.x) {
-    int64_t n = u;
-    int g = 0;
-    if constexpr (G > 1) {
-      if (a.xcd_map) {   // the groups of one series meet in one XCD's L2
-        const int q = u >> 3, r = u & 7;
-        n = (int64_t)(q / G) * 8 + r;
-        g = q % G;
+  if constexpr (StaticTail<PGT>::on) {
+    // one unit per workgroup; the one-group schedule's kSchedPrefetch entry sees no next unit
+    const int b = blockIdx.x;
+    const int n_whole = a.n_whole;
+    cx.next_unit = (int)a.N;
+#ifdef FRUITS_HIP_TIMING_BUILD
+    t_unit[n_unit++] = __builtin_amdgcn_s_memrealtime();
+#endif
+    if (b < n_whole) {
+      cx.out_base = a.out + (int64_t)b * a.out_n_stride;
+      static_run_group<C, PG, 0>(cx, rg, lds, b, 0);
+    } else {
+      constexpr int GT = PGT::groups;
+      const int j = b - n_whole;
+      const int S = (int)a.N - n_whole;
+      int64_t n;
+      int g;
+      if (S % 8 == 0) {   // the groups of one series meet in one XCD's L2
+        const int q = j >> 3, r = j & 7;
+        n = n_whole + (int64_t)(q / GT) * 8 + r;
+        g = q % GT;
       } else {
-        n = u / G;
-        g = u - (int)n * G;
+        n = n_whole + j / GT;
+        g = j % GT;
+      }
+      if (n < a.N) {   // (the host launches exactly n_whole + GT * S workgroups)
+        cx.out_base = a.out + n * a.out_n_stride;
+        static_run_group<C, PGT, 0>(cx, rg, lds, n, g);
       }
     }
-    cx.out_base = a.out + n * a.out_n_stride;
-    cx.next_unit = u + (int)gridDim.x;
-    if (!first_unit) lds_barrier();  // all reads of the previous unit's rows are done
-    first_unit = false;
+  } else {
+    bool first_unit = true;
+    constexpr int G = PG::groups;
+    const int u_end = (int)(a.N * G);
+    for (int u = blockIdx.x; u < u_end; u += gridDim.x) {
+      int64_t n = u;
+      int g = 0;
+      if constexpr (G > 1) {
+        if (a.xcd_map) {   // the groups of one series meet in one XCD's L2
+          const int q = u >> 3, r = u & 7;
+          n = (int64_t)(q / G) * 8 + r;
+          g = q % G;
+        } else {
+          n = u / G;
+          g = u - (int)n * G;
+        }
+      }
+      cx.out_base = a.out + n * a.out_n_stride;
+      cx.next_unit = u + (int)gridDim.x;
+      if (!first_unit) lds_barrier();  // all reads of the previous unit's rows are done
+      first_unit = false;
 #ifdef FRUITS_HIP_TIMING_BUILD
-    if (n_unit < 4) t_unit[n_unit++] = __builtin_amdgcn_s_memrealtime();
+      if (n_unit < 4) t_unit[n_unit++] = __builtin_amdgcn_s_memrealtime();
 #endif
-    static_run_group<C, PG, 0>(cx, rg, lds, n, g);
+      static_run_group<C, PG, 0>(cx, rg, lds, n, g);
+    }
   }
 #ifdef FRUITS_HIP_TIMING_BUILD
   if ((a.debug & 16) && a.dbg != nullptr && cx.lane == 0) {

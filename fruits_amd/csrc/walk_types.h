@@ -215,6 +215,9 @@ struct IssArgs {
   const int32_t *piece_unit_row0;   // walk position of a unit's first output row
   unsigned long long *dbg;  // diagnostic stamps (timing build only)
   int32_t debug;            // timing experiments (FRUITS_HIP_DEBUG), 0 in production
+  int32_t n_whole;         // static program with a tail program (walk_device.h, iss_walk_static_kernel):
+                            // the first n_whole series run as whole-series units, the others as
+                            // (series, group) units of the tail program; N (or more): no such units
 };
 
 }  // namespace fr

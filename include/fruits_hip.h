@@ -80,6 +80,9 @@ extern "C" {
 #define FR_INFO_JIT_PROGRAMS 9 /* run-time compiled static programs loaded for this plan (fr_plan_jit) */
 #define FR_INFO_AOT_PROGRAM 10 /* 1 + index of the pre-compiled static program (one group per series)
                                   the plan's records equal, 0: none */
+#define FR_INFO_STATIC_TAIL 11 /* series that the plan's most recent fr_iss_run launch ran as the finer
+                                  units of a tail program behind the whole-series units (the mixed
+                                  static launch), 0: none */
 
 /* sieve kinds of fr_sieve_* and the fused pipeline */
 #define FR_SIEVE_NPI 0 /* fruits/sieving/increment.py:101-129 */

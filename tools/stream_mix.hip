@@ -7,7 +7,8 @@
 // 16-byte output stores (a plain global store, or a buffer store with the policy bits plain, sc1,
 // sc0 sc1, nt, nt sc1).  Every cell is timed back to back (10 launches between one event pair)
 // and isolated (each launch between its own event pair, the device drained in front of it).
-//   hipcc --offload-arch=gfx950 -O3 tools/stream_mix.hip -o /tmp/sm && /tmp/sm [--persistent]
+//   hipcc --offload-arch=gfx950 -O3 tools/stream_mix.hip -o /tmp/sm && /tmp/sm [--persistent | --tail]
+// --tail: the headline batch with its last series moved in third-units (the walk's mixed launch)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -78,6 +79,62 @@ __global__ __launch_bounds__(256) void mix_kernel(const double *X, double *out, 
   }
 }
 
+// The same bytes with the last N - n_whole series in finer units: workgroup b < n_whole moves
+// series b whole (non-temporal loads, K planes); the workgroups behind are three movers per
+// series of K / 3 planes each, which all read the 3 rows again with plain loads (the XCD-aware
+// numbering of the walk: the movers of one series meet in one L2).  sc1 stores throughout.
+// n_whole = N is the unsplit mover (G = 1, nt reads, sc1).
+__global__ __launch_bounds__(256) void mix_tail_kernel(const double *X, double *out, int N, int n_whole) {
+  const int tid = threadIdx.x, b = blockIdx.x;
+  int n = b, k0 = 0, k1 = K;
+  const bool whole = b < n_whole;
+  if (!whole) {
+    const int j = b - n_whole, q = j >> 3, r = j & 7;   // (N - n_whole is a multiple of 8 here)
+    n = n_whole + (q / 3) * 8 + r;
+    k0 = (q % 3) * (K / 3);
+    k1 = k0 + K / 3;
+  }
+  vd2 v[D][2];
+#pragma unroll
+  for (int d = 0; d < D; ++d)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const vd2 *src = reinterpret_cast<const vd2 *>(X + ((size_t)n * D + d) * T + 2 * (k * 256 + tid));
+      v[d][k] = whole ? __builtin_nontemporal_load(src) : *src;
+    }
+  for (int k = k0; k < k1; ++k) {
+    double *dst = out + ((size_t)k * N + n) * T;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, T * 8, 0x00020000);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      vd2 w = v[0][h] + v[1][h] + v[2][h];
+      w.x += (double)k;
+      vu4 bits;
+      __builtin_memcpy(&bits, &w, 16);
+      __builtin_amdgcn_raw_buffer_store_b128(bits, rs, 16 * (h * 256 + tid), 0, 16);
+    }
+  }
+}
+
+// median back-to-back time (us) of the split mover, 7 batches of 10 launches
+static float run_tail(const double *X, double *out, int N, int n_whole) {
+  hipEvent_t a, b;
+  hipEventCreate(&a); hipEventCreate(&b);
+  const int g = n_whole + 3 * (N - n_whole);
+  auto launch = [&] { hipLaunchKernelGGL(mix_tail_kernel, dim3(g), dim3(256), 0, 0, X, out, N, n_whole); };
+  for (int w = 0; w < 5; ++w) launch();
+  std::vector<float> ts;
+  for (int r = 0; r < 7; ++r) {
+    hipEventRecord(a);
+    for (int rep = 0; rep < 10; ++rep) launch();
+    hipEventRecord(b); hipEventSynchronize(b);
+    float ms; hipEventElapsedTime(&ms, a, b); ts.push_back(ms / 10);
+  }
+  std::sort(ts.begin(), ts.end());
+  hipEventDestroy(a); hipEventDestroy(b);
+  return ts[3] * 1e3f;
+}
+
 struct Cell { float b2b, iso; };
 
 template <int G, int READ, int POL>
@@ -134,6 +191,21 @@ static void row(const double *X, double *out, int N, int grid) {
 }
 
 int main(int argc, char **argv) {
+  if (argc > 1 && !strcmp(argv[1], "--tail")) {
+    // the headline batch, unsplit against the last N - n_whole series in third-units: three
+    // interleaved passes, every time printed
+    const int N = 2048;
+    double *X, *out;
+    hipMalloc(&X, (size_t)N * D * T * 8);
+    hipMalloc(&out, (size_t)K * N * T * 8);
+    hipMemset(X, 0, (size_t)N * D * T * 8);
+    for (int pass = 0; pass < 3; ++pass)
+      for (int n_whole : {2048, 1792, 1536, 1280, 0})
+        printf("pass %d  N %d  n_whole %4d  grid %4d: b2b %6.1f us\n", pass, N, n_whole,
+               n_whole + 3 * (N - n_whole), run_tail(X, out, N, n_whole));
+    hipFree(X); hipFree(out);
+    return 0;
+  }
   const int grid = (argc > 1 && !strcmp(argv[1], "--persistent")) ? 1536 : 0;
   for (int N : {2048, 1536, 3072, 8192}) {
     double *X, *out;
