@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libfruits_hip.so")
 HEADERS = ["kernels.h", "plan.h", "jit.h", "walk.h", "walk_device.h", "walk_fused.h", "walk_types.h", "walk_scan.h", "coswiss.h", "walk_packed.h",
-           "launch_cache.h", "static_programs.h",
+           "launch_cache.h", "launch_choice.h", "static_programs.h",
            os.path.join("..", "..", "include", "fruits_hip.h")]
 
 

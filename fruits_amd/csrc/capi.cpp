@@ -75,7 +75,7 @@ int env_int(const char *name, int dflt) {
 //   wt=0        static programs keep plain output stores (no write-through instance)
 //   tail=S      ahead-of-time static programs with a tail program (the same plan in finer units):
 //               0 - never the mixed launch; S > 0 - the last min(S, N) series as finer units at
-//               any N; unset / -1 - run_walk's rule
+//               any N; unset / -1 - choose_walk_launch's rule
 // Nothing here changes a result; the product reads none of them in normal operation.
 int debug_knob(const char *name, int dflt) {
   const char *v = std::getenv("FRUITS_HIP_DEBUG");
@@ -87,6 +87,21 @@ int debug_knob(const char *name, int dflt) {
     if (*p == ',') ++p;
   }
   return dflt;
+}
+
+// The knobs and switches a launch reads: once per entry-point call, and on every call (a test
+// flips FRUITS_HIP_DEBUG between two runs of one plan).  The only reader of the environment on
+// the way to a launch: the choice itself (launch_choice.h) sees this struct.
+fr::WalkKnobs read_walk_knobs() {
+  fr::WalkKnobs k;
+  const struct { const char *name; int *value; } debug[] = {
+      {"groups", &k.groups}, {"persist", &k.persist}, {"packed", &k.packed}, {"lean", &k.lean},
+      {"wt", &k.wt}, {"tail", &k.tail}, {"static_cache_x100", &k.static_cache_x100},
+      {"static_min_T", &k.static_min_T}, {"stamps", &k.stamps}, {"dbg_bytes", &k.dbg_bytes}};
+  for (const auto &d : debug) *d.value = debug_knob(d.name, *d.value);
+  k.hip_static = env_int("FRUITS_HIP_STATIC", k.hip_static);
+  k.hip_jit = env_int("FRUITS_HIP_JIT", k.hip_jit);
+  return k;
 }
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -210,97 +225,11 @@ int ensure_cos_program(fr::Plan &p, fr::CosProgram &c, hipStream_t st, const cha
   return FR_OK;
 }
 
-int choose_groups(const fr::Plan &p, int64_t N, int requested) {
-  const int U = p.units();
-  if (U <= 1) return 1;
-  int G = requested;
-  if (G <= 0) G = debug_knob("groups", 0);
-  if (G <= 0) {
-    // aim for a few thousand workgroups (256 CUs x several resident each)
-    const int64_t target = 2048;
-    G = (int)((target + N - 1) / (N > 0 ? N : 1));
-  }
-  if (G > U) G = U;
-  if (G < 1) G = 1;
-  return G;
-}
-
-// How a (plan, N, T, groups) launch is shaped: decided identically by the run path
-// and by fr_plan_prepare (which uploads the node order the run will ask for).
-struct LaunchShape {
-  bool packed = false;    // wave-per-series kernel (short series)
-  bool fits = true;       // the staged rows of one time chunk fit the LDS
-  int G = 1;              // groups of root sub-tries per series
-};
-
-bool staged_rows_fit(const fr::Plan &p, int64_t T) {
-  return (size_t)p.rows_staged() * fr::walk_chunk_elems(T) * 8 <= 150 * 1024;
-}
-
-LaunchShape launch_shape(const fr::Plan &p, int64_t N, int64_t T, int requested_groups) {
-  LaunchShape s;
-  s.fits = staged_rows_fit(p, T);
-  // short series: four series per workgroup, one wave each (their rows side by side in LDS)
-  const int64_t packed_chunk = T <= 128 ? 128 : (T <= 256 ? 256 : 384);
-  s.packed = debug_knob("packed", 1) != 0 &&
-             fr::packed_supported(T, p.levels, p.semiring) &&
-             (size_t)4 * p.rows_staged() * packed_chunk * 8 <= 64 * 1024;
-  // (a packed workgroup holds four units: ask for four times the units)
-  s.G = choose_groups(p, s.packed ? (N + 3) / 4 : N, requested_groups);
-  return s;
-}
-
-// LDS carry slots of a multi-chunk walk: 3 per record of the program (nodes + one sentinel
-// per group); sized for up to kSpanGroupsMax groups so that the kernel's LDS footprint -
-// and with it the number of resident workgroups the group choice is made for - does not
-// depend on the choice itself
-constexpr int kSpanGroupsMax = 12;
-int carry_slots_for(const fr::Plan &p, int G) {
-  return 3 * ((int)p.nodes.size() + std::max(G, kSpanGroupsMax));
-}
-bool carries_fit_lds(const fr::Plan &p, int64_t T, int G) {
-  // rows + carries must leave room for >= 4 workgroups per CU (160 KiB LDS)
-  const size_t rows_bytes = (size_t)p.rows_staged() * fr::walk_chunk_elems(T) * 8;
-  return rows_bytes + (size_t)carry_slots_for(p, G) * 8 <= 40 * 1024;
-}
-
-// LDS feature window of a fused cooperative launch (walk_device.h, feat_flush): as many slots
-// as fit next to the rows and carries while four workgroups still share a CU's 160 KiB, at
-// least what the widest node needs (output rows x feature ops).  `fits`: every group's
-// features fit, so a unit flushes once.  0: the widest node does not fit the LDS at all.
-int feat_window_sized(int widest, int largest_group, size_t other_lds_bytes, bool mpi, bool &fits);
-int feat_window_for(const fr::GroupedProgram &gp, size_t other_lds_bytes, int n_ops, bool mpi,
-                    bool &fits) {
-  int widest = 0, largest_group = 0;
-  for (int g = 0; g < gp.groups; ++g) {
-    int total = 0;
-    for (int i = gp.group_begin[g]; i < gp.group_begin[g + 1]; ++i) {
-      if ((gp.recs[i].w[0] & 0xff) == fr::kRecSentinelLevel) continue;
-      const int need = gp.recs[i].w[6] * n_ops;
-      widest = std::max(widest, need);
-      total += need;
-    }
-    largest_group = std::max(largest_group, total);
-  }
-  return feat_window_sized(widest, largest_group, other_lds_bytes, mpi, fits);
-}
-// (widest: the slots one node needs; largest_group: the slots of the largest unit)
-int feat_window_sized(int widest, int largest_group, size_t other_lds_bytes, bool mpi, bool &fits) {
-  const size_t budget = 38 * 1024;
-  int W = 64;
-  while (W < 1024 && W < largest_group &&
-         other_lds_bytes + fr::feat_window_bytes(2 * W, mpi, false) <= budget)
-    W *= 2;
-  if (W < widest) W = (widest + 1) / 2 * 2;
-  if (other_lds_bytes + fr::feat_window_bytes(W, mpi, false) > 160 * 1024) return 0;
-  fits = largest_group <= W;
-  return W;
-}
-
 // Resident workgroups of the cooperative walk kernel instance that (plan, T, fused,
 // vec_ok) selects: a dry run of the launcher (nothing is enqueued).
-int64_t query_resident(const fr::Plan &p, int64_t N, int64_t T, bool fused, bool vec_ok) {
-  if (debug_knob("persist", 1) == 0) return 0;
+int64_t query_resident(const fr::Plan &p, int64_t N, int64_t T, bool fused, bool vec_ok,
+                       const fr::WalkKnobs &k) {
+  if (k.persist == 0) return 0;
   fr::IssArgs a{};
   int32_t resident = 0;
   double *const dummy = reinterpret_cast<double *>(uintptr_t(256));  // never dereferenced
@@ -315,8 +244,8 @@ int64_t query_resident(const fr::Plan &p, int64_t N, int64_t T, bool fused, bool
   a.vec_ok = vec_ok ? 1 : 0;
   a.persistent = 1;
   a.semiring = p.semiring;
-  a.carry_slots = carry_slots_for(p, 1);
-  a.carry_in_lds = (fused || carries_fit_lds(p, T, 1)) ? 1 : 0;   // (the fused walk: always)
+  a.carry_slots = fr::carry_slots_for(p, 1);
+  a.carry_in_lds = (fused || fr::carries_fit_lds(p, T, 1)) ? 1 : 0;   // (the fused walk: always)
   a.feats = fused ? dummy : nullptr;
   a.feat_window = fused ? 128 : 0;   // (the launch's own window may differ a little)
   a.resident_out = &resident;
@@ -327,44 +256,22 @@ int64_t query_resident(const fr::Plan &p, int64_t N, int64_t T, bool fused, bool
   return resident;
 }
 
-// Groups per series for the cooperative kernel (walk.h): a unit is (series, group of root
-// sub-tries) and stages the series' rows itself, so groups only pay where finer units help.
-// Measured on config 2 and its 48-word tiling (tools/gpu_sched.sh: FRUITS_HIP_GROUPS = 1, 2,
-// 3, 6, 9 against N = 64 ... 8192, `resident` = one round of workgroups, 1536 for these
-// kernels):
-//   N < resident        the batch alone cannot fill the chip: ceil(resident / N) groups, at
-//                       most 6 (N = 64: G = 6 7.5 us vs 15.7 with 1; 256: 3; 512: 3; 768 and
-//                       1000: 2)
-//   N < 2 x resident    whole series (N = 1536: 41.7 us, G = 3 46.9; N = 2048: 64.5, G = 3 73.2)
-//   beyond              small plans (<= 32 nodes): 3 groups - finer units even out the last
-//                       rounds and their restaging hits the XCD's L2 (N = 4096: 135.5 vs
-//                       146.6 us, N = 8192: 272 vs 291 us); larger plans keep whole series
-//                       (config 3 / 4 / 5: no difference measured)
-int choose_groups_walk(const fr::Plan &p, int64_t N, int64_t T, int64_t resident, bool fused = false) {
-  const int U = p.units();
-  if (U <= 1 || N <= 0) return 1;
-  if (resident <= 0) return choose_groups(p, N, 0);
-  if (N < resident) {
-    const int64_t G = std::min<int64_t>((resident + N - 1) / N, 6);
-    return (int)std::max<int64_t>(1, std::min<int64_t>(G, U));
+// ... and of the mixed instance of ahead-of-time program `prog` (one group per series with its
+// tail program, write-through stores, no LDS pad: the cache-sized window); 0: unknown
+int64_t query_mixed_resident(int prog, int64_t N, int64_t T) {
+  fr::IssArgs a{};
+  int32_t resident = 0;
+  a.N = N;
+  a.T = T;
+  a.G = 1;
+  a.static_prog = prog;
+  a.n_whole = 0;   // (asks the mixed instance)
+  a.resident_out = &resident;
+  if (fr::launch_iss_walk(a, 0, nullptr) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
   }
-  // fused launches run one short-lived workgroup per unit (run_walk): two groups per series
-  // balance a little better than whole series on LONG plans (config 4, 1351 nodes: 13.08 vs
-  // 13.32 ms); on shorter ones every extra unit is one more staging of the series' rows - the
-  // word shards of config 4 over 8 ranks (~170 nodes each): 1.86 ms with whole series, 2.40 ms
-  // with two groups (tools/bench_shards.py)
-  // (round 3, the pipeline's own kernels: one-chunk plans of 668 / 683 nodes - two word shards of
-  // config 4 - 4.74 / 4.84 ms with whole series, 5.47 / 5.48 ms with two groups; 1351 nodes: 9.53
-  // vs 9.35 ms; config 5, 511 nodes over four time chunks - two groups also halve the LDS carries
-  // of a unit: 17.8 vs 17.3 ms)
-  if (fused)
-    return p.nodes.size() >= (T > fr::walk_chunk_elems(T) ? 400u : 1000u) ? std::min(U, 2) : 1;
-  // materialising launches of long plans run one short-lived workgroup per unit too (the lean
-  // walk, run_walk): two groups per series shorten the last round (of_weight(4,2), N = 2048:
-  // 390 -> 372 us; the same at N = 8192) for one more staging of the series' rows
-  if (!p.letter_sum && p.nodes.size() >= 64 && debug_knob("lean", 1) != 0) return std::min(U, 2);
-  if (N < 2 * resident || p.nodes.size() > 32) return 1;
-  return std::min(U, 3);
+  return resident;
 }
 
 // Run-time compiled static programs of a plan (jit.cpp), by groups per series.
@@ -373,15 +280,6 @@ struct JitState {
   bool tried = false;
   std::string error;     // why the plan has none (not an error of the caller's)
 };
-
-// batches below this many series run a static program with all its groups (to fill the chip)
-constexpr int kStaticSplitBelow = 768;
-
-// (T in (384, 512]: the 1024-element chunk with half of its lanes idle - still ahead of the
-// interpreter's 512-element chunk on cache-sized batches, see run_walk)
-bool static_shape_ok(const fr::Plan &p, int64_t T) {
-  return !p.cos && p.weighting == 0 && p.semiring == fr::kSemiReals && T > debug_knob("static_min_T", 384) && T <= 1024;
-}
 
 // Compiles and loads the plan's static programs (one group and min(3, units) groups per
 // series) unless an ahead-of-time program covers it.  Called with p.mu held; failures leave
@@ -416,27 +314,45 @@ void ensure_jit(fr::Plan &p) {
   }
 }
 
+// The ahead-of-time static programs of the plan for 1, 2 and 3 groups per series (looked up
+// once per plan).  Caller holds p.mu.
+void lookup_static_programs(fr::Plan &p) {
+  if (p.static_prog[0] >= 0) return;
+  const fr::GroupedProgram &g1 = fr::grouped(p, 1);
+  for (int g = 1; g <= 3; ++g)
+    p.static_prog[g] = fr::static_program_for(g1.recs.data(), (int)g1.recs.size(), g, p.row_src.data(),
+                                                   (int)p.row_src.size());
+  p.static_prog[0] = 0;
+}
+
+// The facts of a launch without its static programs: what fr_plan_prepare and the pipeline's
+// compilers choose the interpreter's node order from, and where a run starts.  Caller holds p.mu
+// (`largest_group` lays the node order out).
+fr::WalkFacts walk_facts(fr::Plan &p, int64_t N, int64_t T, int groups, bool fused, bool total_inc,
+                         bool vec_ok, const fr::WalkKnobs &k) {
+  fr::WalkFacts f{N, T, groups, fused, total_inc, 3, vec_ok};
+  const bool packed = fr::walk_is_packed(fr::launch_shape(p, N, T, groups, k), total_inc);
+  if (fr::host_chooses_groups(packed, groups, k)) f.resident = query_resident(p, N, T, fused, vec_ok, k);
+  f.largest_group = [&p](int G) { return fr::largest_group(fr::grouped(p, G)); };
+  return f;
+}
+
 // One-time uploads for the node order a run of this (N, T, groups) asks for.
-int prepare_plan(fr::Plan &p, int64_t N, int64_t T, int32_t groups, bool fused, const char *who) {
+int prepare_plan(fr::Plan &p, int64_t N, int64_t T, int32_t groups, bool fused, const char *who,
+                 const fr::WalkKnobs &k) {
   std::lock_guard<std::mutex> lock(p.mu);
   if (p.cos) return ensure_cos_program(p, *p.cos, nullptr, who);
   if (N == 0 || T == 0 || p.K == 0 || p.nodes.empty()) return FR_OK;
-  const LaunchShape shape = launch_shape(p, N, T, groups);
-  if (!shape.fits)
+  if (!fr::staged_rows_fit(p, T))
     return fail(FR_E_LIMIT, std::string(who) + ": the plan stages " +
                                 std::to_string(p.rows_staged()) +
                                 " rows per time chunk, more than the LDS holds - split the word list");
-  std::vector<int> Gs;
-  const bool auto_groups = !shape.packed && groups <= 0 && debug_knob("groups", 0) <= 0;
-  if (auto_groups) {
-    // (the choice depends on the kernel instance - fused or not, 16-byte aligned or not -
-    // which is only known when the pointers are: upload what either would ask for)
-    Gs.push_back(choose_groups_walk(p, N, T, query_resident(p, N, T, fused, true), fused));
-    if (!fused) Gs.push_back(choose_groups_walk(p, N, T, query_resident(p, N, T, false, false)));
-  } else {
-    Gs.push_back(shape.G);
-  }
-  for (int G : Gs) {
+  // (the choice depends on the kernel instance - fused or not, 16-byte aligned or not -
+  // which is only known when the pointers are: upload what either would ask for.  A static
+  // program reads no tables: the node order is the one a run without it takes)
+  for (const bool vec_ok : {true, false}) {
+    if (fused && !vec_ok) break;
+    const int G = fr::choose_walk_launch(p, walk_facts(p, N, T, groups, fused, false, vec_ok, k), k).G;
     int rc = ensure_device_program(p, fr::grouped(p, G), nullptr, who);
     if (rc != FR_OK) return rc;
   }
@@ -585,9 +501,8 @@ int64_t fr_plan_info(const fr_plan_t *plan, int32_t what) {
       fr::Plan &q = *plan->p;
       if (q.cos) return 0;
       std::lock_guard<std::mutex> lock(q.mu);
-      const fr::GroupedProgram &g1 = fr::grouped(q, 1);
-      return fr::static_program_for(g1.recs.data(), (int)g1.recs.size(), 1, q.row_src.data(),
-                                    (int)q.row_src.size());
+      lookup_static_programs(q);
+      return q.static_prog[1];
     }
     case FR_INFO_JIT_PROGRAMS:
       return p.jit ? (int64_t)static_cast<const JitState *>(p.jit)->progs.size() : 0;
@@ -689,26 +604,20 @@ int32_t fr_plan_fits(const fr_plan_t *plan, int64_t T) {
   if (!plan || !plan->p || T < 0) return fail(FR_E_ARG, "fr_plan_fits: bad argument");
   const fr::Plan &p = *plan->p;
   if (p.cos) return (p.cos->exponent <= fr::kCosMaxExponent && p.levels <= 16) ? 1 : 0;
-  return staged_rows_fit(p, T) ? 1 : 0;
+  return fr::staged_rows_fit(p, T) ? 1 : 0;
 }
 
 int fr_plan_prepare(fr_plan_t *plan, int64_t N, int64_t T, int32_t groups) {
   if (!plan || !plan->p || N < 0 || T < 0) return fail(FR_E_ARG, "fr_plan_prepare: bad argument");
   fr::Plan &p = *plan->p;
-  int rc = prepare_plan(p, N, T, groups, false, "fr_plan_prepare");
+  const fr::WalkKnobs k = read_walk_knobs();
+  int rc = prepare_plan(p, N, T, groups, false, "fr_plan_prepare", k);
   if (rc != FR_OK) return rc;
   // a small plan without an ahead-of-time static program gets one compiled now (hipRTC,
   // cached on disk); a failure is not the caller's: the interpreter runs the plan
-  if (static_shape_ok(p, T) && env_int("FRUITS_HIP_JIT", 1) != 0 &&
-      env_int("FRUITS_HIP_STATIC", 1) != 0) {
+  if (fr::static_shape_ok(p, T, k) && k.hip_jit != 0 && k.hip_static != 0) {
     std::lock_guard<std::mutex> lock(p.mu);
-    if (p.static_prog[0] < 0) {
-      const fr::GroupedProgram &g1 = fr::grouped(p, 1);
-      for (int g = 1; g <= 3; ++g)
-        p.static_prog[g] = fr::static_program_for(g1.recs.data(), (int)g1.recs.size(), g, p.row_src.data(),
-                                                       (int)p.row_src.size());
-      p.static_prog[0] = 0;
-    }
+    lookup_static_programs(p);
     if (p.static_prog[1] <= 0 && fr::static_schedule(p, 1).ok) ensure_jit(p);
   }
   return FR_OK;
@@ -1030,7 +939,7 @@ size_t piece_other_lds(const fr::Plan &p, const fr::PieceType &pt, int64_t T, in
 }
 int piece_window(const fr::Plan &p, const fr::PieceType &pt, int64_t T, int carry_per_node, int n_ops,
                  bool mpi, bool &fits) {
-  return feat_window_sized(pt.widest_node * n_ops, pt.max_unit_rows * n_ops,
+  return fr::feat_window_sized(pt.widest_node * n_ops, pt.max_unit_rows * n_ops,
                            piece_other_lds(p, pt, T, carry_per_node), mpi, fits);
 }
 
@@ -1115,224 +1024,171 @@ void ensure_fused_pieces(fr_pipeline &pl, const fr::FusedKey &key, bool cache_on
   it->second.fits = std::move(type_fits);
 }
 
-// Shared body of fr_iss_run and fr_pipeline_run: validates, lays out the
-// workspace, fills the exp tables and launches the trie walk.
-int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t D, int64_t T,
-             const double *d_lookup, int64_t lookup_rows, double *d_out, int64_t out_k_stride,
-             int64_t out_n_stride, void *d_work, int64_t work_bytes, int32_t groups,
-             hipStream_t st, const FusedArgs *fu) {
-  const std::string w(who);
-  if (N < 0 || D < 1 || T < 0) return fail(FR_E_ARG, w + ": bad shape");
-  const int64_t D_words = (fu && fu->prep) ? fu->n_prep : D;   // dimensions the words may name
-  if (p.max_dim > D_words)
-    return fail(FR_E_DIM, w + ": a word references dimension " + std::to_string(p.max_dim) +
-                              " but the input has only " + std::to_string(D_words));
-  if (N == 0 || T == 0 || p.K == 0 || (!p.cos && p.nodes.empty())) return FR_OK;
-  if (!d_X || (!fu && !d_out)) return fail(FR_E_ARG, w + ": null device pointer");
-  if (p.cos) {
-    fr::CosProgram &c = *p.cos;
-    if (c.exponent > fr::kCosMaxExponent || p.levels > 16)
-      return fail(FR_E_LIMIT, w + ": CosWISS kernels cover exponents <= 4 and words of <= 16 "
-                              "letters");
-    const size_t need = work_layout(p, N, T, 0).total();
-    if (!d_work || (size_t)work_bytes < need)
-      return fail(FR_E_NOMEM, w + ": workspace too small (need " + std::to_string(need) +
-                                  " bytes)");
-    {
-      std::lock_guard<std::mutex> lock(p.mu);
-      int rc = ensure_cos_program(p, c, st, who);
-      if (rc != FR_OK) return rc;
-    }
-    double *trig = static_cast<double *>(d_work);
-    hipError_t e = fr::launch_trig_tables(c.d_freqs, c.F, T, trig, st);
-    if (e != hipSuccess) return hip_fail(e, "trig_tables launch");
+// One call of the walk (fr_iss_run, fr_pipeline_run): what run_walk's parts share.
+struct WalkCall {
+  const char *who;
+  fr::Plan &p;
+  const double *d_X;
+  int64_t N, D, T;
+  const double *d_lookup;
+  int64_t lookup_rows;
+  double *d_out;
+  int64_t out_k_stride, out_n_stride;
+  void *d_work;
+  int64_t work_bytes;
+  int32_t groups;
+  hipStream_t st;
+  const FusedArgs *fu;
+  fr::IssArgs args() const {   // input, output and shape: the same for every kernel
     fr::IssArgs a{};
     a.X = d_X;
-    a.aux = trig;
     a.out = d_out;
     a.N = N;
     a.D = D;
     a.T = T;
     a.out_k_stride = out_k_stride;
     a.out_n_stride = out_n_stride;
-    a.factors = c.d_factors;
-    a.cw_letter_begin = c.d_letter_begin;
-    a.cw_fac_begin = c.d_fac_begin;
-    a.cw_W = c.W;
-    a.cw_F = c.F;
-    a.cw_total = c.total ? 1 : 0;
-    if (c.d_mask) {
-      if (c.mask_T != T)
-        return fail(FR_E_ARG, w + ": the dropout mask was set for series of length " +
-                                  std::to_string(c.mask_T));
-      a.cw_mask = static_cast<const double *>(c.d_mask);
-      a.cw_Lmax = c.Lmax;
-    }
-    a.cw_x_unit_stride = c.x_unit_stride;
-    if (fu && fu->prep) {
-      if (c.x_unit_stride != 0)
-        return fail(FR_E_LIMIT, w + ": a CosWISS with per-unit inputs (ffn) has no fused preparation");
-      a.prep = fu->prep;
-      a.stats = fu->stats;
-      a.n_prep = fu->n_prep;
-    }
-    a.packed = (T <= 384 && debug_knob("packed", 1) != 0) ? 1 : 0;
-    a.vec_ok = (T % 2 == 0) && aligned16(d_X) && aligned16(trig) &&
-               (fu || (aligned16(d_out) && (out_k_stride % 2 == 0) && (out_n_stride % 2 == 0)));
-    if (fu) {
-      a.ops = fu->ops;
-      a.feats = fu->feats;
-      a.cnt = fu->cnt;
-      a.feat_stride = fu->feat_stride;
-      a.n_ops = fu->n_ops;
-      a.n_ops_padded = fu->n_ops_padded;
-      a.series_cuts = fu->series_cuts;
-      a.cut_slots = fu->cut_slots;
-      // feature window of the cooperative kernel: the ops of the unit's one output row
-      a.has_mpi = fu->has_mpi ? 1 : 0;
-      a.feat_window = (fu->n_ops + 1) / 2 * 2;
-      a.feat_fits = 1;
-      if (a.feat_window > 4096)
-        return fail(FR_E_LIMIT, w + ": too many sieve features per iterated sum for the fused launch");
-    }
-    // one short-lived workgroup per (series, word, frequency) unit: 0-2.5 % faster than a
-    // persistent grid (exponent 2: 1515 -> 1478 us)
-    a.persistent = 0;
-    e = fr::launch_coswiss(a, c.exponent, st);
-    if (e != hipSuccess) return hip_fail(e, "coswiss launch");
-    return FR_OK;
+    return a;
   }
+};
+
+// `run` = false: nothing to compute.  (A CosWISS plan's own limits: run_coswiss.)
+int check_walk_args(const WalkCall &c, bool &run) {
+  const fr::Plan &p = c.p;
+  const std::string w(c.who);
+  run = false;
+  if (c.N < 0 || c.D < 1 || c.T < 0) return fail(FR_E_ARG, w + ": bad shape");
+  const int64_t D_words = (c.fu && c.fu->prep) ? c.fu->n_prep : c.D;   // dimensions the words may name
+  if (p.max_dim > D_words)
+    return fail(FR_E_DIM, w + ": a word references dimension " + std::to_string(p.max_dim) +
+                              " but the input has only " + std::to_string(D_words));
+  if (c.N == 0 || c.T == 0 || p.K == 0 || (!p.cos && p.nodes.empty())) return FR_OK;
+  if (!c.d_X || (!c.fu && !c.d_out)) return fail(FR_E_ARG, w + ": null device pointer");
+  run = true;
+  if (p.cos) return FR_OK;
   if (p.weighting != 0) {
-    if (!d_lookup) return fail(FR_E_ARG, w + ": weighted plan needs a lookup");
-    if (lookup_rows != 1 && lookup_rows != N)
+    if (!c.d_lookup) return fail(FR_E_ARG, w + ": weighted plan needs a lookup");
+    if (c.lookup_rows != 1 && c.lookup_rows != c.N)
       return fail(FR_E_ARG, w + ": lookup_rows must be 1 or N");
   }
-  const WorkLayout wl = work_layout(p, N, T, p.weighting ? lookup_rows : 0);
-  if (wl.total() > 0 && (!d_work || (size_t)work_bytes < wl.total()))
-    return fail(FR_E_NOMEM, w + ": workspace too small (need " + std::to_string(wl.total()) +
-                                " bytes)");
-  const bool vec_ok_pre = (T % 2 == 0) && aligned16(d_X) &&
-                          (fu || (aligned16(d_out) && (out_k_stride % 2 == 0) &&
-                                  (out_n_stride % 2 == 0)));
+  const size_t need = work_layout(p, c.N, c.T, p.weighting ? c.lookup_rows : 0).total();
+  if (need > 0 && (!c.d_work || (size_t)c.work_bytes < need))
+    return fail(FR_E_NOMEM, w + ": workspace too small (need " + std::to_string(need) + " bytes)");
   // the staged rows (input dimensions + exp tables) of one time chunk must fit the LDS
-  LaunchShape shape = launch_shape(p, N, T, groups);
-  if (!shape.fits)
+  if (!fr::staged_rows_fit(p, c.T))
     return fail(FR_E_LIMIT, w + ": the plan stages " + std::to_string(p.rows_staged()) +
                                 " rows per time chunk (input dimensions + exp tables of " +
                                 std::to_string(p.alphas.size()) +
                                 " distinct alphas), more than the LDS holds - split the word list");
-  // (a totally weighted plan with differencing sieves runs the cooperative kernels, which have
-  // the instantiation for it, also on short series)
-  const bool packed = shape.packed &&
-                      !(fu && fu->total_inc && p.weighting == FR_W_TOTAL);
-  const bool auto_groups = !packed && groups <= 0 && debug_knob("groups", 0) <= 0;
-  const int64_t resident = auto_groups ? query_resident(p, N, T, fu != nullptr, vec_ok_pre) : 0;
-  fr::GroupedProgram *gpp = nullptr;
-  int static_lds_pad = 0;
-  int static_wt = 0;                        // 1: the ahead-of-time program's write-through instance
-  int static_prog = 0;                      // > 0: ahead-of-time program, -1: run-time compiled
-  bool static_tail_window = false;          // one group per series, chosen by the cache-sized window
-  const int tail_knob = debug_knob("tail", -1);
-  const fr::JitProgram *jit_prog = nullptr;
+  return FR_OK;
+}
+
+// The sieve side of a fused launch, the trie walk's and CosWISS's alike.
+void apply_fused_args(const FusedArgs &fu, fr::IssArgs &a) {
+  a.ops = fu.ops;
+  a.feats = fu.feats;
+  a.cnt = fu.cnt;
+  a.feat_stride = fu.feat_stride;
+  a.n_ops = fu.n_ops;
+  a.n_ops_padded = fu.n_ops_padded;
+  a.series_cuts = fu.series_cuts;
+  a.cut_slots = fu.cut_slots;
+  a.has_mpi = fu.has_mpi ? 1 : 0;
+  if (fu.prep) {
+    a.prep = fu.prep;
+    a.stats = fu.stats;
+    a.n_prep = fu.n_prep;
+  }
+}
+
+int run_coswiss(const WalkCall &c, const fr::WalkKnobs &k) {
+  fr::Plan &p = c.p;
+  fr::CosProgram &cp = *p.cos;
+  const FusedArgs *fu = c.fu;
+  const std::string w(c.who);
+  const int64_t T = c.T;
+  if (cp.exponent > fr::kCosMaxExponent || p.levels > 16)
+    return fail(FR_E_LIMIT, w + ": CosWISS kernels cover exponents <= 4 and words of <= 16 "
+                            "letters");
+  const size_t need = work_layout(p, c.N, T, 0).total();
+  if (!c.d_work || (size_t)c.work_bytes < need)
+    return fail(FR_E_NOMEM, w + ": workspace too small (need " + std::to_string(need) +
+                                " bytes)");
   {
     std::lock_guard<std::mutex> lock(p.mu);
-    // A pre-compiled static program (walk_static_inst.hip) runs plans whose records equal one
-    // of the standard word sets': materialising, one aligned 1024-element chunk, unweighted
-    // Reals, the group count its schedule was generated for.  It reads no device tables, so
-    // nothing is uploaded for it (and a run of it is capturable without fr_plan_prepare).
-    int static_groups = 0;
-    const int asked = groups > 0 ? groups : debug_knob("groups", 0);
-    if (!fu && !packed && vec_ok_pre && static_shape_ok(p, T) && N > 0 &&
-        asked <= 3 && env_int("FRUITS_HIP_STATIC", 1) != 0) {
-      if (p.static_prog[0] < 0) {
-        const fr::GroupedProgram &g1 = fr::grouped(p, 1);
-        for (int g = 1; g <= 3; ++g)
-          p.static_prog[g] = fr::static_program_for(g1.recs.data(), (int)g1.recs.size(), g, p.row_src.data(),
-                                                       (int)p.row_src.size());
-        p.static_prog[0] = 0;
-      }
-      // no ahead-of-time program: one compiled at run time by fr_plan_prepare - or right here
-      // with FRUITS_HIP_JIT=2 (a couple of seconds, once per plan; never inside a capture)
-      const bool aot = p.static_prog[1] > 0;
-      if (!aot && env_int("FRUITS_HIP_JIT", 1) == 2 && !stream_is_capturing(st)) ensure_jit(p);
-      JitState *js = aot ? nullptr : static_cast<JitState *>(p.jit);
-      auto have = [&](int g) {
-        return p.static_prog[g] > 0 || (js != nullptr && js->progs.count(g) != 0);
-      };
-      // Groups per series.  Small batches: as many groups as the schedule has, to fill the
-      // chip.  Batches whose input + output are at most 1.4 x the 256 MiB Infinity Cache: ONE
-      // group - every input row is then read once, with non-temporal loads that do not
-      // allocate in that cache, where the input would only evict output lines (config 2:
-      // 69 -> 56 us).  Larger batches stream through HBM whatever is done; there the
-      // finer units balance better (N = 8192: 273 vs 283 us).
-      // (round 4, tools/static_window.py, fraction of 8 TB/s, one group + nt / three groups /
-      // no static program: N = 2048 (1.31 x the cache) 0.763 / 0.654 / 0.656; 2304 (1.48 x)
-      // 0.637 / 0.679 / 0.623; 3072 (1.97 x) 0.638 / 0.712 / 0.675; 4096 0.719 / 0.713 / 0.680 -
-      // the window used to end at 2 x, where the sweep showed the static program behind the
-      // walk without one)
-      const int gmax = have(3) ? 3 : (have(2) ? 2 : 1);
-      const double footprint = 8.0 * (double)N * (double)T * (double)(p.dims_used + p.K);
-      const bool cache_sized = N >= kStaticSplitBelow &&
-                               footprint <= 0.01 * debug_knob("static_cache_x100", 140) * 256.0 * 1024.0 * 1024.0;
-      static_groups = asked > 0 ? asked : (cache_sized ? 1 : gmax);
-      // (tail=S: the one-group program with its tail program at any N - see the mixed launch below)
-      if (tail_knob > 0 && asked <= 0 && aot && fr::static_program_tail_groups(p.static_prog[1]) > 0)
-        static_groups = 1;
-      // Batches that stream through HBM (beyond twice the cache): FOUR resident workgroups per
-      // CU instead of six - fewer concurrent write streams suit the memory system better
-      // (N = 4096 / 8192 / 16384: 134 -> 122, 263 -> 241, 525 -> 493 us); 16 KB of unused LDS
-      // per workgroup is how a launch asks for that.  Cache-sized and small batches keep six
-      // (N = 2048: 56.2 vs 58.6 us with four).
-      static_lds_pad = (!cache_sized && N >= kStaticSplitBelow) ? 16384 : 0;
-      // Series of 385 ... 512 elements fill half of the program's 1024-element chunk: measured
-      // (round 4, of_weight(2,3), fraction of 8 TB/s, interpreter with its 512-element chunk /
-      // static program) T = 512: N = 2048 0.572 / 0.625, 4096 0.567 / 0.744, 8192 (streams through
-      // HBM) 0.641 / 0.538; T = 400: 0.506 / 0.594, 0.559 / 0.736, 0.503 / 0.443 - the program on
-      // cache-sized batches only
-      if (have(static_groups) && (T > 512 || cache_sized)) {
-        static_prog = p.static_prog[static_groups] > 0 ? p.static_prog[static_groups] : -1;
-        if (static_prog < 0) {
-          jit_prog = &js->progs[static_groups];
-          // (a module is loaded on ONE device: elsewhere the interpreter runs the plan)
-          if (jit_prog->device != fr::current_device()) {
-            jit_prog = nullptr;
-            static_prog = 0;
-          }
-        }
-      }
-      // Cache policy of the output stores (walk_static_inst.hip: sc1 for one group, nt sc1 for
-      // three).  A plain store leaves its line dirty in the XCD's 4 MiB L2 and the launch ends
-      // with a write-back of up to 32 MiB that nothing overlaps; a write-through store sends the
-      // bytes out during the body.  Measured (of_weight(2,3), T = 1024, back-to-back us, plain ->
-      // policy, same box, three rounds): one group + nt input, N = 1536 40.5 -> 39.4, 2048
-      // 57.4 -> 54.8 (nt sc1 there: 64.8); three groups, N = 3072 93.5 -> 79.3, 8192 248 -> 193
-      // (sc1 there: 91.4, 245; at N = 2048 three groups + nt sc1 reach 61.3, behind one group).
-      // So: one group in the cache-sized window, three groups where the batch streams through
-      // HBM; small batches (unmeasured) and two-group programs keep plain stores.
-      // FRUITS_HIP_DEBUG wt=0 turns it off (A/B of one build).
-      if (static_prog > 0 && debug_knob("wt", 1) != 0)
-        static_wt = (static_groups == 1 && cache_sized) || (static_groups == 3 && static_lds_pad != 0);
-      static_tail_window = static_prog > 0 && static_groups == 1 && cache_sized && static_wt != 0;
-    }
-    const int G = static_prog ? static_groups
-                              : (auto_groups ? choose_groups_walk(p, N, T, resident, fu != nullptr) : shape.G);
-    gpp = &fr::grouped(p, G);   // (map nodes are stable: the reference outlives the lock)
-    if (!static_prog) {
-      int rc = ensure_device_program(p, *gpp, st, who);
-      if (rc != FR_OK) return rc;
-    }
+    int rc = ensure_cos_program(p, cp, c.st, c.who);
+    if (rc != FR_OK) return rc;
   }
-  fr::GroupedProgram &gp = *gpp;
+  double *trig = static_cast<double *>(c.d_work);
+  hipError_t e = fr::launch_trig_tables(cp.d_freqs, cp.F, T, trig, c.st);
+  if (e != hipSuccess) return hip_fail(e, "trig_tables launch");
+  fr::IssArgs a = c.args();
+  a.aux = trig;
+  a.factors = cp.d_factors;
+  a.cw_letter_begin = cp.d_letter_begin;
+  a.cw_fac_begin = cp.d_fac_begin;
+  a.cw_W = cp.W;
+  a.cw_F = cp.F;
+  a.cw_total = cp.total ? 1 : 0;
+  if (cp.d_mask) {
+    if (cp.mask_T != T)
+      return fail(FR_E_ARG, w + ": the dropout mask was set for series of length " +
+                                std::to_string(cp.mask_T));
+    a.cw_mask = static_cast<const double *>(cp.d_mask);
+    a.cw_Lmax = cp.Lmax;
+  }
+  a.cw_x_unit_stride = cp.x_unit_stride;
+  if (fu && fu->prep && cp.x_unit_stride != 0)
+    return fail(FR_E_LIMIT, w + ": a CosWISS with per-unit inputs (ffn) has no fused preparation");
+  a.packed = (T <= 384 && k.packed != 0) ? 1 : 0;
+  a.vec_ok = (T % 2 == 0) && aligned16(c.d_X) && aligned16(trig) &&
+             (fu || (aligned16(c.d_out) && (c.out_k_stride % 2 == 0) && (c.out_n_stride % 2 == 0)));
+  if (fu) {
+    apply_fused_args(*fu, a);
+    // feature window of the cooperative kernel: the ops of the unit's one output row
+    a.feat_window = (fu->n_ops + 1) / 2 * 2;
+    a.feat_fits = 1;
+    if (a.feat_window > 4096)
+      return fail(FR_E_LIMIT, w + ": too many sieve features per iterated sum for the fused launch");
+  }
+  // one short-lived workgroup per (series, word, frequency) unit: 0-2.5 % faster than a
+  // persistent grid (exponent 2: 1515 -> 1478 us)
+  a.persistent = 0;
+  e = fr::launch_coswiss(a, cp.exponent, c.st);
+  if (e != hipSuccess) return hip_fail(e, "coswiss launch");
+  return FR_OK;
+}
 
-  fr::IssArgs a{};
-  a.X = d_X;
-  a.out = d_out;
-  a.N = N;
-  a.n_whole = (int32_t)std::min<int64_t>(N, 0x7fffffff);   // (no finer tail units)
-  a.D = D;
-  a.T = T;
-  a.out_k_stride = out_k_stride;
-  a.out_n_stride = out_n_stride;
+// What choose_walk_launch needs to know of this call.  Caller holds p.mu.
+fr::WalkFacts gather_walk_facts(const WalkCall &c, bool vec_ok, const fr::WalkKnobs &k) {
+  fr::Plan &p = c.p;
+  const bool total_inc = c.fu && c.fu->total_inc && p.weighting == FR_W_TOTAL;
+  fr::WalkFacts f = walk_facts(p, c.N, c.T, c.groups, c.fu != nullptr, total_inc, vec_ok, k);
+  if (c.fu) f.carry_per_node = c.fu->carry_per_node;
+  if (!fr::static_launch_possible(p, f, k)) return f;
+  lookup_static_programs(p);
+  // no ahead-of-time program: one compiled at run time by fr_plan_prepare - or right here
+  // with FRUITS_HIP_JIT=2 (a couple of seconds, once per plan; never inside a capture)
+  if (p.static_prog[1] <= 0 && k.hip_jit == 2 && !stream_is_capturing(c.st)) ensure_jit(p);
+  for (int g = 1; g <= 3; ++g) f.aot[g] = p.static_prog[g];
+  // (a module is loaded on ONE device: elsewhere the interpreter runs the plan)
+  if (const JitState *js = static_cast<const JitState *>(p.jit))
+    for (const auto &kv : js->progs)
+      if (kv.first <= 3 && kv.second.device == fr::current_device()) f.jit[kv.first] = true;
+  f.tail_groups = fr::static_program_tail_groups(p.static_prog[1]);
+  f.mixed_resident = [&p, &c] { return query_mixed_resident(p.static_prog[1], c.N, c.T); };
+  return f;
+}
+
+// The kernel arguments of the launch `ch` of group program `gp`; fills the exp tables.
+int fill_walk_args(const WalkCall &c, const fr::GroupedProgram &gp, const fr::WalkChoice &ch,
+                   bool vec_ok, const fr::WalkKnobs &k, fr::IssArgs &a) {
+  const fr::Plan &p = c.p;
+  const FusedArgs *fu = c.fu;
+  const std::string w(c.who);
+  const int64_t T = c.T;
+  const WorkLayout wl = work_layout(p, c.N, T, p.weighting ? c.lookup_rows : 0);
+  a.n_whole = ch.n_whole;
   a.recs = gp.d_recs;
   a.factors = gp.d_factors;
   a.emit_rows = gp.d_emit_rows;
@@ -1344,245 +1200,196 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   a.G = gp.groups;
   a.R = p.rows_staged();
   a.total_nodes = (int32_t)p.nodes.size();
-  char *work = static_cast<char *>(d_work);
+  char *work = static_cast<char *>(c.d_work);
   if (p.weighting != 0) {
     double *aux = reinterpret_cast<double *>(work);
-    const int64_t count = lookup_rows * T;
-    hipError_t e = fr::launch_exp_tables(d_lookup, count, gp.d_alphas, (int)p.alphas.size(), aux,
-                                         p.semiring == fr::kSemiArctic, st);
+    const int64_t count = c.lookup_rows * T;
+    hipError_t e = fr::launch_exp_tables(c.d_lookup, count, gp.d_alphas, (int)p.alphas.size(), aux,
+                                         p.semiring == fr::kSemiArctic, c.st);
     if (e != hipSuccess) return hip_fail(e, "exp_tables launch");
     a.aux = aux;
     a.aux_tab_stride = count;
-    a.aux_n_stride = lookup_rows == 1 ? 0 : T;
+    a.aux_n_stride = c.lookup_rows == 1 ? 0 : T;
   }
   if (wl.carry_bytes) a.carry = reinterpret_cast<double *>(work + wl.aux_bytes);
-  a.vec_ok = vec_ok_pre && (!a.aux || aligned16(a.aux));
-  a.debug = debug_knob("stamps", 0);
+  a.vec_ok = vec_ok && (!a.aux || aligned16(a.aux));
+  a.debug = k.stamps;
   if (a.debug & 16) {
     // diagnostic build only: stamps go to the tail of the workspace if the caller
     // sized it with FRUITS_HIP_DBG_BYTES extra bytes
-    const int64_t extra = debug_knob("dbg_bytes", 0);
-    if (extra > 0 && d_work && work_bytes >= (int64_t)wl.total() + extra)
+    if (k.dbg_bytes > 0 && c.d_work && c.work_bytes >= (int64_t)wl.total() + k.dbg_bytes)
       a.dbg = reinterpret_cast<unsigned long long *>(work + align_up(wl.total(), 256));
   }
-  // Persistent grid (one resident round of workgroups striding over the units) or one
-  // short-lived workgroup per unit.  Measured (tools/gpu_persist.sh, gpu_static2.sh): the fused
-  // kernels gain 3-12 % from the hardware dispatcher's balancing (config 4: 25.1 -> 22.1 ms,
-  // config 5: 42.6 -> 37.3 ms); the materialising interpreter keeps the persistent grid up
-  // to two resident rounds (config 2: 68.9 vs 73.7 us) and drops it beyond (N = 8192:
-  // 287 -> 256 us).
-  {
-    const int64_t round = resident > 0 ? resident : 1536;
-    int by_shape = fu ? 0 : ((N * (int64_t)gp.groups < 2 * round) ? 1 : 0);
-    // wave-per-series kernels (short series), materialising: T <= 128 without the persistent
-    // grid (16384 x 128: 86 -> 77 us, 32768 x 64: 120 -> 100 us), longer ones with (8192 x 256:
-    // 71 vs 75 us)
-    if (packed && !fu) by_shape = T > 192 ? 1 : 0;
-    a.persistent = debug_knob("persist", by_shape);
-  }
-  a.packed = packed ? 1 : 0;
+  a.persistent = ch.persistent;
+  a.packed = ch.packed ? 1 : 0;
   a.prefetch_next = 24;  // longest unit (nodes) that touches its successor's rows
   a.semiring = p.semiring;
   a.letter_sum = p.letter_sum ? 1 : 0;
-  a.k_stride_bytes32 = (out_k_stride > 0 && out_k_stride < (int64_t(1) << 29))
-                           ? (uint32_t)(out_k_stride * 8) : 0u;
-  a.xcd_map = (a.G > 1 && N % 8 == 0) ? 1 : 0;
-  a.carry_slots = carry_slots_for(p, gp.groups);
-  a.carry_per_node = 3;
-  a.carry_in_lds = carries_fit_lds(p, T, gp.groups) ? 1 : 0;
-  if (fu && !packed) {
-    // the fused walk keeps its chunk carries in LDS, three slots per record of the largest group
-    int most = 0;
-    for (int g = 0; g < gp.groups; ++g) most = std::max(most, gp.group_begin[g + 1] - gp.group_begin[g]);
-    a.carry_per_node = fu->carry_per_node;
-    a.carry_slots = a.carry_per_node * most;
-    a.carry_in_lds = 1;
-  }
-  if (fu) {
-    a.ops = fu->ops;
-    a.feats = fu->feats;
-    a.cnt = fu->cnt;
-    a.feat_stride = fu->feat_stride;
-    a.n_ops = fu->n_ops;
-    a.n_ops_padded = fu->n_ops_padded;
-    a.series_cuts = fu->series_cuts;
-    a.cut_slots = fu->cut_slots;
-    a.total_inc = (fu->total_inc && p.weighting == FR_W_TOTAL) ? 1 : 0;
-    a.high_order = fu->carry_per_node > 3 ? 1 : 0;
-    a.total_weighting = p.weighting == FR_W_TOTAL ? 1 : 0;
-    a.has_mpi = fu->has_mpi ? 1 : 0;
-    if ((int64_t)p.K * fu->n_ops_padded * 32 >= (int64_t(1) << 32) || gp.recs.size() >= (size_t(1) << 26))
-      return fail(FR_E_LIMIT, w + ": the program tables exceed 4 GiB - split the word list");
-    if (!packed) {
-      const int64_t chunk = fr::walk_chunk_elems(T);
-      const size_t other = ((size_t)a.R * chunk + 24 + (T > chunk ? a.carry_slots : 0)) * 8;
-      bool fits = false;
-      a.feat_window = feat_window_for(gp, other, fu->n_ops, fu->has_mpi, fits);
-      a.feat_fits = fits ? 1 : 0;
-      if (a.feat_window == 0)
-        return fail(FR_E_LIMIT, w + ": the chunk carries and the features of one node (output rows "
-                                    "x sieve features) do not fit the LDS - split the word list");
-      if (p.letter_sum)
-        return fail(FR_E_LIMIT, w + ": letter-sum (argmax) plans have no fused walk");
-    }
-    if (fu->prep) {
-      a.prep = fu->prep;
-      a.stats = fu->stats;
-      a.n_prep = fu->n_prep;
-    }
-  }
-  a.static_prog = static_prog > 0 ? static_prog : 0;
-  a.lds_pad = static_lds_pad;
-  a.wt = static_wt;
-  // Materialising launches of the interpreter's plans run through the fused walk's node loop with
-  // a store epilogue (walk_fused.h, MODE 2: half the instructions per node) whenever that walk
-  // covers the plan: chunk carries in LDS, no letter sums (Arctic argmax).
-  const int64_t resident_round = resident > 0 ? resident : 1536;
-  if (!fu && !packed && !static_prog && !p.letter_sum && debug_knob("lean", 1) != 0 &&
-      (p.nodes.size() > 32 || N * (int64_t)gp.groups >= 2 * resident_round)) {
-    // (short plans on batches of less than two resident rounds keep the interpreter's persistent
-    // grid and its prefetch of the next unit's rows: of_weight(2,3) at N = 2048 66 vs 75 us)
-    int most = 0;
-    for (int g = 0; g < gp.groups; ++g) most = std::max(most, gp.group_begin[g + 1] - gp.group_begin[g]);
+  a.k_stride_bytes32 = (c.out_k_stride > 0 && c.out_k_stride < (int64_t(1) << 29))
+                           ? (uint32_t)(c.out_k_stride * 8) : 0u;
+  a.xcd_map = ch.xcd_map;
+  a.carry_slots = ch.carry_slots;
+  a.carry_per_node = ch.carry_per_node;
+  a.carry_in_lds = ch.carry_in_lds;
+  a.static_prog = ch.static_prog > 0 ? ch.static_prog : 0;
+  a.lds_pad = ch.lds_pad;
+  a.wt = ch.wt;
+  a.lean = ch.lean;
+  a.nt_input = ch.nt_input;
+  a.total_weighting = ((fu || ch.lean) && p.weighting == FR_W_TOTAL) ? 1 : 0;
+  if (!fu) return FR_OK;
+  apply_fused_args(*fu, a);
+  a.total_inc = (fu->total_inc && p.weighting == FR_W_TOTAL) ? 1 : 0;
+  a.high_order = fu->carry_per_node > 3 ? 1 : 0;
+  if ((int64_t)p.K * fu->n_ops_padded * 32 >= (int64_t(1) << 32) || gp.recs.size() >= (size_t(1) << 26))
+    return fail(FR_E_LIMIT, w + ": the program tables exceed 4 GiB - split the word list");
+  if (!ch.packed) {
     const int64_t chunk = fr::walk_chunk_elems(T);
-    const size_t lds = ((size_t)a.R * chunk + 24 + (T > chunk ? 3 * (size_t)most : 0)) * 8;
-    if (lds <= 40 * 1024 || T <= chunk) {
-      a.lean = 1;
-      a.carry_slots = 3 * most;
-      a.carry_in_lds = 1;
-      a.persistent = 0;
-      a.total_weighting = p.weighting == FR_W_TOTAL ? 1 : 0;
-    }
+    const size_t other = ((size_t)a.R * chunk + 24 + (T > chunk ? a.carry_slots : 0)) * 8;
+    bool fits = false;
+    a.feat_window = fr::feat_window_for(gp, other, fu->n_ops, fu->has_mpi, fits);
+    a.feat_fits = fits ? 1 : 0;
+    if (a.feat_window == 0)
+      return fail(FR_E_LIMIT, w + ": the chunk carries and the features of one node (output rows "
+                                  "x sieve features) do not fit the LDS - split the word list");
+    if (p.letter_sum)
+      return fail(FR_E_LIMIT, w + ": letter-sum (argmax) plans have no fused walk");
   }
-  // The interpreter's share of the same finding, in the window where it was measured to pay:
-  // one group per series and a batch just above the Infinity Cache (1 to 1.5 times its
-  // 256 MiB - config 2: 70 -> 65 us; 264 MB: 43 -> 45 us, 440 MB: 88 -> 93 us, so not there).
+  return FR_OK;
+}
+
+// A large plan in pieces (plan.h, PiecedProgram), where the pipeline has compiled them: one
+// launch per piece type, each over (series x the type's units); the features leave in walk
+// order.  `done` = false: the pipeline has no pieces for this launch.
+int launch_pieces(const WalkCall &c, const fr::IssArgs &a, bool &done) {
+  fr::Plan &p = c.p;
+  const FusedArgs *fu = c.fu;
+  const int64_t T = c.T;
+  done = false;
+  if (fu->walk_feats == nullptr || fu->walk_of_row == nullptr) return FR_OK;
+  const fr::FusedKey key = fused_key_for(p, T, fu->total_inc, fu->carry_per_node > 3);
+  fr_pipeline::Pieces pcs;
   {
-    const double footprint = 8.0 * (double)N * (double)T * (double)(p.dims_used + p.K);
-    const double cache = 256.0 * 1024.0 * 1024.0;
-    a.nt_input = (!fu && !packed && a.G == 1 && footprint > cache &&
-                  footprint <= 1.5 * cache) ? 1 : 0;
+    std::lock_guard<std::mutex> lock(fu->pl->jit_mu);
+    auto it = fu->pl->jit_pieces.find(key.packed());
+    if (it != fu->pl->jit_pieces.end() && !it->second.progs.empty() &&
+        it->second.device == fr::current_device())
+      pcs = it->second;
   }
-  // static programs of several groups run one short-lived workgroup per unit: the hardware
-  // dispatcher balances them and keeps the write front compact
-  if (static_prog) a.persistent = 0;
-  // The mixed launch (walk_device.h, iss_walk_static_kernel<C, PG, PGT>): a batch of between one
-  // and two resident rounds R of whole-series workgroups ends in a partial round whose workgroups
-  // live as long as those of the full one, on a chip that empties around them (DESIGN.md 4.1:
-  // N = 2048, R = 1536 - the second half of the span at a third of the occupancy).  The first R
-  // series run as whole-series units as before; the other N - R run as the finer units of the
-  // plan's multi-group program, at the end of the grid.  R is what the launcher reports for the
-  // mixed instance on this device.  Ahead-of-time programs in the cache-sized window only.
-  // NOT MEASURED YET (DESIGN.md 4.1 says how): expected from the node cost, 54.7 -> 39-47 us at
-  // N = 2048 unless the drain of the Infinity Cache (about 48 us for 302 MB) caps it.
-  // FRUITS_HIP_DEBUG tail=0 turns it off (A/B of one build); tail=S runs the last min(S, N)
-  // series as finer units at any N (tests at small shapes).
-  int64_t tail_series = 0;
-  if (static_prog > 0 && a.G == 1 && !a.persistent && tail_knob != 0 &&
-      fr::static_program_tail_groups(static_prog) > 0 && N <= 0x7fffffff) {
-    if (tail_knob > 0) {
-      tail_series = std::min<int64_t>(tail_knob, N);
-    } else if (static_tail_window) {
-      fr::IssArgs b = a;
-      int32_t R = 0;
-      b.resident_out = &R;
-      b.n_whole = 0;   // (asks the mixed instance)
-      if (fr::launch_iss_walk(b, p.levels, nullptr) != hipSuccess) (void)hipGetLastError();
-      else if (R > 0 && R < N && N < 2 * (int64_t)R) tail_series = N - R;
-    }
-    a.n_whole = (int32_t)(N - tail_series);
-  }
+  if (pcs.progs.empty()) return FR_OK;
+  const fr::PiecedProgram *pp;
   {
     std::lock_guard<std::mutex> lock(p.mu);
-    p.last_tail_series = tail_series;
+    pp = &p.pieced.at(pcs.max_piece);
   }
-  if (fu && fu->pl && !packed && fu->walk_feats != nullptr && fu->walk_of_row != nullptr) {
-    // a large plan in pieces (plan.h, PiecedProgram): one launch per piece type, each over
-    // (series x the type's units); the features leave in walk order
-    const fr::FusedKey key = fused_key_for(p, T, fu->total_inc, fu->carry_per_node > 3);
-    fr_pipeline::Pieces pcs;
-    {
-      std::lock_guard<std::mutex> lock(fu->pl->jit_mu);
-      auto it = fu->pl->jit_pieces.find(key.packed());
-      if (it != fu->pl->jit_pieces.end() && !it->second.progs.empty() &&
-          it->second.device == fr::current_device())
-        pcs = it->second;
-    }
-    if (!pcs.progs.empty()) {
-      const fr::PiecedProgram *pp;
-      {
-        std::lock_guard<std::mutex> lock(p.mu);
-        pp = &p.pieced.at(pcs.max_piece);
-      }
-      const int64_t chunk = fr::walk_chunk_elems(T);
-      const int64_t F = (int64_t)p.K * fu->pl->per_sum;
-      // (one launch per type, back to back on the caller's stream.  Forked onto side streams -
-      // normal or low priority - behind an event and joined again the launches were 0.5-2 %
-      // SLOWER on configs 4 / 5: kernels of different code on one CU share its instruction cache)
-      std::vector<size_t> order(pp->types.size());
-      for (size_t t = 0; t < order.size(); ++t) order[t] = t;
-      for (size_t oi = 0; oi < order.size(); ++oi) {
-        const size_t t = order[oi];
-        const fr::PieceType &pt = pp->types[t];
-        fr::IssArgs b = a;
-        b.recs = pt.d_recs;
-        b.emit_rows = pt.d_emit_rows;
-        b.piece_items = pt.d_items;
-        b.piece_unit_begin = pt.d_unit_begin;
-        b.piece_unit_row0 = pt.d_unit_row0;
-        b.group_begin = nullptr;
-        b.slot_rows = nullptr;
-        b.group_row_begin = nullptr;
-        b.shape_ids = nullptr;
-        b.G = pt.units();
-        b.xcd_map = (b.G > 1 && N % 8 == 0) ? 1 : 0;
-        b.ops = pcs.d_ops_walk;
-        b.feats = fu->walk_feats;
-        b.feat_stride = F;
-        b.carry_per_node = fu->carry_per_node;
-        b.carry_slots = b.carry_per_node * pt.max_unit_nodes;
-        b.carry_in_lds = 1;
-        b.persistent = 0;
-        b.nchunks = (int32_t)((T + chunk - 1) / chunk);
-        const size_t other = piece_other_lds(p, pt, T, b.carry_per_node);
-        bool fits = false;
-        b.feat_window = piece_window(p, pt, T, b.carry_per_node, fu->n_ops, fu->has_mpi, fits);
-        b.feat_fits = fits ? 1 : 0;
-        if ((pcs.fits[t] != 0) != fits)   // (the kernel was compiled for exactly this: ensure_fused_pieces)
-          return fail(FR_E_LIMIT, w + ": a piece kernel was compiled for another feature window");
-        if (b.feat_window == 0)
-          return fail(FR_E_LIMIT, w + ": the chunk carries and the features of one node do not fit the LDS");
-        const size_t lds = other + fr::feat_window_bytes(b.feat_window, b.has_mpi != 0, false);
-        hipError_t je = fr::jit_launch_fused(pcs.progs[t], b, lds, st);
-        if (je != hipSuccess) return hip_fail(je, "fused walk (a piece type) launch");
-      }
-      *fu->walk_of_row = pcs.d_walk_of_row;
-      return FR_OK;
+  const int64_t chunk = fr::walk_chunk_elems(T);
+  const int64_t F = (int64_t)p.K * fu->pl->per_sum;
+  // (one launch per type, back to back on the caller's stream.  Forked onto side streams -
+  // normal or low priority - behind an event and joined again the launches were 0.5-2 %
+  // SLOWER on configs 4 / 5: kernels of different code on one CU share its instruction cache)
+  for (size_t t = 0; t < pp->types.size(); ++t) {
+    const fr::PieceType &pt = pp->types[t];
+    fr::IssArgs b = a;
+    b.recs = pt.d_recs;
+    b.emit_rows = pt.d_emit_rows;
+    b.piece_items = pt.d_items;
+    b.piece_unit_begin = pt.d_unit_begin;
+    b.piece_unit_row0 = pt.d_unit_row0;
+    b.group_begin = b.slot_rows = b.group_row_begin = b.shape_ids = nullptr;
+    b.G = pt.units();
+    b.xcd_map = (b.G > 1 && c.N % 8 == 0) ? 1 : 0;
+    b.ops = pcs.d_ops_walk;
+    b.feats = fu->walk_feats;
+    b.feat_stride = F;
+    b.carry_per_node = fu->carry_per_node;
+    b.carry_slots = b.carry_per_node * pt.max_unit_nodes;
+    b.carry_in_lds = 1;
+    b.persistent = 0;
+    b.nchunks = (int32_t)((T + chunk - 1) / chunk);
+    const size_t other = piece_other_lds(p, pt, T, b.carry_per_node);
+    bool fits = false;
+    b.feat_window = piece_window(p, pt, T, b.carry_per_node, fu->n_ops, fu->has_mpi, fits);
+    b.feat_fits = fits ? 1 : 0;
+    if ((pcs.fits[t] != 0) != fits)   // (the kernel was compiled for exactly this: ensure_fused_pieces)
+      return fail(FR_E_LIMIT, std::string(c.who) + ": a piece kernel was compiled for another feature window");
+    if (b.feat_window == 0)
+      return fail(FR_E_LIMIT, std::string(c.who) + ": the chunk carries and the features of one node do not fit the LDS");
+    const size_t lds = other + fr::feat_window_bytes(b.feat_window, b.has_mpi != 0, false);
+    hipError_t je = fr::jit_launch_fused(pcs.progs[t], b, lds, c.st);
+    if (je != hipSuccess) return hip_fail(je, "fused walk (a piece type) launch");
+  }
+  *fu->walk_of_row = pcs.d_walk_of_row;
+  done = true;
+  return FR_OK;
+}
+
+// The pipeline's run-time compiled kernel for this instantiation (fr_pipeline_prepare).
+// `done` = false: it has none on this device.
+int launch_own_kernel(const WalkCall &c, const fr::GroupedProgram &gp, fr::IssArgs &a, bool &done) {
+  const FusedArgs *fu = c.fu;
+  done = false;
+  const fr::FusedKey key = fused_key_for(c.p, c.T, fu->total_inc, fu->carry_per_node > 3);
+  fr::JitProgram own{};
+  {
+    std::lock_guard<std::mutex> lock(fu->pl->jit_mu);
+    auto st_it = fu->pl->jit_static.find((uint64_t)key.packed() | (uint64_t)gp.groups << 32);
+    if (st_it != fu->pl->jit_static.end() && st_it->second.device == fr::current_device()) {
+      own = st_it->second;   // (the plan as straight-line code, for exactly this group program)
+    } else {
+      auto it = fu->pl->jit.find(key.packed());
+      if (it != fu->pl->jit.end()) own = it->second;
     }
   }
-  if (fu && fu->pl && !packed) {
-    // the pipeline's run-time compiled kernel for this instantiation (fr_pipeline_prepare)
-    const fr::FusedKey key = fused_key_for(p, T, fu->total_inc, fu->carry_per_node > 3);
-    fr::JitProgram own{};
-    {
-      std::lock_guard<std::mutex> lock(fu->pl->jit_mu);
-      auto st_it = fu->pl->jit_static.find((uint64_t)key.packed() | (uint64_t)gp.groups << 32);
-      if (st_it != fu->pl->jit_static.end() && st_it->second.device == fr::current_device()) {
-        own = st_it->second;   // (the plan as straight-line code, for exactly this group program)
-      } else {
-        auto it = fu->pl->jit.find(key.packed());
-        if (it != fu->pl->jit.end()) own = it->second;
-      }
+  if (own.fn == nullptr || own.device != fr::current_device()) return FR_OK;
+  const int64_t chunk = fr::walk_chunk_elems(c.T);
+  a.nchunks = (int32_t)((c.T + chunk - 1) / chunk);
+  const size_t lds = ((size_t)a.R * chunk + 16 + 8 + (a.nchunks > 1 ? a.carry_slots : 0)) * 8 +
+                     fr::feat_window_bytes(a.feat_window, a.has_mpi != 0, false);
+  hipError_t je = fr::jit_launch_fused(own, a, lds, c.st);
+  if (je != hipSuccess) return hip_fail(je, "fused walk (run-time compiled) launch");
+  done = true;
+  return FR_OK;
+}
+
+// Shared body of fr_iss_run and fr_pipeline_run: validates, chooses the launch
+// (launch_choice.h), fills the exp tables and launches the trie walk.
+int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t D, int64_t T,
+             const double *d_lookup, int64_t lookup_rows, double *d_out, int64_t out_k_stride,
+             int64_t out_n_stride, void *d_work, int64_t work_bytes, int32_t groups,
+             hipStream_t st, const FusedArgs *fu) {
+  const WalkCall c{who, p, d_X, N, D, T, d_lookup, lookup_rows, d_out, out_k_stride, out_n_stride,
+                   d_work, work_bytes, groups, st, fu};
+  const fr::WalkKnobs k = read_walk_knobs();
+  bool run = false, done = false;
+  int rc = check_walk_args(c, run);
+  if (rc != FR_OK || !run) return rc;
+  if (p.cos) return run_coswiss(c, k);
+  const bool vec_ok = (T % 2 == 0) && aligned16(d_X) &&
+                      (fu || (aligned16(d_out) && (out_k_stride % 2 == 0) && (out_n_stride % 2 == 0)));
+  fr::WalkChoice ch;
+  fr::GroupedProgram *gp = nullptr;
+  const fr::JitProgram *jit_prog = nullptr;
+  {
+    std::lock_guard<std::mutex> lock(p.mu);
+    ch = fr::choose_walk_launch(p, gather_walk_facts(c, vec_ok, k), k);
+    gp = &fr::grouped(p, ch.G);   // (map nodes are stable: the pointer outlives the lock)
+    if (ch.static_prog < 0) jit_prog = &static_cast<JitState *>(p.jit)->progs[ch.G];
+    if (!ch.static_prog) {   // (a static program reads no device tables)
+      rc = ensure_device_program(p, *gp, st, who);
+      if (rc != FR_OK) return rc;
     }
-    if (own.fn != nullptr && own.device == fr::current_device()) {
-      const int64_t chunk = fr::walk_chunk_elems(T);
-      a.nchunks = (int32_t)((T + chunk - 1) / chunk);
-      const size_t lds = ((size_t)a.R * chunk + 16 + 8 + (a.nchunks > 1 ? a.carry_slots : 0)) * 8 +
-                         fr::feat_window_bytes(a.feat_window, a.has_mpi != 0, false);
-      hipError_t je = fr::jit_launch_fused(own, a, lds, st);
-      if (je != hipSuccess) return hip_fail(je, "fused walk (run-time compiled) launch");
-      return FR_OK;
-    }
+  }
+  fr::IssArgs a = c.args();
+  rc = fill_walk_args(c, *gp, ch, vec_ok, k, a);
+  if (rc != FR_OK) return rc;
+  {
+    std::lock_guard<std::mutex> lock(p.mu);
+    p.last_tail_series = ch.tail_series;
+  }
+  if (fu && fu->pl && !ch.packed) {
+    rc = launch_pieces(c, a, done);
+    if (rc == FR_OK && !done) rc = launch_own_kernel(c, *gp, a, done);
+    if (rc != FR_OK || done) return rc;
   }
   hipError_t e = jit_prog ? fr::jit_launch(*jit_prog, a, st) : fr::launch_iss_walk(a, p.levels, st);
   if (e != hipSuccess) return hip_fail(e, "iss_walk launch");
@@ -1994,37 +1801,34 @@ int fr_pipeline_set_preparation(fr_pipeline_t *pl, int32_t D, int32_t inc_lag, i
 // The kernel instantiation a fused launch of this pipeline over N series takes, or false when
 // it has none of its own (CosWISS, wave-per-series kernels, letter sums, nothing fits).
 static bool fused_instance_of(fr_pipeline_t *pl, int64_t N, int32_t groups, fr::FusedKey &key,
-                              LaunchShape &shape) {
+                              const fr::WalkKnobs &k) {
   fr::Plan &p = *pl->plan->p;
-  if (p.cos || N <= 0 || env_int("FRUITS_HIP_JIT", 1) == 0 || p.letter_sum) return false;
+  if (p.cos || N <= 0 || k.hip_jit == 0 || p.letter_sum) return false;
   bool total_inc = false;
   for (const PipeSieve &sv : pl->sieves)
     if (sv.kind != FR_SIEVE_END && sv.inc >= 1) total_inc = true;
-  shape = launch_shape(p, N, pl->T, groups);
-  const bool packed = shape.packed && !(total_inc && p.weighting == FR_W_TOTAL);
-  if (packed || !shape.fits) return false;
+  const fr::LaunchShape shape = fr::launch_shape(p, N, pl->T, groups, k);
+  if (fr::walk_is_packed(shape, total_inc && p.weighting == FR_W_TOTAL) || !shape.fits) return false;
   key = fused_key_for(p, pl->T, total_inc, pl->jit_ops.cps > 3);
   return true;
 }
 
-static int pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups, bool cache_only);
-
-static int pipeline_prepare(fr_pipeline_t *pl, int64_t N, int32_t groups, bool cache_only) {
+static int pipeline_prepare(fr_pipeline_t *pl, int64_t N, int32_t groups, bool cache_only,
+                            const fr::WalkKnobs &k) {
   if (!pl || !pl->plan || !pl->plan->p || N < 0)
     return fail(FR_E_ARG, "fr_pipeline_prepare: bad argument");
   if (!pl->have_quantiles)
     return fail(FR_E_ARG, "fr_pipeline_prepare: call fr_pipeline_set_quantiles first");
   fr::Plan &p = *pl->plan->p;
   if (!pl->argmax_words.empty())   // (the plan runs as a materialising walk, the sieves in a kernel of the library)
-    return prepare_plan(p, N, pl->T, groups, false, "fr_pipeline_prepare");
-  int rc = prepare_plan(p, N, pl->T, groups, true, "fr_pipeline_prepare");
+    return prepare_plan(p, N, pl->T, groups, false, "fr_pipeline_prepare", k);
+  int rc = prepare_plan(p, N, pl->T, groups, true, "fr_pipeline_prepare", k);
   if (rc != FR_OK) return rc;
   // The pipeline's own kernel: the fused walk with the sieves as compile-time constants (hipRTC,
   // 1-2 s once per pipeline shape, cached on disk); a failure is not the caller's - the generic
   // kernel runs the pipeline.  Not for the wave-per-series kernels (T <= 384) and CosWISS.
   fr::FusedKey key;
-  LaunchShape shape;
-  if (fused_instance_of(pl, N, groups, key, shape)) {
+  if (fused_instance_of(pl, N, groups, key, k)) {
     // (a large plan runs in pieces: their tables go up here, on the caller's thread)
     if (pieces_eligible(*pl)) {
       rc = ensure_pieces_tables(*pl, key, "fr_pipeline_prepare");
@@ -2035,28 +1839,15 @@ static int pipeline_prepare(fr_pipeline_t *pl, int64_t N, int32_t groups, bool c
   return FR_OK;
 }
 
-int fr_pipeline_prepare(fr_pipeline_t *pl, int64_t N, int32_t groups) {
-  return pipeline_prepare(pl, N, groups, false);
-}
-
-int fr_pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups) {
-  return pipeline_compile_plan(pl, N, groups, false);
-}
-
-int fr_pipeline_prepare_cached(fr_pipeline_t *pl, int64_t N, int32_t groups) {
-  int rc = pipeline_prepare(pl, N, groups, true);
-  return rc != FR_OK ? rc : pipeline_compile_plan(pl, N, groups, true);
-}
-
-static int pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups, bool cache_only) {
+static int pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups, bool cache_only,
+                                 const fr::WalkKnobs &k) {
   if (!pl || !pl->plan || !pl->plan->p || N < 0)
     return fail(FR_E_ARG, "fr_pipeline_compile_plan: bad argument");
   if (!pl->have_quantiles)
     return fail(FR_E_ARG, "fr_pipeline_compile_plan: call fr_pipeline_set_quantiles first");
   fr::Plan &p = *pl->plan->p;
   fr::FusedKey key;
-  LaunchShape shape;
-  if (!fused_instance_of(pl, N, groups, key, shape) || debug_knob("fused_static", 1) == 0) return FR_OK;
+  if (!fused_instance_of(pl, N, groups, key, k) || debug_knob("fused_static", 1) == 0) return FR_OK;
   // a large plan: in pieces, every piece type straight-line code in a kernel of its own; the
   // node shapes below only where the plan has no such cover
   if (pieces_eligible(*pl)) {
@@ -2072,12 +1863,10 @@ static int pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups, b
   }
   // for the group program a launch over N series will pick (another group count at run time
   // simply takes the kernel of fr_pipeline_prepare)
-  const int asked = groups > 0 ? groups : debug_knob("groups", 0);
   fr::FusedPlan fp;
   {
     std::lock_guard<std::mutex> lock(p.mu);
-    const int G = asked > 0 ? shape.G
-                            : choose_groups_walk(p, N, pl->T, query_resident(p, N, pl->T, true, true), true);
+    const int G = fr::choose_walk_launch(p, walk_facts(p, N, pl->T, groups, true, key.TI != 0, true, k), k).G;
     const fr::GroupedProgram &gp = fr::grouped(p, G);
     if ((int)p.nodes.size() <= fr::kFusedStaticMaxNodes) {
       // a small plan: the records themselves (straight-line code)
@@ -2094,6 +1883,20 @@ static int pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups, b
   }
   ensure_fused_static(*pl, key, fp, cache_only);
   return FR_OK;
+}
+
+int fr_pipeline_prepare(fr_pipeline_t *pl, int64_t N, int32_t groups) {
+  return pipeline_prepare(pl, N, groups, false, read_walk_knobs());
+}
+
+int fr_pipeline_compile_plan(fr_pipeline_t *pl, int64_t N, int32_t groups) {
+  return pipeline_compile_plan(pl, N, groups, false, read_walk_knobs());
+}
+
+int fr_pipeline_prepare_cached(fr_pipeline_t *pl, int64_t N, int32_t groups) {
+  const fr::WalkKnobs k = read_walk_knobs();
+  int rc = pipeline_prepare(pl, N, groups, true, k);
+  return rc != FR_OK ? rc : pipeline_compile_plan(pl, N, groups, true, k);
 }
 
 int32_t fr_pipeline_bundle(fr_pipeline_t *pl, const double *h_quant, int32_t groups, const char *dir,
@@ -2113,8 +1916,7 @@ int32_t fr_pipeline_bundle(fr_pipeline_t *pl, const double *h_quant, int32_t gro
     jops = pl->jit_ops;
   }
   fr::FusedKey key;
-  LaunchShape shape;
-  if (!fused_instance_of(pl, 1 << 20, groups, key, shape)) return 0;
+  if (!fused_instance_of(pl, 1 << 20, groups, key, read_walk_knobs())) return 0;
   std::vector<std::string> errs;
   std::atomic<int> done{0};
   std::mutex err_mu;

@@ -4,14 +4,12 @@
 
 #include <cstdint>
 
+#include "launch_choice.h"   // walk_chunk_elems, packed_supported
 #include "plan.h"
 #include "walk_types.h"
 
 namespace fr {
 
-
-int walk_chunk_elems(int64_t T);
-bool packed_supported(int64_t T, int levels, int semiring);
 int static_program_for(const NodeRec *recs, int n, int groups, const int32_t *row_src, int rows);
 int static_program_tail_groups(int prog);
 hipError_t launch_iss_walk(IssArgs &a, int levels, hipStream_t st);

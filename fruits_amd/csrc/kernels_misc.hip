@@ -1587,8 +1587,6 @@ hipError_t launch_select_ranks(void *jobs, int n_jobs, const void *groups, int n
 }
 
 // ---------------------------------------------------------------- launchers
-int walk_chunk_elems(int64_t T) { return T <= 512 ? 512 : 1024; }
-
 #define DECL_INST(m, l) hipError_t walk_inst_m##m##_l##l(const IssArgs &, int, hipStream_t);
 DECL_INST(0, 2) DECL_INST(0, 4) DECL_INST(0, 6) DECL_INST(0, 8)
 DECL_INST(1, 2) DECL_INST(1, 4) DECL_INST(1, 6) DECL_INST(1, 8)
@@ -1596,14 +1594,6 @@ DECL_INST(2, 2) DECL_INST(2, 4) DECL_INST(2, 6) DECL_INST(2, 8)
 hipError_t walk_static_launch(const IssArgs &, hipStream_t);
 hipError_t walk_packed_inst_m0(const IssArgs &, int, hipStream_t);
 hipError_t walk_packed_inst_m1(const IssArgs &, int, hipStream_t);
-
-// short series: four series per workgroup, one wave each (walk_packed.h)
-bool packed_supported(int64_t T, int levels, int semiring) {
-  (void)semiring;  // all three semirings are instantiated
-  // measured against the cooperative kernel: T = 300 138 -> 88 us, T = 384 143 -> 100 us;
-  // beyond (4 pieces per wave, 8 elements per lane) it is no faster (T = 512: 73 vs 79 us)
-  return (T <= 256 && levels <= 8) || (T <= 384 && levels <= 4);
-}
 
 hipError_t launch_iss_walk(IssArgs &a, int levels, hipStream_t st) {
   const int chunk = walk_chunk_elems(a.T);

@@ -403,6 +403,170 @@ def test_plan_compiler_sanitized(tmp_path):
     assert "K=18 nodes=18" in r.stdout.splitlines()[0]
 
 
+def test_launch_choice_table(tmp_path):
+    """The launch choice of the trie walk (csrc/launch_choice.h, choose_walk_launch) is a pure
+    function of facts and knobs: compiled for the host (tests/native/launch_choice_host.cpp, with
+    plan.cpp) it is pinned cell by cell - the rules of DESIGN.md 4.1 with one resident round of
+    1536 workgroups and R = 1536 for the mixed instance, of_weight(2,3) EXTENDED with
+    ahead-of-time programs for one and three groups and a tail program unless a row says
+    otherwise.  A change of the rules shows here as the rows that moved.  Built a second time
+    under AddressSanitizer + UBSan where the runtime exists (host code only)."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    srcs = [os.path.join(ROOT, "tests", "native", "launch_choice_host.cpp"),
+            os.path.join(ROOT, "fruits_amd", "csrc", "plan.cpp")]
+
+    def plan(words, weighting=0, flags=1, letter_depths=False):
+        ws = [fr.words.SimpleWord(s) for s in words]
+        depths = [w.table().shape[0] for w in ws] if letter_depths else orc.cache_plan(words)
+        lines = [f"{len(ws)} {weighting} {flags}"]
+        for w, d in zip(ws, depths):
+            t = w.table()
+            lines.append(f"{t.shape[0]} {t.shape[1]} {d} " + " ".join(str(int(v)) for v in t.ravel())
+                         + " " + " ".join(["1.0"] * t.shape[0]))
+        return "\n".join(lines)
+
+    P23, P11, P42, P62, P91, PTOT, PARC = range(7)
+    plans = [plan(M["words"]["2,3"]["words"]),
+             plan([str(w) for w in fr.words.of_weight(1, dim=1)]),
+             plan(M["words"]["4,2"]["words"]), plan(M["words"]["6,2"]["words"]),
+             plan(M["words"]["9,1"]["words"]),
+             plan(M["words"]["2,3"]["words"], weighting=nat.FR_W_TOTAL),
+             plan(M["words"]["2,3"]["words"], flags=1 | 2 | 8, letter_depths=True)]
+    UNSET = -2 ** 31
+
+    def case(N, T=1024, p=P23, aot=(16, 0, 17), tail_groups=3, groups=0, fused=0, total_inc=0,
+             per_node=3, k_groups=0, wt=1, tail=-1, static=1):
+        if p != P23:
+            aot, tail_groups = ((1, 0, 0), 0) if p == P11 else ((0, 0, 0), 0)
+        resident = 0 if groups > 0 or k_groups > 0 else 1536   # (asked only where the host chooses)
+        return (f"{p} {N} {T} {groups} {fused} {total_inc} {per_node} 1 {resident} {aot[0]} {aot[1]} {aot[2]} 0 "
+                f"{tail_groups} 1536  {k_groups} {UNSET} 1 1 {wt} {tail} 140 384 {static}")
+
+    table = [
+        # small batch: every group of the schedule, plain stores
+        (case(512),
+         "packed=0 G=3 static=17 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=512 xcd=1 mixed_asked=0"),
+        # one resident round exactly: whole series, no tail
+        (case(1536),
+         "packed=0 G=1 static=16 wt=1 pad=0 cache=1 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=1536 xcd=0 mixed_asked=1"),
+        (case(1537),
+         "packed=0 G=1 static=16 wt=1 pad=0 cache=1 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=1 whole=1536 xcd=0 mixed_asked=1"),
+        # the headline: one group, write-through, 512 series as finer units
+        (case(2048),
+         "packed=0 G=1 static=16 wt=1 pad=0 cache=1 lean=0"
+         " persistent=0 nt=1 slots=90 per_node=3 in_lds=1 tail=512 whole=1536 xcd=0 mixed_asked=1"),
+        # 1.48 x the cache: three groups, four workgroups per CU
+        (case(2304),
+         "packed=0 G=3 static=17 wt=1 pad=16384 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=2304 xcd=1 mixed_asked=0"),
+        (case(3072),
+         "packed=0 G=3 static=17 wt=1 pad=16384 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=3072 xcd=1 mixed_asked=0"),
+        (case(8192),
+         "packed=0 G=3 static=17 wt=1 pad=16384 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=8192 xcd=1 mixed_asked=0"),
+        # T = 512: the program on cache-sized batches only (there with its mixed launch) ...
+        (case(2048, T=512),
+         "packed=0 G=1 static=16 wt=1 pad=0 cache=1 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=512 whole=1536 xcd=0 mixed_asked=1"),
+        # ... beyond, the lean walk - which keeps the LDS pad of the shape
+        (case(8192, T=512),
+         "packed=0 G=3 static=0 wt=0 pad=16384 cache=0 lean=1"
+         " persistent=0 nt=0 slots=21 per_node=3 in_lds=1 tail=0 whole=8192 xcd=1 mixed_asked=0"),
+        # static_shape_ok rejects T <= static_min_T, packed_supported accepts (levels <= 4)
+        (case(2048, T=384),
+         "packed=1 G=4 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=1 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=2048 xcd=1 mixed_asked=0"),
+        (case(8192, T=256),
+         "packed=1 G=1 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=1 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=8192 xcd=0 mixed_asked=0"),
+        (case(16384, T=128),
+         "packed=1 G=1 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=16384 xcd=0 mixed_asked=0"),
+        # FRUITS_HIP_STATIC=0: the interpreter, persistent, non-temporal input
+        (case(2048, static=0),
+         "packed=0 G=1 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=1 nt=1 slots=90 per_node=3 in_lds=1 tail=0 whole=2048 xcd=0 mixed_asked=0"),
+        (case(4096, static=0),
+         "packed=0 G=3 static=0 wt=0 pad=0 cache=0 lean=1"
+         " persistent=0 nt=0 slots=21 per_node=3 in_lds=1 tail=0 whole=4096 xcd=1 mixed_asked=0"),
+        # min(ceil(1536 / 64), 6) groups (the plan has 9 units)
+        (case(64, static=0),
+         "packed=0 G=6 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=1 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=64 xcd=1 mixed_asked=0"),
+        # the tail rule needs the write-through instance
+        (case(2048, wt=0),
+         "packed=0 G=1 static=16 wt=0 pad=0 cache=1 lean=0"
+         " persistent=0 nt=1 slots=90 per_node=3 in_lds=1 tail=0 whole=2048 xcd=0 mixed_asked=0"),
+        (case(2048, tail=0),
+         "packed=0 G=1 static=16 wt=1 pad=0 cache=1 lean=0"
+         " persistent=0 nt=1 slots=90 per_node=3 in_lds=1 tail=0 whole=2048 xcd=0 mixed_asked=0"),
+        (case(24, tail=8),
+         "packed=0 G=1 static=16 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=8 whole=16 xcd=0 mixed_asked=0"),
+        # no tail program
+        (case(24, tail=8, p=P11),
+         "packed=0 G=1 static=1 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=39 per_node=3 in_lds=1 tail=0 whole=24 xcd=0 mixed_asked=0"),
+        # no two-group program: the lean walk (4096 units are two rounds)
+        (case(2048, k_groups=2),
+         "packed=0 G=2 static=0 wt=0 pad=0 cache=1 lean=1"
+         " persistent=0 nt=0 slots=30 per_node=3 in_lds=1 tail=0 whole=2048 xcd=1 mixed_asked=0"),
+        (case(2048, k_groups=2, aot=(16, 99, 17)),
+         "packed=0 G=2 static=99 wt=0 pad=0 cache=1 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=2048 xcd=1 mixed_asked=0"),
+        # 115 nodes: no static program (the shape's pad stays)
+        (case(2048, p=P42),
+         "packed=0 G=2 static=0 wt=0 pad=16384 cache=0 lean=1"
+         " persistent=0 nt=0 slots=177 per_node=3 in_lds=1 tail=0 whole=2048 xcd=1 mixed_asked=0"),
+        # four chunks: rows + 3 x 40 carries fit 40 KiB
+        (case(512, T=4096, p=P42),
+         "packed=0 G=3 static=0 wt=0 pad=0 cache=0 lean=1"
+         " persistent=0 nt=0 slots=120 per_node=3 in_lds=1 tail=0 whole=512 xcd=1 mixed_asked=0"),
+        (case(2048, p=P42, fused=1, per_node=5),
+         "packed=0 G=1 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=580 per_node=5 in_lds=1 tail=0 whole=2048 xcd=0 mixed_asked=0"),
+        (case(8192, p=P62, fused=1),
+         "packed=0 G=2 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=2031 per_node=3 in_lds=1 tail=0 whole=8192 xcd=1 mixed_asked=0"),
+        # >= 400 nodes over several chunks
+        (case(8192, T=4096, p=P91, fused=1),
+         "packed=0 G=2 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=771 per_node=3 in_lds=1 tail=0 whole=8192 xcd=1 mixed_asked=0"),
+        # differencing sieves on a totally weighted plan: never packed
+        (case(4096, T=256, p=PTOT, fused=1, total_inc=1),
+         "packed=0 G=1 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=57 per_node=3 in_lds=1 tail=0 whole=4096 xcd=0 mixed_asked=0"),
+        # Arctic letter sums: never lean
+        (case(8192, p=PARC),
+         "packed=0 G=3 static=0 wt=0 pad=0 cache=0 lean=0"
+         " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=8192 xcd=1 mixed_asked=0"),
+    ]
+    text = (f"{len(plans)}\n" + "\n".join(plans) + f"\n{len(table)}\n"
+            + "\n".join(c for c, _ in table) + "\n")
+    for flags in ([], ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]):
+        exe = str(tmp_path / ("launch_choice" + ("_san" if flags else "")))
+        r = subprocess.run([gxx, "-std=c++17", "-O1", "-Wall"] + flags + srcs + ["-o", exe],
+                           capture_output=True, text=True)
+        if flags and r.returncode != 0 and "sanitize" in r.stderr:
+            pytest.skip("sanitizer runtime not available: " + r.stderr[-200:])
+        assert r.returncode == 0, r.stderr
+        assert "warning" not in r.stderr, r.stderr
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+        r = subprocess.run([exe], input=text, capture_output=True, text=True, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        got = dict(re.findall(r"^case (\d+): (.*)$", r.stdout, re.M))
+        for i, (c, want) in enumerate(table):
+            assert got[str(i)] == want, (i, c)
+
+
 def test_numpy_sum_model(tmp_path):
     """STD's statistics follow numpy's summation order (csrc/pairwise.h): the order logic of the
     device routine, compiled for the host (tests/native/pairwise_host.cpp, the lanes' shuffles
