@@ -1430,7 +1430,7 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
     const int c1 = C1[i];
     std::string bad;
     int code = FR_E_ARG;
-    if (sv.kind < 0 || sv.kind > FR_SIEVE_LPI || c1 < 2) bad = "bad sieve " + std::to_string(i);
+    if (sv.kind < 0 || sv.kind > FR_SIEVE_CUR || c1 < 2) bad = "bad sieve " + std::to_string(i);
     else if (sv.kind == FR_SIEVE_LPI) {
       // (a run crosses lanes, waves and time chunks: the window has no carry for it)
       bad = "LPI is not fused";
@@ -2221,7 +2221,7 @@ int fr_pathlen_lookup(const double *d_X, int64_t N, int64_t D, int64_t T, int32_
 int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride, int32_t inc,
              const int64_t *d_cuts, int64_t cut_rows, int32_t C1, const double *d_q, int32_t Q1,
              double *d_out, int64_t out_stride, void *stream) {
-  if (kind < 0 || kind > FR_SIEVE_LPI) return fail(FR_E_ARG, "fr_sieve: unknown kind");
+  if (kind < 0 || kind > FR_SIEVE_CUR) return fail(FR_E_ARG, "fr_sieve: unknown kind");
   if (N < 0 || T < 1 || C1 < 2 || (cut_rows != 1 && cut_rows != N))
     return fail(FR_E_ARG, "fr_sieve: bad shape");
   if (kind != FR_SIEVE_END && (Q1 < 2 || !d_q)) return fail(FR_E_ARG, "fr_sieve: bad quantiles");

@@ -236,7 +236,8 @@ __global__ __launch_bounds__(256) void sieve_kernel(int kind, const double *__re
       for (int64_t t = lo + tid; t < hi; t += blockDim.x) {
         const double v = diff_at(row, t, inc);
         if (qlo < v && v <= qhi) {
-          sum += v;
+          // CUR (segment.py:242-260): the squares; no population, nothing divides the sum
+          sum += kind == FR_SIEVE_CUR_K ? v * v : v;
           cnt += 1.0;
         }
       }
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(256) void sieve_kernel(int kind, const double *__re
           c += sm_cnt[w];
         }
         out[n * out_stride + j * Q + k] =
-            (kind == FR_SIEVE_NPI_K) ? c : (c > 0.0 ? s / c : 0.0);
+            (kind == FR_SIEVE_NPI_K) ? c : (kind == FR_SIEVE_CUR_K ? s : (c > 0.0 ? s / c : 0.0));
       }
     }
   }
@@ -1850,7 +1851,7 @@ hipError_t launch_sieve(int kind, const double *A, int64_t N, int64_t T, int64_t
                         const int64_t *cuts, int64_t cut_rows, int C1, const double *q, int Q1,
                         double *out, int64_t out_stride, hipStream_t st) {
   if (N <= 0) return hipSuccess;
-  if (kind >= FR_SIEVE_MAX_K)
+  if (kind >= FR_SIEVE_MAX_K && kind != FR_SIEVE_CUR_K)   // (CUR: a sum per band, like NPI / MPI)
     hipLaunchKernelGGL(band_sieve_kernel, dim3((unsigned)N), dim3(256), 0, st, kind, A, T, a_stride,
                        inc, cuts, cut_rows, C1, q, Q1, out, out_stride);
   else

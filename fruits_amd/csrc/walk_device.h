@@ -669,6 +669,26 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
     }
     return;
   }
+  if (kind == FR_SIEVE_CUR_K) {
+    // CUR (fruits/sieving/segment.py:228-272): the sum of the squares inside the band; no
+    // population, nothing divides it - the waves' (and the chunks') partial sums add up
+    double sum = 0.0;
+#pragma unroll
+    for (int h = 0; h < P; ++h)
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int t = t_first + h * C::PIECE + e;
+        const double v = d[h * E + e];
+        const bool in = t >= lo && t < hi && qlo < v && v <= qhi;
+        sum += in ? v * v : 0.0;
+      }
+    sum = wave_last_lane(wave_inclusive_scan<0>(sum));
+    if (cx.lane == 0) {
+      if constexpr (C::TEAM != 1) lds_add(cx.fl_val + slot, sum);
+      else cx.feat_row[col] = sum;
+    }
+    return;
+  }
   // XPI: the sum of MPI is one of positions relative to the segment start (integers: exact)
   const bool mpi = kind == FR_SIEVE_MPI_K || kind == FR_SIEVE_XPI_K;
   int cnt = 0;

@@ -70,6 +70,10 @@ __device__ __forceinline__ void lds_add_lane0(int off, double v) {
   asm volatile("s_mov_b64 exec, 1\n\tds_add_f64 %0, %1\n\ts_mov_b64 exec, -1"
                :: "v"(off), "v"(v) : "memory");
 }
+__device__ __forceinline__ void lds_add_lane63(int off, double v) {
+  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_add_f64 %0, %1\n\ts_mov_b64 exec, -1"
+               :: "v"(off), "v"(v) : "memory", "scc");
+}
 __device__ __forceinline__ void lds_add2_lane63(int off0, double v0, int off1, double v1) {
   asm volatile("s_lshl_b64 exec, 1, 63\n\tds_add_f64 %0, %1\n\tds_add_f64 %2, %3\n\ts_mov_b64 exec, -1"
                :: "v"(off0), "v"(v0), "v"(off1), "v"(v1) : "memory", "scc");
@@ -432,6 +436,22 @@ __device__ __forceinline__ void fop(WalkCtx &cx, const int32_t *w, int slot, con
     }
     key = wave_max_u64(key);
     if (cx.lane == 0) lds_max_u64(cx.fl_val + slot, key);
+    return;
+  }
+  if (kind == FR_SIEVE_CUR_K) {
+    // CUR (fruits/sieving/segment.py:228-272): the sum of the squares inside the band.  No
+    // population and nothing to divide: the partial sums of the waves - and, through the flush,
+    // of the time chunks - add up in fl_val like NPI's counts
+    double sum = 0.0;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int t = t_first + e;
+      const double v = d[e];
+      const bool in = t >= lo && t < hi && qlo < v && v <= qhi;
+      sum += in ? v * v : 0.0;
+    }
+    sum = wave_inclusive_scan<0>(sum);  // lane 63 holds the wave total
+    lds_add_lane63(lds_offset(cx.fl_val + slot), sum);
     return;
   }
   // XPI: MPI of the positions relative to the segment start (integer sums: exact in any order)

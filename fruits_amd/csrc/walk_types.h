@@ -96,6 +96,7 @@ constexpr int FR_SIEVE_MAX_K = 3;
 constexpr int FR_SIEVE_MIN_K = 4;
 constexpr int FR_SIEVE_XPI_K = 5;
 constexpr int FR_SIEVE_LPI_K = 6;
+constexpr int FR_SIEVE_CUR_K = 7;
 
 #if defined(__HIP__) || defined(__HIPCC_RTC__)
 #define FR_HOST_DEVICE __host__ __device__

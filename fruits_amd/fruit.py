@@ -65,7 +65,7 @@ class _FittedRows:
                 if r0 <= k < r0 + n:
                     for i, sv in enumerate(fitted):
                         if qs[i] is not None:
-                            qs[i][k - r0] = sv._quantiles
+                            qs[i][k - r0] = _leaf(sv)._quantiles
             yield r0, n, qs
 
     def add_rows(self, n: int) -> list:
@@ -98,7 +98,7 @@ class _FittedRows:
             for sv, q in zip(fitted, qs):
                 sv._cache = self._cache
                 if q is not None:
-                    sv._quantiles = q[k - r0].copy()
+                    _leaf(sv)._quantiles = q[k - r0].copy()
             self._made[k] = fitted
         return fitted
 
@@ -111,6 +111,20 @@ class _FittedRows:
         else:
             table = np.concatenate([qs[i] for _, _, qs in self._with_made()])
         return table[np.asarray(rows, dtype=np.int64)]
+
+
+def _reduced(sv):
+    """(sieve that holds the cuts and thresholds, FR_SIEVE_* kind, differencing order of the
+    transform, of the fit) of a sieve the fused pipeline or the device-side fit can express
+    (SegmentSieve._reduced; a wrapper of sieving/wrapper.py answers for its inner sieve), else
+    None."""
+    return sv._reduced() if hasattr(sv, "_reduced") else None
+
+
+def _leaf(sv):
+    """The sieve that holds ``sv``'s thresholds: the inner sieve of a reducible wrapper."""
+    form = _reduced(sv)
+    return sv if form is None else form[0]
 
 
 def _interpolated_quantiles(sieve, reqs, lo_vals: np.ndarray, hi_vals: np.ndarray) -> np.ndarray:
@@ -451,13 +465,17 @@ class FruitSlice:
         forms the thresholds is appended - Fruit.fit runs them when every slice has been queued,
         so that the device goes from one slice's selection to the next slice's iterated sums
         without waiting for the host."""
-        from .sieving.segment import SegmentSieve
         if os.environ.get("FRUITS_AMD_DEVICE_FIT", "1") == "0" or len(self._iss) != 1:
             return False
-        for sv in self._sieves:
-            if sv.requires_fitting and not (isinstance(sv, SegmentSieve)
-                                            and 0 <= getattr(sv, "_inc", 0) <= 8):
+        # (a sieve wrapper that is its inner sieve at another differencing order is fitted as
+        # that: the thresholds belong to the inner sieve - _reduced, sieving/wrapper.py)
+        forms = [_reduced(sv) for sv in self._sieves]
+        for sv, form in zip(self._sieves, forms):
+            if sv.requires_fitting and not (form is not None and 0 <= form[3] <= 8):
                 return False
+        # what asks for order statistics, and the differencing order it asks them of
+        leaves = [None if form is None else form[0] for form in forms]
+        fit_inc = [None if form is None else form[3] for form in forms]
         iss = self._iss[0]
         Ns, T = int(Sd.shape[0]), int(Sd.shape[2])
         n = Ns * T
@@ -467,7 +485,8 @@ class FruitSlice:
             block = iss.transform_device(Sd, s, e, lookup)
             # (what a sieve asks for depends on its q and the sample size only: once per sieve,
             # not once per copy)
-            asks = [sv._quantile_requests(n) if sv.requires_fitting else None for sv in self._sieves]
+            asks = [leaf._quantile_requests(n) if sv.requires_fitting else None
+                    for sv, leaf in zip(self._sieves, leaves)]
             # Every iterated sum is asked for the same order statistics: the jobs of ONE row -
             # (differencing order, rank) pairs, those that several sieves share (NPI / MPI with the
             # same band) once - are laid out as a template and repeated for the rows with numpy
@@ -475,17 +494,17 @@ class FruitSlice:
             # device idle for 2-4 ms per slice between the iterated sums and their selection)
             t_index: dict = {}
             t_inc, t_rank, t_pairs = [], [], []
-            for sv, reqs in zip(self._sieves, asks):
+            for inc, reqs in zip(fit_inc, asks):
                 if reqs is None:
                     continue
                 idx = []
                 for (_, lo, hi, _) in reqs:
                     for r in (lo, hi):
-                        if (sv._inc, r) not in t_index:
-                            t_index[(sv._inc, r)] = len(t_inc)
-                            t_inc.append(sv._inc)
+                        if (inc, r) not in t_index:
+                            t_index[(inc, r)] = len(t_inc)
+                            t_inc.append(inc)
                             t_rank.append(r)
-                    idx.append((t_index[(sv._inc, lo)], t_index[(sv._inc, hi)]))
+                    idx.append((t_index[(inc, lo)], t_index[(inc, hi)]))
                 t_pairs.append((np.asarray([a for a, _ in idx], dtype=np.int64),
                                 np.asarray([b for _, b in idx], dtype=np.int64)))
             K_rows, J = int(block.shape[0]), len(t_inc)
@@ -503,7 +522,7 @@ class FruitSlice:
                 # (`block` lives until its selection is done)
                 vals = (pending.result() if pending is not None else np.zeros(0)).reshape(K_rows, J)
                 which = 0
-                for i, (sieve, reqs) in enumerate(zip(self._sieves, asks)):
+                for i, (sieve, reqs) in enumerate(zip(leaves, asks)):
                     if reqs is not None:
                         lo_idx, hi_idx = t_pairs[which]
                         tables[i] = _interpolated_quantiles(sieve, reqs, vals[:, lo_idx], vals[:, hi_idx])
@@ -521,7 +540,8 @@ class FruitSlice:
     # ---- fused ISS + sieves (one launch, no (K, N, T) tensor) --------------------
     def _fusable(self) -> bool:
         from .sieving.increment import MPI, NPI, XPI
-        from .sieving.segment import END, MAX, MIN
+        from .sieving.segment import AVG, CUR, END, MAX, MIN, STD
+        from .sieving.wrapper import INC, INT
         # (a chain of ISS: the LAST one fuses with the sieves, once per row of the chain in front
         # of it - fruits/fruit.py:440-454 feeds every row of an ISS to the next one)
         if os.environ.get("FRUITS_AMD_FUSED", "1") == "0" or not self._iss:
@@ -547,10 +567,17 @@ class FruitSlice:
                 return False     # (every (word, frequency) reads its own transformed input:
                                  # fused word by word, _transform_ffn_fused - single ISS only)
         for sv in self._sieves:
-            # (LPI is not fused: a run crosses lanes, waves and time chunks - DESIGN 4.3)
-            if type(sv) not in (NPI, MPI, XPI, MAX, MIN, END):
+            # a wrapper (INC / INT) takes part as its inner sieve at another differencing order
+            # where that is exact (_reduced, sieving/wrapper.py); else the slice materialises
+            form, inner = _reduced(sv), sv
+            while type(inner) in (INC, INT):
+                inner = inner._sieve
+            if form is None or form[0] is not inner:
                 return False
-            if type(sv) is not END and not -8 <= sv._inc <= 8:
+            # (LPI is not fused: a run crosses lanes, waves and time chunks - DESIGN 4.3)
+            if type(inner) not in (NPI, MPI, XPI, MAX, MIN, END, CUR, AVG, STD):
+                return False
+            if type(inner) is not END and not -8 <= form[2] <= 8:
                 return False     # (cumulated rows: series of one time chunk; the pipeline says if not)
         return True
 
@@ -569,7 +596,6 @@ class FruitSlice:
             return self._fused_cache[key]
         entry = None
         if self._fusable():
-            from .sieving.segment import END
             iss = self._iss[-1]
             iss._check_supported()
             if hasattr(iss, "_arm_plan"):     # CosWISS dropout: the plan carries the mask
@@ -606,7 +632,8 @@ class FruitSlice:
                 if lazy:     # (the thresholds of all rows are arrays already)
                     off = 0
                     for i, sv in enumerate(self._sieves):
-                        if type(sv) is END:
+                        sv, kind, _, _ = _reduced(sv)
+                        if kind == nat.FR_SIEVE_END:
                             continue
                         th = self._sieves_extended.thresholds(i, rows)
                         if th is None:
@@ -618,7 +645,8 @@ class FruitSlice:
                     sieves = self._sieves_extended[row] if self._sieves_extended else self._sieves
                     off = 0
                     for sv in sieves:
-                        if type(sv) is END:
+                        sv, kind, _, _ = _reduced(sv)
+                        if kind == nat.FR_SIEVE_END:
                             continue
                         if not sv.requires_fitting:
                             sv._get_unfitted_quantiles()
@@ -635,7 +663,6 @@ class FruitSlice:
     def _pipeline_specs(acting, T: int):
         """What fr_pipeline_create is told about the sieves ``acting`` for series of length T:
         (specs, cut columns, slots of the per-series cut table)."""
-        from .sieving.segment import END
         # float ("coquantile") cuts differ from series to series: such a sieve names
         # columns of a per-series table instead of indices; sieves with the same cuts
         # share their columns (so NPI / MPI pairs still merge)
@@ -643,17 +670,21 @@ class FruitSlice:
         # fruits/sieving/segment.py:90-91 - so the copies decide the norm here too)
         specs, cut_columns, n_slots = [], {}, 0
         for sv in acting:
-            inc = 0 if type(sv) is END else sv._inc
+            # (a wrapper: its inner sieve at the reduced order - cuts, thresholds and the column
+            # order are the inner sieve's, which are the wrapper's)
+            sv, kind, inc, _ = _reduced(sv)
+            if kind == nat.FR_SIEVE_END:
+                inc = 0
             if sv._has_float_cuts():
                 cuts_key = (tuple(sv._cut), sv._coquantile_norm)
                 if cuts_key not in cut_columns:
                     cut_columns[cuts_key] = (n_slots, sv)
                     n_slots += len(sv._cut) + 1
                 slot0 = cut_columns[cuts_key][0]
-                specs.append((sv._kind | nat.FR_SIEVE_SERIES_CUTS, inc,
+                specs.append((kind | nat.FR_SIEVE_SERIES_CUTS, inc,
                               np.arange(slot0, slot0 + len(sv._cut) + 1), len(sv._q)))
             else:
-                specs.append((sv._kind, inc, sv._int_cut_row(T), len(sv._q)))
+                specs.append((kind, inc, sv._int_cut_row(T), len(sv._q)))
         return specs, cut_columns, n_slots
 
     @staticmethod

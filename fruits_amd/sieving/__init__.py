@@ -1,3 +1,4 @@
 from .abstract import FeatureSieve
 from .segment import *
 from .increment import *
+from .wrapper import *

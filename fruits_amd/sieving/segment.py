@@ -18,12 +18,25 @@ from .. import _native as nat
 from ..cache import CacheType
 from .abstract import FeatureSieve
 
-__all__ = ["MAX", "MIN", "END"]
+__all__ = ["MAX", "MIN", "END", "CUR", "AVG", "STD"]
 
 
 class SegmentSieve(FeatureSieve, ABC):
     _kind = -1   # FR_SIEVE_* code
-    _inc = 0
+    _inc = 0     # differencing order of the rows the kernel looks at
+
+    @property
+    def _fit_inc(self) -> int:
+        """Differencing order of the rows ``fit`` takes its quantiles of - the transform's,
+        except for CUR / AVG / STD (their ``fit`` sees the row itself)."""
+        return self._inc
+
+    def _reduced(self):
+        """(sieve that holds cuts and thresholds, FR_SIEVE_* kind, differencing order of the
+        transform, of the fit): what the fused pipeline and the device-side fit are told about
+        this sieve.  A wrapper (sieving/wrapper.py) answers with its inner sieve at another
+        order, or None when it is no such sieve."""
+        return self, self._kind, self._inc, self._fit_inc
 
     def __init__(self, cut: Union[Sequence[float], float] = -1,
                  q: Optional[Sequence[float]] = None,
@@ -213,6 +226,26 @@ class END(SegmentSieve):
         cuts = super()._get_transformed_cuts(X)
         self._check_cuts(cuts, X.shape[1])
         return cuts
+
+
+class CUR(SegmentSieve):
+    """Curvature: the sum of the squared second-order increments inside each band of every
+    segment, 0 for an empty one (fruits/sieving/segment.py:228-272).  The bands are bands of
+    the second-order increments; ``fit`` takes its quantiles of the row itself, as the
+    reference does."""
+    _kind = nat.FR_SIEVE_CUR
+    _inc = 2
+    _fit_inc = 0
+
+
+class AVG(CUR):
+    """Returns exactly CUR's numbers: the reference's ``_transform`` calls ``CUR._backend``
+    (fruits/sieving/segment.py:309), its band mean is never reached."""
+
+
+class STD(CUR):
+    """Returns exactly CUR's numbers: the reference's ``_transform`` calls ``CUR._backend``
+    (fruits/sieving/segment.py:352), its band standard deviation is never reached."""
 
 
 def self_cut_repr(rows) -> str:

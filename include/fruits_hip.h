@@ -92,6 +92,8 @@ extern "C" {
 #define FR_SIEVE_MIN 4 /* fruits/sieving/segment.py:155-200   */
 #define FR_SIEVE_XPI 5 /* fruits/sieving/increment.py:166-198 */
 #define FR_SIEVE_LPI 6 /* fruits/sieving/increment.py:201-239 */
+#define FR_SIEVE_CUR 7 /* fruits/sieving/segment.py:228-272: sum of v*v over the in-band elements of the
+                          inc-times differenced row (CUR itself: inc = 2); AVG / STD return the same */
 /* OR-ed into a sieve's kind at fr_pipeline_create: its cuts are PER SERIES (coquantile
  * cuts, fruits/sieving/segment.py:51-64) - the sieve's `cuts` entries then name columns
  * ("slots") of the table given to fr_pipeline_set_series_cuts */
@@ -250,7 +252,9 @@ int fr_pathlen_lookup(const double *d_X, int64_t N, int64_t D, int64_t T,
  * (fruits/sieving/increment.py:63-71, 107-129, 138-163, 172-198, 207-239), MAX/MIN._backend
  * (fruits/sieving/segment.py:113-153, 161-200) and END._transform (segment.py:210-219) on a
  * materialised (N, T) iterated sum.  MAX / MIN: 0 for an empty segment AND for an empty band
- * (the reference raises ValueError there); XPI / LPI: 0 for an empty band.
+ * (the reference raises ValueError there); XPI / LPI: 0 for an empty band.  FR_SIEVE_CUR
+ * (CUR._backend, segment.py:242-260, with inc = 2): the sum of squares inside the band, 0 for
+ * an empty one.
  *
  *   d_A      (N, T) f64, row stride a_stride elements
  *   inc      >= 0: number of increment passes fused into the load
@@ -269,7 +273,7 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
  * ISS + sieves in ONE launch: replaces the loop of FruitSlice.transform
  * (fruits/fruit.py:538-550) - for every iterated sum, for every sieve,
  * sieve.transform(itsum) - without ever materialising the (K, N, T) tensor.
- * Sieves: NPI / MPI / XPI with inc -8 to 8, MAX / MIN (inc 0) and END; integer cuts or
+ * Sieves: NPI / MPI / XPI / CUR and MAX / MIN with inc -8 to 8, and END; integer cuts or
  * per-series cuts (FR_SIEVE_SERIES_CUTS).  LPI is not fused (FR_E_LIMIT).  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
  * column order (iterated sum, then sieve, then segment, then band).
  *
@@ -280,7 +284,7 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
  *                      [-T, T-1] fails with FR_E_INDEX (the reference raises IndexError)
  *   h_quant            HOST (K, q_stride) thresholds of every iterated sum (the fitted
  *                      sieve copies of fruit.py:484-496), q_stride =
- *                      fr_pipeline_info(p, 1) = sum of Q1 over the NPI/MPI sieves;
+ *                      fr_pipeline_info(p, 1) = sum of Q1 over the band sieves (all but END);
  *                      fr_pipeline_set_quantiles resolves them with the cuts into a
  *                      device table of per-row feature ops (call once after fit; it
  *                      allocates and synchronises)
