@@ -40,7 +40,10 @@ EXPORTS = [
     "fr_pipeline_set_preparation", "fr_pipeline_set_series_cuts", "fr_pipeline_set_argmax", "fr_arctic_argmax", "fr_coswiss_set_dropout",
     "fr_coswiss_set_input_stride", "fr_coswiss_ffn",
     "fr_prep_fir", "fr_prep_project", "fr_prep_normalize", "fr_prep_leadlag",
+    "fr_prep_mask", "fr_prep_pointwise",
 ]
+FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
+FR_PW_FLAG_SIN = FR_PW_FLAG_LOWER = 1
 
 _lib = None
 _torch = None
@@ -975,4 +978,61 @@ def prep_leadlag(Xd, out=None):
     out = _prep_out(out, (N, 2 * D, 2 * T - 1), Xd)
     check(lib().fr_prep_leadlag(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(out),
                                 stream_ptr()), "fr_prep_leadlag")
+    return out
+
+
+def prep_mask(Xd, mask_d=None, cs_d=None, ce_d=None, out=None):
+    """fr_prep_mask: ``out = keep ? X : +0.0``.  ``mask_d``: ceil(T / 32) 32-bit words (an int32
+    device tensor, bit ``t % 32`` of word ``t // 32`` keeps time step ``t``) shared by all series;
+    ``cs_d`` / ``ce_d``: int64 device tensors of at least N counts, series n keeps the slice
+    ``[cs[n] - 1 : ce[n]]``.  Either source may be absent."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    words = 0
+    if mask_d is not None:
+        if mask_d.dtype != t.int32 or mask_d.dim() != 1 or not mask_d.is_contiguous():
+            raise TypeError("the time mask must be a contiguous int32 device tensor of words")
+        words = int(mask_d.numel())
+    windows = 0
+    if cs_d is not None or ce_d is not None:
+        for c in (cs_d, ce_d):
+            if c is None or c.dtype != t.int64 or c.dim() != 1 or not c.is_contiguous():
+                raise TypeError("window counts must be contiguous int64 (N) device tensors")
+        windows = min(int(cs_d.numel()), int(ce_d.numel()))
+    out = _prep_out(out, (N, D, T), Xd)
+    check(lib().fr_prep_mask(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(mask_d),
+                             C.c_int64(words), dptr(cs_d), dptr(ce_d), C.c_int64(windows),
+                             dptr(out), stream_ptr()), "fr_prep_mask")
+    return out
+
+
+def prep_pointwise(mode: int, Xd, w_d=None, w2_d=None, shift: int = 0, q: float = 0.0,
+                   v: float = 0.0, flags: int = 0, out=None):
+    """fr_prep_pointwise.  FR_PW_MUL / FR_PW_ADD: ``w_d`` (Nw, T), the result has
+    ``max(N, Nw)`` series; FR_PW_ROTATE: ``w_d`` / ``w2_d`` the (T) cosines / sines; FR_PW_POW:
+    ``w_d`` (D) exponents; FR_PW_SHIFT: ``shift``; FR_PW_CLIP: ``q``, ``v``."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    Nw, n_out = 0, N
+    for tab in (w_d, w2_d):
+        if tab is not None and (tab.dtype != t.float64 or not tab.is_contiguous()):
+            raise TypeError("tables must be contiguous float64 device tensors")
+    if mode in (FR_PW_MUL, FR_PW_ADD):
+        if w_d is None or w_d.dim() != 2 or int(w_d.shape[1]) != T:
+            raise ValueError("the table of FR_PW_MUL / FR_PW_ADD must be (Nw, T)")
+        Nw = int(w_d.shape[0])
+        if N and Nw and (N == Nw or N == 1 or Nw == 1):
+            n_out = max(N, Nw)
+    elif mode == FR_PW_ROTATE:
+        if w_d is None or w2_d is None or w_d.numel() != T or w2_d.numel() != T:
+            raise ValueError("a rotation needs (T) cosines and (T) sines")
+    elif mode == FR_PW_POW:
+        if w_d is None or w_d.numel() != D:
+            raise ValueError("one exponent per dimension")
+    out = _prep_out(out, (n_out, D, T), Xd)
+    check(lib().fr_prep_pointwise(C.c_int32(int(mode)), dptr(Xd), C.c_int64(N), C.c_int64(D),
+                                  C.c_int64(T), dptr(w_d), C.c_int64(Nw), dptr(w2_d),
+                                  C.c_int64(int(shift)), C.c_double(float(q)), C.c_double(float(v)),
+                                  C.c_int32(int(flags)), dptr(out), stream_ptr()),
+          "fr_prep_pointwise")
     return out

@@ -31,7 +31,9 @@ def units():
     out = [("kernels_misc", "kernels_misc.hip", []),
            # the preparateurs: no contraction either - NRM and LAG are compared bit for bit, and
            # the sums of RIN / MAV / JLD / FFN round every product like the reference
-           ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
+           ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]),
+           # the time masks and pointwise maps: RPE rounds both products of a rotation
+           ("kernels_filter", "kernels_filter.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
            ("capi", "capi.cpp", []), ("jit", "jit.cpp", []),
            # (the registry also holds the mixed kernels of the one-group programs and their
            # tail programs: no contraction, like the programs' own units below)

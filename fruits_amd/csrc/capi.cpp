@@ -2728,4 +2728,76 @@ int fr_prep_leadlag(const double *d_X, int64_t N, int64_t D, int64_t T, double *
   return FR_OK;
 }
 
+// ---------------------------------------------------------------- streaming preparateurs (kernels_filter.hip)
+int fr_prep_mask(const double *d_X, int64_t N, int64_t D, int64_t T, const uint32_t *d_mask,
+                 int64_t mask_words, const int64_t *d_cs, const int64_t *d_ce, int64_t n_windows,
+                 double *d_out, void *stream) {
+  if (N < 0 || D < 1 || T < 1) return fail(FR_E_ARG, "fr_prep_mask: bad shape");
+  if (d_mask && mask_words != (T + 31) / 32)
+    return fail(FR_E_ARG, "fr_prep_mask: the time mask has to hold ceil(T / 32) words");
+  if ((d_cs == nullptr) != (d_ce == nullptr))
+    return fail(FR_E_ARG, "fr_prep_mask: a window needs both its start and its end counts");
+  if (d_cs && n_windows < N)
+    return fail(FR_E_ARG, "fr_prep_mask: fewer windows than series");
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || d_X == d_out) return fail(FR_E_ARG, "fr_prep_mask: null or aliased device pointer");
+  hipError_t e = fr::launch_prep_mask(d_X, N, D, T, d_mask, d_cs, d_ce, d_out, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(FR_E_LIMIT, "fr_prep_mask: grid too large");
+  }
+  if (e != hipSuccess) return hip_fail(e, "prep mask launch");
+  return FR_OK;
+}
+
+int fr_prep_pointwise(int32_t mode, const double *d_X, int64_t Nx, int64_t D, int64_t T,
+                      const double *d_w, int64_t Nw, const double *d_w2, int64_t shift, double q,
+                      double v, int32_t flags, double *d_out, void *stream) {
+  if (mode < FR_PW_MUL || mode > FR_PW_CLIP) return fail(FR_E_ARG, "fr_prep_pointwise: unknown mode");
+  if (Nx < 0 || D < 1 || T < 1) return fail(FR_E_ARG, "fr_prep_pointwise: bad shape");
+  int64_t N = Nx;
+  fr::PointwiseArgs a{};
+  a.X = d_X;
+  a.out = d_out;
+  a.D = D;
+  a.T = T;
+  a.x_stride = D * T;
+  a.flags = flags;
+  if (mode == FR_PW_MUL || mode == FR_PW_ADD) {
+    if (Nw < 0) return fail(FR_E_ARG, "fr_prep_pointwise: bad shape");
+    if (Nx != Nw && Nx != 1 && Nw != 1)
+      return fail(FR_E_ARG, "fr_prep_pointwise: " + std::to_string(Nx) + " series do not broadcast against " +
+                                std::to_string(Nw) + " table rows");
+    N = (Nx == 0 || Nw == 0) ? 0 : (Nx > Nw ? Nx : Nw);
+    if (N > 0 && !d_w) return fail(FR_E_ARG, "fr_prep_pointwise: null device pointer");
+    a.w = d_w;
+    a.x_stride = Nx == 1 ? 0 : D * T;
+    a.w_stride = Nw == 1 ? 0 : T;
+  } else if (mode == FR_PW_ROTATE) {
+    if (D != 2) return fail(FR_E_ARG, "fr_prep_pointwise: a rotation needs exactly 2 dimensions");
+    if (N > 0 && (!d_w || !d_w2)) return fail(FR_E_ARG, "fr_prep_pointwise: null device pointer");
+    a.w = d_w;
+    a.w2 = d_w2;
+  } else if (mode == FR_PW_POW) {
+    if (N > 0 && !d_w) return fail(FR_E_ARG, "fr_prep_pointwise: null device pointer");
+    a.w = d_w;
+  } else if (mode == FR_PW_SHIFT) {
+    if (shift < 0) return fail(FR_E_ARG, "fr_prep_pointwise: negative shift");
+    a.shift = shift < T ? shift : T;
+  } else {
+    a.q = q;
+    a.v = v;
+  }
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || d_X == d_out)
+    return fail(FR_E_ARG, "fr_prep_pointwise: null or aliased device pointer");
+  hipError_t e = fr::launch_prep_pointwise(mode, a, N, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    return fail(FR_E_LIMIT, "fr_prep_pointwise: grid too large");
+  }
+  if (e != hipSuccess) return hip_fail(e, "prep pointwise launch");
+  return FR_OK;
+}
+
 }  // extern "C"

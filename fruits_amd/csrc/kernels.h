@@ -88,5 +88,22 @@ hipError_t launch_prep_normalize(const double *X, int64_t rows, int64_t len, dou
                                  hipStream_t st);
 hipError_t launch_prep_leadlag(const double *X, int64_t rows, int64_t T, double *out,
                                hipStream_t st);
+// the streaming preparateurs of kernels_filter.hip: time masks (DIL, WIN, DOT, PDD, CTS pseudo)
+// and pointwise maps (SPE, RPE, RDW, CTS, QTC); hipErrorInvalidValue: a grid limit or an
+// unknown mode.  The modes and flags are those of FR_PW_* in fruits_hip.h.
+enum { PW_MUL = 0, PW_ADD = 1, PW_ROTATE = 2, PW_POW = 3, PW_SHIFT = 4, PW_CLIP = 5 };
+enum { PW_FLAG_SIN = 1, PW_FLAG_LOWER = 1 };
+struct PointwiseArgs {
+  const double *X, *w, *w2;
+  double *out;
+  int64_t D, T;
+  int64_t x_stride, w_stride;   // series strides of X and of the SPE table (0: one series)
+  int64_t shift;
+  double q, v;
+  int flags;
+};
+hipError_t launch_prep_mask(const double *X, int64_t N, int64_t D, int64_t T, const uint32_t *mask,
+                            const int64_t *cs, const int64_t *ce, double *out, hipStream_t st);
+hipError_t launch_prep_pointwise(int mode, const PointwiseArgs &a, int64_t N, hipStream_t st);
 
 }  // namespace fr

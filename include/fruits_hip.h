@@ -533,6 +533,46 @@ int fr_prep_normalize(const double *d_X, int64_t N, int64_t D, int64_t T, int32_
 int fr_prep_leadlag(const double *d_X, int64_t N, int64_t D, int64_t T, double *d_out,
                     void *stream);
 
+/* Time masks: out = keep ? X : +0.0 (a select: a dropped NaN / infinity / negative value becomes
+ * +0.0 exactly).  Replaces DIL._transform (fruits/preparation/filter.py:56-62), DOT._transform
+ * (:189-194), PDD._transform (:252-258), the pseudo_shift branch of CTS._transform
+ * (transform.py:940-941) and WIN._transform (filter.py:93-108).  keep is the AND of two sources,
+ * either of which may be absent (both absent: a copy):
+ *   d_mask: bit t % 32 of word t / 32 of `mask_words` = ceil(T / 32) 32-bit words, shared by all
+ *     series (bits at and beyond T are ignored);
+ *   d_cs / d_ce (both or neither): int64 per series, `n_windows` >= N of them; series n keeps
+ *     the Python slice [cs[n] - 1 : ce[n]] of its rows - a start of -1 (cs = 0) is T - 1, an
+ *     empty slice keeps nothing.  Any values are safe: the bounds are clamped to the row.
+ * A lane pair that is dropped entirely is not read.  d_out (N, D, T). */
+int fr_prep_mask(const double *d_X, int64_t N, int64_t D, int64_t T, const uint32_t *d_mask,
+                 int64_t mask_words, const int64_t *d_cs, const int64_t *d_ce, int64_t n_windows,
+                 double *d_out, void *stream);
+
+/* Pointwise maps; `mode` picks one kernel instantiation:
+ *   FR_PW_MUL / FR_PW_ADD - SPE._transform (transform.py:789-812): X * w or X + w with d_w
+ *     (Nw, T).  X has Nx series and w has Nw; the two are equal or one of them is 1 (numpy's
+ *     broadcast of X * wave[:, None, :], else FR_E_ARG) and d_out has max(Nx, Nw) series.
+ *     flags & FR_PW_FLAG_SIN: d_w holds the phase and the kernel takes its sine.
+ *   FR_PW_ROTATE - RPE._backend (transform.py:859-875), D == 2: out0 = c x0 - s x1,
+ *     out1 = s x0 + c x1 with c = d_w (T), s = d_w2 (T); every product is rounded.
+ *   FR_PW_POW - RDW._transform (transform.py:601-602): X ** w[d], d_w (D).
+ *   FR_PW_SHIFT - CTS._transform (transform.py:943-944): out[t] = X[min(t + shift, T - 1)],
+ *     shift >= 0 (at or beyond T: every value is the row's last).
+ *   FR_PW_CLIP - QTC._transform (transform.py:990-1001): X > q ? v : X, with
+ *     flags & FR_PW_FLAG_LOWER X < q ? v : X; NaN passes through.
+ * Arguments a mode does not name are ignored.  d_out (max(Nx, Nw), D, T). */
+#define FR_PW_MUL 0
+#define FR_PW_ADD 1
+#define FR_PW_ROTATE 2
+#define FR_PW_POW 3
+#define FR_PW_SHIFT 4
+#define FR_PW_CLIP 5
+#define FR_PW_FLAG_SIN 1
+#define FR_PW_FLAG_LOWER 1
+int fr_prep_pointwise(int32_t mode, const double *d_X, int64_t Nx, int64_t D, int64_t T,
+                      const double *d_w, int64_t Nw, const double *d_w2, int64_t shift, double q,
+                      double v, int32_t flags, double *d_out, void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest

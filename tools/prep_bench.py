@@ -1,11 +1,14 @@
-"""`python tools/prep_bench.py [reps] [launches]`: the four preparateur entries (fr_prep_fir,
-fr_prep_project, fr_prep_normalize, fr_prep_leadlag) at (2048, 3, 1024) and (8192, 6, 4096),
+"""`python tools/prep_bench.py [reps] [launches]`: the six preparateur entries (fr_prep_fir,
+fr_prep_project, fr_prep_normalize, fr_prep_leadlag, fr_prep_mask, fr_prep_pointwise) at
+(2048, 3, 1024) and (8192, 6, 4096) - RPE on the first two dimensions -
 HIP-event timed, next to a `torch.Tensor.copy_` that reads + writes the same number of bytes in
 the same process (the yardstick of docs/history.md 4.1c).  Every candidate runs the ENTRY on
 device tables and an output allocated beforehand, `launches` (default 10) back to back between
 one event pair, so the host side of a call hides behind the launch in front of it; the candidates
 of a shape are interleaved over `reps` rounds (default 15) and the median per launch is printed
-as one markdown table row: entry, shape, us, MB read + written, us of the copy, ratio."""
+as one markdown table row: entry, shape, us, MB read + written, us of the copy, ratio.  MB is the
+compulsory traffic: every output element written, every input element read once - of a masked
+input only the kept elements (the row names the kept share), of a table its own bytes."""
 import statistics
 import sys
 
@@ -14,6 +17,7 @@ import numpy as np
 import fruits_amd  # noqa: F401
 from fruits_amd import _native as nat
 from fruits_amd import preparation as P
+from fruits_amd.cache import CacheType, SharedSeedCache
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 launches = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -25,6 +29,11 @@ def fitted(p, shape, seed=1):
     np.random.seed(seed)
     p.fit(np.broadcast_to(0.0, shape))
     return p
+
+
+def derived(p, Xd):
+    """The device tables the warm-up transform of ``p`` left behind (_derived_tables)."""
+    return p._programs[("derived", str(Xd.device))][1]
 
 
 def entry_call(p, Xd):
@@ -48,7 +57,58 @@ def entry_call(p, Xd):
         return lambda: nat.prep_ffn(Xd, W1, b, W2, p._center, p._relu_out, out=out), out
     if kind == "NRM":
         return lambda: nat.prep_normalize(Xd, p._scale_dim, out=out), out
-    return lambda: nat.prep_leadlag(Xd, out=out), out
+    if kind == "LAG":
+        return lambda: nat.prep_leadlag(Xd, out=out), out
+    T = int(Xd.shape[2])
+    if kind in ("DOT", "PDD", "DIL"):
+        md, = derived(p, Xd)
+        return lambda: nat.prep_mask(Xd, md, out=out), out
+    if kind == "WIN":
+        cs = p._cache.get_device(CacheType.COQUANTILE, f"{p._start}:L2")
+        ce = p._cache.get_device(CacheType.COQUANTILE, f"{p._end}:L2")
+        return lambda: nat.prep_mask(Xd, None, cs, ce, out=out), out
+    if kind == "SPE" and p._step_transform is None:
+        wd, = derived(p, Xd)
+        return lambda: nat.prep_pointwise(nat.FR_PW_MUL, Xd, wd, out=out), out
+    if kind == "SPE":
+        path = p._cache.get_device(CacheType.ISS, p._step_transform)
+        phase = (path / path[:, -1:] ** p._freq).contiguous()
+        return lambda: nat.prep_pointwise(nat.FR_PW_MUL, Xd, phase, flags=nat.FR_PW_FLAG_SIN,
+                                          out=out), out
+    if kind == "RPE":
+        cd, sd = derived(p, Xd)
+        return lambda: nat.prep_pointwise(nat.FR_PW_ROTATE, Xd, cd, sd, out=out), out
+    if kind == "RDW":
+        wd, = p._device_tables(Xd, p._weights)
+        return lambda: nat.prep_pointwise(nat.FR_PW_POW, Xd, wd, out=out), out
+    if kind == "CTS":
+        return lambda: nat.prep_pointwise(nat.FR_PW_SHIFT, Xd, shift=p._steps(T), out=out), out
+    q = float(p._quantile)
+    return lambda: nat.prep_pointwise(nat.FR_PW_CLIP, Xd, q=q, v=q, out=out), out
+
+
+def kept_share(p, out, Xd):
+    """The share of the input a mask keeps (what fr_prep_mask has to read), else 1."""
+    kind = type(p).__name__
+    if kind in ("DOT", "PDD", "DIL", "WIN"):
+        return float((out != 0).double().mean())       # (a standard-normal input has no zeros)
+    return 1.0
+
+
+def streaming(shape, Xd):
+    """(name, preparateur, input) of the fr_prep_mask / fr_prep_pointwise candidates."""
+    cache = SharedSeedCache()
+    cache.adopt_device_input(Xd)
+    win, spe = P.WIN(0.25, 0.75), P.SPE(0.5, step_transform="L1")
+    win._cache = spe._cache = cache
+    qtc = P.QTC(0.7)
+    qtc._quantile = 0.5
+    X2 = Xd[:, :2, :].contiguous()
+    return [("mask DOT n=2", fitted(P.DOT(2), shape), Xd),
+            ("mask PDD 0.8/0.5", fitted(P.PDD(0.8, 0.5), shape), Xd),
+            ("mask WIN 0.25-0.75", win, Xd), ("SPE table", P.SPE(0.5), Xd), ("SPE L1 device sin", spe, Xd),
+            ("RPE (2 dims)", P.RPE(0.5), X2), ("RDW pow", fitted(P.RDW("uniform"), shape), Xd.abs()),
+            ("CTS s=3", P.CTS(3), Xd), ("QTC", qtc, Xd)]
 
 
 def timed(fn):
@@ -71,10 +131,16 @@ for shape in ((2048, 3, 1024), (8192, 6, 4096)):
     cands += [(f"MAV w={w}", fitted(P.MAV(w), shape)) for w in (5, 102)]
     cands += [(f"JLD {D}->{half}", fitted(P.JLD(half), shape)), ("FFN default", fitted(P.FFN(), shape)),
               ("NRM", P.NRM()), ("LAG", P.LAG())]
+    cands = [(name, p, Xd) for name, p in cands] + streaming(shape, Xd)
     jobs = []
-    for name, p in cands:
-        fn, out = entry_call(p, Xd)
-        moved = Xd.numel() * 8 + out.numel() * 8
+    for name, p, Xin in cands:
+        fn, out = entry_call(p, Xin)
+        share = kept_share(p, out, Xin)
+        if share < 1.0:
+            name += f" (keeps {share:.2f})"
+        moved = int(Xin.numel() * 8 * share) + out.numel() * 8
+        if type(p).__name__ in ("SPE", "RPE"):       # the wave (per series with a step transform)
+            moved += (Xin.shape[0] if p.__dict__.get("_step_transform") else 2) * Xin.shape[2] * 8
         src = t.empty(moved // 16, dtype=t.float64, device="cuda").normal_()
         dst = t.empty_like(src)
         jobs.append((name, fn, (lambda d=dst, s_=src: d.copy_(s_)), moved, out, [], []))
