@@ -23,7 +23,11 @@ HEADERS = ["kernels.h", "plan.h", "jit.h", "walk.h", "walk_device.h", "walk_fuse
 
 
 # headers that only some units include: {header: unit names}
-LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep")}
+CAPI = ("capi_core", "capi_plan", "capi_walk", "capi_pipeline", "capi_select", "capi_kernels")
+LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep"),
+                 "capi_common.h": CAPI,
+                 "capi_plan.h": ("capi_plan", "capi_walk", "capi_pipeline"),
+                 "capi_pipeline.h": ("capi_walk", "capi_pipeline")}
 
 
 def units():
@@ -34,10 +38,11 @@ def units():
            ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]),
            # the time masks and pointwise maps: RPE rounds both products of a rotation
            ("kernels_filter", "kernels_filter.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
-           ("capi", "capi.cpp", []), ("jit", "jit.cpp", []),
+           ("jit", "jit.cpp", []),
            # (the registry also holds the mixed kernels of the one-group programs and their
            # tail programs: no contraction, like the programs' own units below)
            ("walk_static_reg", "walk_static_inst.hip", ["-DSTATIC_REGISTRY", "-ffp-contract=off"])]
+    out += [(u, u + ".cpp", []) for u in CAPI]   # the C ABI, one unit per concern
     # The walks: no a*b+c contraction - the reference rounds a letter's product before the
     # cumulative sum adds it (fruits/iss/semiring.py:143-149) - in EVERY unit, so that the record
     # interpreter (mode 0), the lean materialising walk (mode 2), the fused walk (mode 1), the

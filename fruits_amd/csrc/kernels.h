@@ -1,4 +1,4 @@
-// Internal interface between the C ABI (capi.cpp) and the HIP kernels.
+// Internal interface between the C ABI (capi_*.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 

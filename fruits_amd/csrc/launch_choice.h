@@ -1,7 +1,7 @@
 // How a trie walk is launched: choose_walk_launch, ONE pure function from facts (the plan, the
-// shape, what the device and the registry report) and knobs (the environment, read by capi.cpp
+// shape, what the device and the registry report) and knobs (the environment, read by capi_core.cpp
 // once per call) to a choice.  Host-only and free of HIP, so that a CPU test pins the choice
-// (tests/native/launch_choice_host.cpp); capi.cpp gathers the facts and carries the choice out.
+// (tests/native/launch_choice_host.cpp); capi_walk.cpp gathers the facts and carries the choice out.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -23,7 +23,7 @@ inline bool packed_supported(int64_t T, int levels, int semiring) {
   return (T <= 256 && levels <= 8) || (T <= 384 && levels <= 4);
 }
 
-// The developer knobs of FRUITS_HIP_DEBUG (capi.cpp, debug_knob) and the environment switches a
+// The developer knobs of FRUITS_HIP_DEBUG (capi_core.cpp, debug_knob) and the environment switches a
 // launch reads; the defaults are what an empty environment gives.
 constexpr int kKnobUnset = INT_MIN;
 struct WalkKnobs {
@@ -246,7 +246,7 @@ inline WalkChoice choose_walk_launch(const Plan &p, const WalkFacts &f, const Wa
   // of the standard word sets': materialising, one aligned 1024-element chunk, unweighted
   // Reals, the group count its schedule was generated for.  It reads no device tables, so
   // nothing is uploaded for it (and a run of it is capturable without fr_plan_prepare).
-  // No ahead-of-time program: one compiled at run time (capi.cpp, ensure_jit) where this device
+  // No ahead-of-time program: one compiled at run time (capi_plan.cpp, ensure_jit) where this device
   // has it loaded.
   const bool static_ok = static_launch_possible(p, f, k);
   const bool aot = f.aot[1] > 0;

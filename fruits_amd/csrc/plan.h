@@ -142,7 +142,7 @@ struct Plan {
   // -1: not looked up yet)
   int static_prog[4] = {-1, -1, -1, -1};
   int64_t last_tail_series = 0;   // FR_INFO_STATIC_TAIL: the most recent materialising launch (under mu)
-  void *jit = nullptr;   // run-time compiled static programs (capi.cpp: JitState), or nullptr
+  void *jit = nullptr;   // run-time compiled static programs (capi_plan.h: JitState), or nullptr
   int device = -1;     // HIP device the uploaded tables live on (-1: nothing uploaded yet)
   std::mutex mu;       // guards `programs`, `cos->d_blob` and `device` (uploads at run time)
 

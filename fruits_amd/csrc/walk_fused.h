@@ -37,7 +37,7 @@
 
 namespace fr {
 
-// feature-op flags (FeatOp::kind_inc), resolved by the host (capi.cpp, fr_pipeline_set_quantiles)
+// feature-op flags (FeatOp::kind_inc), resolved by the host (capi_pipeline.cpp, fr_pipeline_set_quantiles)
 constexpr int32_t OPF_SERIES_CUTS = 1 << 16;
 // bits 20-22: the op's SHAPE when it is one of the common ones (0: none of them)
 constexpr int OPF_SHAPE_SHIFT = 20;

@@ -1,7 +1,7 @@
 // Walk kernels whose program is a compile-time constant (walk.h, walk_static).  One
 // translation unit per pre-generated program (STATIC_PROG = its index in
 // static_programs.h, fruits_amd/gen_static.py), plus the registry (STATIC_REGISTRY) that
-// capi.cpp asks whether the plan it is about to run is one of them.
+// capi_plan.cpp asks whether the plan it is about to run is one of them.
 #include "walk.h"
 
 #include <cstring>
@@ -85,7 +85,7 @@ hipError_t walk_static_launch(const IssArgs &a, hipStream_t st) {
 #else
 // Two instances per program: plain output stores, and the cache policy that the program's group
 // count was measured to gain from in the window where the host asks for it (IssArgs::wt,
-// capi.cpp run_walk): one group (cache-sized batches, non-temporal input) writes through the L2
+// capi_walk.cpp run_walk): one group (cache-sized batches, non-temporal input) writes through the L2
 // (sc1); three groups (batches that stream through HBM, plain input loads shared by the sibling
 // groups) write through and non-temporal (nt sc1).  Two-group programs keep plain stores only.
 template <int G>

@@ -100,10 +100,11 @@ def bundle_slice(entry) -> tuple:
 
 def manifest_key() -> str:
     """What the bundle depends on: the device sources the kernels are generated from, this file,
-    the plan compiler and the JIT's source generator."""
+    the plan compiler, the JIT's source generator and the pipeline's op table and compilers."""
     h = hashlib.sha256()
     for f in ("csrc/walk_types.h", "csrc/walk_scan.h", "csrc/walk_device.h", "csrc/walk_fused.h",
-              "csrc/jit.cpp", "csrc/plan.cpp", "csrc/capi.cpp", "gen_bundle.py"):
+              "csrc/jit.cpp", "csrc/plan.cpp", "csrc/capi_pipeline.cpp", "csrc/capi_pipeline.h",
+              "gen_bundle.py"):
         with open(os.path.join(HERE, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()
@@ -132,7 +133,7 @@ def build_bundle(force: bool = False, jobs: int = 0, verbose: bool = True) -> st
     import fruits_amd as fr
     entries = manifest(fr)
     # the entries with the most to compile first (nodes x sieves); every entry compiles its
-    # kernels on threads of its own (csrc/capi.cpp, fr_pipeline_bundle) - together a little more
+    # kernels on threads of its own (csrc/capi_pipeline.cpp, fr_pipeline_bundle) - together a little more
     # than the cores, the compiler's longest single job (~2 min here) is what bounds the build
     entries.sort(key=lambda e: -len(e[2].words) * len(e[3]))
     cores = os.cpu_count() or 2

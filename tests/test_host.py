@@ -209,6 +209,181 @@ def test_plan_rejects_bad_input():
     assert deep.info(nat.FR_INFO_LEVELS) <= 8 and deep.rows == 32
 
 
+def test_entry_refusals_say_what_they_said():
+    """Every argument check of the thin entries (and of fr_select_ranks) runs before any HIP call:
+    each case below trips exactly one of them - or the early return of an empty batch - and pins
+    the return code and the exact text of fr_last_error()."""
+    L = nat.lib()
+    i32, i64, f64 = C.c_int32, C.c_int64, C.c_double
+    p, q, null = C.c_void_p(0x1000), C.c_void_p(0x2000), None   # device pointers: never dereferenced
+    OK, ARG, DIM, LIMIT = 0, nat.FR_E_ARG, nat.FR_E_DIM, nat.FR_E_LIMIT
+
+    def ints(*v):
+        return (i32 * len(v))(*v)
+
+    def longs(*v):
+        return (i64 * len(v))(*v)
+
+    def fir(N=2, D=3, T=8, kern=p, J=2, w=2, d_ndim=p, O=2, d_dims=p, h_ndim=ints(1, 1),
+            h_dims=ints(0, 2), mode=0, adaptive=0, X=p, out=q):
+        return L.fr_prep_fir(X, i64(N), i64(D), i64(T), kern, i32(J), i32(w), d_ndim, i32(O), d_dims,
+                             h_ndim, h_dims, i32(mode), i32(adaptive), out, null)
+
+    def project(N=2, D=3, T=8, kern=p, bias=p, d_ndim=p, O=2, d_dims=p, J=2, h_ndim=ints(1, 1),
+                h_dims=ints(0, 2), W1=p, b1=p, W2=p, hidden=0, X=p, out=q):
+        return L.fr_prep_project(X, i64(N), i64(D), i64(T), kern, bias, d_ndim, i32(O), d_dims, i32(J),
+                                 h_ndim, h_dims, W1, b1, W2, i32(hidden), i32(0), out, null)
+
+    def mask(N=2, D=1, T=40, m=null, words=0, cs=null, ce=null, n_windows=0, X=p, out=q):
+        return L.fr_prep_mask(X, i64(N), i64(D), i64(T), m, i64(words), cs, ce, i64(n_windows), out, null)
+
+    def pointwise(mode, Nx=3, D=2, T=8, w=p, Nw=3, w2=p, shift=0, X=p, out=q):
+        return L.fr_prep_pointwise(i32(mode), X, i64(Nx), i64(D), i64(T), w, i64(Nw), w2, i64(shift),
+                                   f64(0.5), f64(0.0), i32(0), out, null)
+
+    def sieve(kind=nat.FR_SIEVE_NPI, N=3, T=8, inc=0, cuts=p, cut_rows=1, C1=2, dq=p, Q1=2, A=p, out=q):
+        return L.fr_sieve(i32(kind), A, i64(N), i64(T), i64(T), i32(inc), cuts, i64(cut_rows), i32(C1),
+                          dq, i32(Q1), out, i64(1), null)
+
+    def select(rows=2, N=3, T=8, n_jobs=1, row=ints(0), inc=ints(0), rank=longs(0), A=p,
+               out=(f64 * 1)()):
+        return L.fr_select_ranks(A, i64(rows), i64(N), i64(T), i32(n_jobs), row, inc, rank, out, null)
+
+    def combine(n_terms=4, N=2, T=8, n_out=2, stride=16, terms=p):
+        return L.fr_coswiss_combine(terms, i64(n_terms), i64(N), i64(T), i32(n_out), p, p, p, p, q,
+                                    i64(stride), null)
+
+    cases = [
+        (lambda: L.fr_increments(p, i64(-1), i64(8), i64(1), q, null, i64(0), null), ARG, "fr_increments: bad shape"),
+        (lambda: L.fr_increments(p, i64(2), i64(8), i64(-1), q, null, i64(0), null), ARG, "fr_increments: bad shape"),
+        (lambda: L.fr_increments(p, i64(0), i64(8), i64(1), q, null, i64(0), null), OK, None),
+        (lambda: L.fr_increments(null, i64(2), i64(8), i64(1), q, null, i64(0), null), ARG,
+         "fr_increments: null device pointer"),
+        (lambda: L.fr_pathlen_lookup(p, i64(2), i64(1), i64(8), i32(3), i32(0), f64(1.0), q, null), ARG,
+         "fr_pathlen_lookup: bad argument"),
+        (lambda: L.fr_pathlen_lookup(p, i64(2), i64(0), i64(8), i32(2), i32(0), f64(1.0), q, null), ARG,
+         "fr_pathlen_lookup: bad argument"),
+        (lambda: L.fr_pathlen_lookup(p, i64(0), i64(1), i64(8), i32(1), i32(0), f64(1.0), q, null), OK, None),
+        (lambda: L.fr_pathlen_lookup(p, i64(2), i64(1), i64(8), i32(1), i32(0), f64(1.0), null, null), ARG,
+         "fr_pathlen_lookup: null device pointer"),
+        (lambda: sieve(kind=nat.FR_SIEVE_CUR + 1), ARG, "fr_sieve: unknown kind"),
+        (lambda: sieve(kind=-1), ARG, "fr_sieve: unknown kind"),
+        (lambda: sieve(C1=1), ARG, "fr_sieve: bad shape"),
+        (lambda: sieve(T=0), ARG, "fr_sieve: bad shape"),
+        (lambda: sieve(cut_rows=2), ARG, "fr_sieve: bad shape"),
+        (lambda: sieve(Q1=1), ARG, "fr_sieve: bad quantiles"),
+        (lambda: sieve(dq=null), ARG, "fr_sieve: bad quantiles"),
+        (lambda: sieve(inc=9), LIMIT, "fr_sieve: inc must be in [0, 8]"),
+        (lambda: sieve(inc=-1), LIMIT, "fr_sieve: inc must be in [0, 8]"),
+        (lambda: sieve(N=0, cut_rows=0), OK, None),
+        (lambda: sieve(kind=nat.FR_SIEVE_END, dq=null, Q1=0, N=0), OK, None),
+        (lambda: sieve(cuts=null), ARG, "fr_sieve: null device pointer"),
+        (lambda: L.fr_pre_transform(p, i64(2), i64(8), i64(8), i32(9), q, null), ARG, "fr_pre_transform: bad argument"),
+        (lambda: L.fr_pre_transform(p, i64(2), i64(0), i64(8), i32(1), q, null), OK, None),
+        (lambda: L.fr_pre_transform(p, i64(2), i64(8), i64(8), i32(1), null, null), ARG,
+         "fr_pre_transform: null device pointer"),
+        (lambda: L.fr_standardize(p, i64(2), i64(-1), i32(1), f64(0.0), q, null), ARG, "fr_standardize: bad shape"),
+        (lambda: L.fr_standardize(p, i64(0), i64(8), i32(1), f64(0.0), q, null), OK, None),
+        (lambda: L.fr_standardize(null, i64(2), i64(8), i32(1), f64(0.0), q, null), ARG,
+         "fr_standardize: null device pointer"),
+        (lambda: L.fr_nan_to_num(p, i64(-1), null), ARG, "fr_nan_to_num: bad count"),
+        (lambda: L.fr_nan_to_num(p, i64(0), null), OK, None),
+        (lambda: L.fr_nan_to_num(null, i64(4), null), ARG, "fr_nan_to_num: null device pointer"),
+        (lambda: L.fr_arctic_argmax(p, i64(2), i64(2), i64(8), i32(-1), p, p, q, null), ARG,
+         "fr_arctic_argmax: bad shape"),
+        (lambda: L.fr_arctic_argmax(p, i64(2), i64(0), i64(8), i32(1), p, p, q, null), OK, None),
+        (lambda: L.fr_arctic_argmax(p, i64(2), i64(2), i64(8), i32(1), null, p, q, null), ARG,
+         "fr_arctic_argmax: null device pointer"),
+        (lambda: combine(n_terms=-1), ARG, "fr_coswiss_combine: bad shape"),
+        (lambda: combine(N=0), OK, None),
+        (lambda: combine(n_out=0), OK, None),
+        (lambda: combine(N=1 << 30, n_out=2, stride=1 << 40), LIMIT, "fr_coswiss_combine: grid too large"),
+        (lambda: combine(stride=15), ARG, "fr_coswiss_combine: rows of d_out overlap"),
+        (lambda: combine(terms=null), ARG, "fr_coswiss_combine: null device pointer"),
+        (lambda: L.fr_coswiss_ffn(p, i64(2), i64(1), i64(8), p, p, p, i32(0), q, null), ARG, "fr_coswiss_ffn: bad shape"),
+        (lambda: L.fr_coswiss_ffn(p, i64(2), i64(1), i64(0), p, p, p, i32(4), q, null), OK, None),
+        (lambda: L.fr_coswiss_ffn(p, i64(2), i64(1), i64(8), p, null, p, i32(4), q, null), ARG,
+         "fr_coswiss_ffn: null device pointer"),
+        # (fr_select_ranks returns the code its _begin half left for the calling thread)
+        (lambda: select(n_jobs=0, rows=0), OK, None),
+        (lambda: select(out=null), ARG, "fr_select_ranks: bad argument"),
+        (lambda: select(N=0), ARG, "fr_select_ranks: bad argument"),
+        (lambda: select(rank=null), ARG, "fr_select_ranks: bad argument"),
+        (lambda: select(A=null), ARG, "fr_select_ranks: null device pointer"),
+        (lambda: select(N=1, T=1 << 31), LIMIT,
+         "fr_select_ranks: series of 2^31 elements or more (time indices are 32-bit)"),
+        (lambda: select(n_jobs=2, row=ints(0, 2), inc=ints(0, 0), rank=longs(0, 0), out=(f64 * 2)()), ARG,
+         "fr_select_ranks: job 1 out of range"),
+        (lambda: select(inc=ints(9)), ARG, "fr_select_ranks: job 0 out of range"),
+        (lambda: select(rank=longs(24)), ARG, "fr_select_ranks: job 0 out of range"),
+        # FIR (mode 0) and the moving average (mode 1)
+        (lambda: fir(mode=2), ARG, "fr_prep_fir: bad shape"),
+        (lambda: fir(T=0), ARG, "fr_prep_fir: bad shape"),
+        (lambda: fir(mode=1, w=0), ARG, "fr_prep_fir: a moving average wider than the series"),
+        (lambda: fir(mode=1, w=9), ARG, "fr_prep_fir: a moving average wider than the series"),
+        (lambda: fir(mode=1, w=8, N=0, h_ndim=null, h_dims=null), OK, None),
+        (lambda: fir(mode=1, w=8, out=p), ARG, "fr_prep_fir: null or aliased device pointer"),
+        (lambda: fir(J=0), ARG, "fr_prep_fir: 1 <= slots <= D (slot j adds dimension j itself)"),
+        (lambda: fir(J=4), ARG, "fr_prep_fir: 1 <= slots <= D (slot j adds dimension j itself)"),
+        (lambda: fir(w=8), ARG, "fr_prep_fir: the kernel must be shorter than the series"),
+        (lambda: fir(h_ndim=null), ARG, "fr_prep_fir: null host table"),
+        (lambda: fir(h_ndim=ints(3, -1)), ARG, "fr_prep_fir: negative group size"),
+        (lambda: fir(h_ndim=ints(1, 2)), ARG, "fr_prep_fir: the group sizes do not add up to the number of slots"),
+        (lambda: fir(h_dims=ints(0, 3)), DIM, "fr_prep_fir: slot 1 names dimension 3 of 3"),
+        (lambda: fir(h_dims=ints(-1, 0)), DIM, "fr_prep_fir: slot 0 names dimension -1 of 3"),
+        (lambda: fir(kern=null), ARG, "fr_prep_fir: null device pointer"),
+        (lambda: fir(w=8, adaptive=1, N=0), OK, None),
+        (lambda: fir(X=null), ARG, "fr_prep_fir: null or aliased device pointer"),
+        # the grouped projection (hidden == 0) and the hidden layer
+        (lambda: project(O=0), ARG, "fr_prep_project: bad shape"),
+        (lambda: project(J=-1), ARG, "fr_prep_project: bad shape"),
+        (lambda: project(h_dims=null), ARG, "fr_prep_project: null host table"),
+        (lambda: project(h_ndim=ints(1, 0)), ARG,
+         "fr_prep_project: the group sizes do not add up to the number of slots"),
+        (lambda: project(bias=null), ARG, "fr_prep_project: null device pointer"),
+        (lambda: project(N=0), OK, None),
+        (lambda: project(hidden=4, D=17), LIMIT,
+         "fr_prep_project: a hidden layer between at most 16 input and 16 output dimensions"),
+        (lambda: project(hidden=4, W2=null), ARG, "fr_prep_project: null device pointer"),
+        (lambda: project(hidden=4, N=0, h_ndim=null, h_dims=null), OK, None),
+        (lambda: project(hidden=4, out=p), ARG, "fr_prep_project: null or aliased device pointer"),
+        (lambda: L.fr_prep_normalize(p, i64(2), i64(0), i64(8), i32(0), q, null), ARG, "fr_prep_normalize: bad shape"),
+        (lambda: L.fr_prep_normalize(p, i64(0), i64(1), i64(8), i32(1), q, null), OK, None),
+        (lambda: L.fr_prep_normalize(p, i64(2), i64(1), i64(8), i32(0), p, null), ARG,
+         "fr_prep_normalize: null or aliased device pointer"),
+        (lambda: L.fr_prep_leadlag(p, i64(-1), i64(1), i64(8), q, null), ARG, "fr_prep_leadlag: bad shape"),
+        (lambda: L.fr_prep_leadlag(p, i64(0), i64(1), i64(8), q, null), OK, None),
+        (lambda: L.fr_prep_leadlag(p, i64(2), i64(1), i64(8), null, null), ARG,
+         "fr_prep_leadlag: null or aliased device pointer"),
+        (lambda: mask(T=0), ARG, "fr_prep_mask: bad shape"),
+        (lambda: mask(m=p, words=1), ARG, "fr_prep_mask: the time mask has to hold ceil(T / 32) words"),
+        (lambda: mask(cs=p), ARG, "fr_prep_mask: a window needs both its start and its end counts"),
+        (lambda: mask(ce=p), ARG, "fr_prep_mask: a window needs both its start and its end counts"),
+        (lambda: mask(cs=p, ce=p, n_windows=1), ARG, "fr_prep_mask: fewer windows than series"),
+        (lambda: mask(N=0, m=p, words=2, cs=p, ce=p), OK, None),
+        (lambda: mask(m=p, words=2, out=p), ARG, "fr_prep_mask: null or aliased device pointer"),
+        (lambda: pointwise(nat.FR_PW_CLIP + 1), ARG, "fr_prep_pointwise: unknown mode"),
+        (lambda: pointwise(-1), ARG, "fr_prep_pointwise: unknown mode"),
+        (lambda: pointwise(nat.FR_PW_CLIP, T=0), ARG, "fr_prep_pointwise: bad shape"),
+        (lambda: pointwise(nat.FR_PW_ADD, Nw=-1), ARG, "fr_prep_pointwise: bad shape"),
+        (lambda: pointwise(nat.FR_PW_MUL, Nx=3, Nw=2), ARG,
+         "fr_prep_pointwise: 3 series do not broadcast against 2 table rows"),
+        (lambda: pointwise(nat.FR_PW_MUL, Nx=1, Nw=4, w=null), ARG, "fr_prep_pointwise: null device pointer"),
+        (lambda: pointwise(nat.FR_PW_MUL, Nx=1, Nw=0), OK, None),
+        (lambda: pointwise(nat.FR_PW_ROTATE, D=3), ARG, "fr_prep_pointwise: a rotation needs exactly 2 dimensions"),
+        (lambda: pointwise(nat.FR_PW_ROTATE, w2=null), ARG, "fr_prep_pointwise: null device pointer"),
+        (lambda: pointwise(nat.FR_PW_POW, w=null), ARG, "fr_prep_pointwise: null device pointer"),
+        (lambda: pointwise(nat.FR_PW_SHIFT, shift=-1), ARG, "fr_prep_pointwise: negative shift"),
+        (lambda: pointwise(nat.FR_PW_SHIFT, Nx=0, shift=99), OK, None),
+        (lambda: pointwise(nat.FR_PW_CLIP, out=p), ARG, "fr_prep_pointwise: null or aliased device pointer"),
+    ]
+    for i, (call, code, text) in enumerate(cases):
+        rc = call()
+        assert rc == code, (i, rc, nat.last_error())
+        if text is not None:
+            assert nat.last_error() == text, (i, nat.last_error())
+
+
 # ---------------------------------------------------------------- stages (no compute)
 def test_iss_bookkeeping():
     words = fr.words.of_weight(2, dim=3)
