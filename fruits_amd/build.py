@@ -32,7 +32,8 @@ LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep"),
 
 def units():
     """(object name, source, extra flags)"""
-    out = [("kernels_misc", "kernels_misc.hip", []),
+    out = [("kernels_misc", "kernels_misc.hip", []), ("kernels_sieve", "kernels_sieve.hip", []),
+           ("kernels_select", "kernels_select.hip", []), ("walk_dispatch", "walk_dispatch.cpp", []),
            # the preparateurs: no contraction either - NRM and LAG are compared bit for bit, and
            # the sums of RIN / MAV / JLD / FFN round every product like the reference
            ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]),

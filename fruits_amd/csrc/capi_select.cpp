@@ -250,10 +250,7 @@ int fr_select_ranks_end(fr_selection_t *sel, double *h_out) {
       double v = sel->h_out_dev[sel->dev_of[s]];
       if (sel->via_succ[s]) {
         const unsigned long long k = sel->h_succ[sel->dev_of[s]];
-        if (k != ~0ull) {   // the order-preserving key back to the double (kernels_misc.hip)
-          const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-          std::memcpy(&v, &u, 8);
-        }
+        if (k != ~0ull) v = fr::order_key_value(k);
       }
       h_out[sel->order[s]] = v;
     }

@@ -10,6 +10,14 @@
 
 namespace fr {
 
+// deepest differencing order of a sieve (IncrementSieve): the sieves and the selection unroll to it
+constexpr int kMaxInc = 8;
+// blocks of 256 threads of a grid-stride launch over `total` elements, at most `cap`
+inline unsigned grid_blocks(int64_t total, int64_t cap) {
+  const int64_t blocks = (total + 255) / 256;
+  return (unsigned)(blocks > cap ? cap : blocks);
+}
+
 int static_program_for(const NodeRec *recs, int n, int groups, const int32_t *row_src, int rows);
 int static_program_tail_groups(int prog);
 hipError_t launch_iss_walk(IssArgs &a, int levels, hipStream_t st);
@@ -37,7 +45,7 @@ constexpr int kSelGroupMax = 8;
 constexpr int kSelTrackJobs = 2;     // jobs per group and differencing order whose successor the gather pass tracks
 // (fruit_reduced's fit: 2048 23.0 ms - a few jobs per slice went on through five more digits -
 // 4096 20.1, 8192 20.3, 16384 20.3)
-constexpr int kSelSmallCap = 4096;   // candidates a job settles inside one workgroup (kernels_misc.hip)
+constexpr int kSelSmallCap = 4096;   // candidates a job settles inside one workgroup (kernels_select.hip)
 // job.pad bit 0: also return the next order statistic (succ[job] = its order key; all-ones
 // when there is none); succ must be preset to all-ones
 hipError_t launch_select_ranks(void *jobs, int n_jobs, const void *groups, int n_groups,
@@ -61,7 +69,7 @@ hipError_t launch_coswiss_combine(const double *A, int64_t N, int64_t T, int n_o
 hipError_t launch_nan_to_num(double *x, int64_t count, hipStream_t st);
 hipError_t launch_standardize(const double *X, int64_t rows, int64_t T, int div_std, double eps,
                               double *out, hipStream_t st);
-// Arctic argmax rows -> features (kernels_misc.hip, argmax_sieve_kernel): `words` = device
+// Arctic argmax rows -> features (kernels_sieve.hip, argmax_sieve_kernel): `words` = device
 // (n_words, 4) int32 {first V row, letters, first output row, 0}; the dynamic LDS of a workgroup
 // (one row of V, the positions of a word's prefixes) must fit kArgmaxSieveLds
 constexpr size_t kArgmaxSieveLds = 64 * 1024 - 4096;

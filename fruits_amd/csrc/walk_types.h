@@ -103,22 +103,29 @@ constexpr int FR_SIEVE_CUR_K = 7;
 #else
 #define FR_HOST_DEVICE
 #endif
-// MAX / MIN in integers: an order-preserving 64-bit key of the value (its bits with the sign bit
-// flipped, or all bits flipped for a negative value), complemented for MIN - so that both are a
+// The order key: an order-preserving 64-bit image of a double (its bits with the sign bit flipped,
+// or all bits flipped for a negative value) and its inverse - what the rank selection sorts by.
+// MAX / MIN in integers: that key of the value, complemented for MIN - so that both are a
 // MAXIMUM of keys, and key 0 (a NaN's, which never is in a band) is the empty band.  The
 // reductions (wave shuffles, ds_max_u64 into the fused walk's window, the flush onto the feature
 // row) are then exact and independent of order.
-FR_HOST_DEVICE inline uint64_t band_key(double v, bool is_min) {
+FR_HOST_DEVICE inline uint64_t order_key(double v) {
   const uint64_t b = __builtin_bit_cast(uint64_t, v);
-  const uint64_t k = (b >> 63) ? ~b : (b | (1ull << 63));
+  return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+FR_HOST_DEVICE inline double order_key_value(uint64_t k) {
+  const uint64_t b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+  return __builtin_bit_cast(double, b);
+}
+FR_HOST_DEVICE inline uint64_t band_key(double v, bool is_min) {
+  const uint64_t k = order_key(v);
   return is_min ? ~k : k;
 }
 // ... and back; the empty band is 0.0 (the reference's empty-segment value)
 FR_HOST_DEVICE inline double band_key_value(uint64_t k, bool is_min) {
   if (is_min) k = ~k;
   if (k == 0 || k == ~0ull) return 0.0;
-  const uint64_t b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
-  return __builtin_bit_cast(double, b);
+  return order_key_value(k);
 }
 
 // One feature of one iterated sum, everything resolved on the host (32 bytes, read

@@ -771,6 +771,57 @@ def test_numpy_sum_model(tmp_path):
     assert np.signbit(L.pw_host_sum(z.ctypes.data, 9)) == np.signbit(np.add.reduce(z))
 
 
+def test_order_key_host(tmp_path):
+    """The one order key (csrc/walk_types.h) that the rank selection, the band sieves and the C ABI
+    share, compiled for the host (tests/native/order_key_host.cpp) over +-0.0, the denormal
+    minimum, 1, DBL_MAX, the infinities and a quiet NaN: order_key_value(order_key(v)) has v's
+    bits, a < b <=> order_key(a) < order_key(b) with -0.0 below +0.0, band_key is the key or its
+    complement, and the empty band of either kind is 0.0."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "order_key_host")
+    subprocess.check_call([gxx, "-std=c++17", "-O2", "-Wall", "-I", os.path.join(ROOT, "fruits_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "order_key_host.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "0 checks failed" in r.stdout, r.stdout + r.stderr
+
+
+def test_build_headers_match_includes():
+    """build.py rebuilds a unit when a header it lists for the unit is newer - so the lists must be
+    what the sources include: every local header a unit includes, directly or through another
+    header, is in HEADERS or listed for that unit in LOCAL_HEADERS (a missing entry silently
+    skips a rebuild); LOCAL_HEADERS names existing units only; and every .hip / .cpp of csrc/ is
+    some unit's source.  The generated jit_sources.inc is exempt."""
+    from fruits_amd import build as B
+    inc = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
+
+    def closure(path, seen):
+        with open(path) as f:
+            text = f.read()
+        for name in inc.findall(text):
+            p = os.path.normpath(os.path.join(os.path.dirname(path), name))
+            if name != "jit_sources.inc" and p not in seen:
+                seen.add(p)
+                closure(p, seen)
+        return seen
+
+    units = B.units()
+    names = {u[0] for u in units}
+    common = {os.path.normpath(os.path.join(B.CSRC, h)) for h in B.HEADERS}
+    for name, src, _ in units:
+        local = {os.path.normpath(os.path.join(B.CSRC, h)) for h, us in B.LOCAL_HEADERS.items() if name in us}
+        missing = closure(os.path.join(B.CSRC, src), set()) - common - local
+        assert not missing, (name, sorted(os.path.relpath(m, B.CSRC) for m in missing))
+    for h, us in B.LOCAL_HEADERS.items():
+        assert os.path.exists(os.path.join(B.CSRC, h)), h
+        assert set(us) <= names, (h, sorted(set(us) - names))
+    sources = {f for f in os.listdir(B.CSRC) if f.endswith((".hip", ".cpp"))}
+    assert sources == {u[1] for u in units}, sources ^ {u[1] for u in units}
+
+
 @pytest.mark.parametrize("key,piece,types", [("6,2", 64, 5), ("6,2", 128, 4), ("9,1", 64, 5), ("4,2", 16, None),
                                              ("3,3", 8, None)])
 def test_plan_in_pieces_is_a_cover(key, piece, types):
