@@ -25,6 +25,7 @@ HEADERS = ["kernels.h", "plan.h", "jit.h", "walk.h", "walk_device.h", "walk_fuse
 # headers that only some units include: {header: unit names}
 CAPI = ("capi_core", "capi_plan", "capi_walk", "capi_pipeline", "capi_select", "capi_kernels")
 LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep"),
+                 "select_partition.h": ("kernels_select",),
                  "capi_common.h": CAPI,
                  "capi_plan.h": ("capi_plan", "capi_walk", "capi_pipeline"),
                  "capi_pipeline.h": ("capi_walk", "capi_pipeline")}

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "select_partition.h"
 
 namespace fr {
 
@@ -44,9 +45,12 @@ __device__ __forceinline__ void next_level(int t, double (&v)[MI + 1]) {
 #pragma unroll
   for (int j = 0; j + LVL <= MI; ++j) v[j] = (t - j >= 1) ? v[j] - v[j + 1] : 0.0;
 }
-// The element loop of the data passes: block b takes series b, b + grid, ... and its threads stride
-// over the time axis (no per-element 64-bit division; few series: the time axis is split over the
-// blocks).  A wave takes FOUR elements per lane at a time wherever all of them exist (f4; the rest
+// The element loop of the data passes: which series and which part of the time axis a block takes is
+// select_partition's business (select_partition.h: every element exactly once, for every grid; no
+// per-element 64-bit division); its threads stride over the time range.  Every block of a launch
+// goes through the loop - one whose range is empty (a series shorter than the blocks it is shared
+// among) runs no iteration and takes part in whatever its kernel does around the loop.
+// A wave takes FOUR elements per lane at a time wherever all of them exist (f4; the rest
 // one by one, f1): the loads of the four are in flight together, only the first of them can lie in
 // the zero-padded head of a series (the others need no bounds tests), and whatever a pass reads
 // per JOB - its prefix, its histogram row - is read once for the four.
@@ -72,14 +76,11 @@ __device__ __forceinline__ void next_level4(const int (&t)[kSelUnroll], double (
 template <int MI, class F4, class F1>
 __device__ __forceinline__ void for_elements(const double *__restrict__ base, int64_t N, int64_t T, F4 f4, F1 f1) {
   static_assert(MI < 64, "elements 1 .. 3 of a group of four lie behind the padded head");
-  const int64_t per_series = (N >= (int64_t)gridDim.x) ? 1 : ((int64_t)gridDim.x + N - 1) / N;
-  const int64_t n_first = (int64_t)blockIdx.x / per_series, part = (int64_t)blockIdx.x % per_series;
-  const int64_t n_step = ((int64_t)gridDim.x + per_series - 1) / per_series;
-  const int64_t t_len = (T + per_series - 1) / per_series;
-  const int t_lo = (int)(part * t_len), t_hi = (int)((part * t_len + t_len < T) ? part * t_len + t_len : T);
+  const SelPartition mine = select_partition((int64_t)blockIdx.x, (int64_t)gridDim.x, N, T);
+  const int t_lo = mine.t_lo, t_hi = mine.t_hi;
   const int step = (int)blockDim.x;
   const int wave_last = (int)(threadIdx.x | 63u);   // the wave's last lane
-  for (int64_t n = n_first; n < N; n += n_step) {
+  for (int64_t n = mine.n_first; n < N; n += mine.n_step) {
     const double *__restrict__ row = base + n * T;
     for (int tb = t_lo; tb < t_hi; tb += step * kSelUnroll) {
       const int t0 = tb + (int)threadIdx.x;
@@ -718,15 +719,23 @@ __device__ __forceinline__ void succ_level(const SelGroup &g, int jb, int t, dou
       const unsigned long long key = order_key(v[0]);
       // the level's first job: a running minimum in a register, published at the end
       if (key > g.prefix[g.act[kb]] && key < best[LVL]) best[LVL] = key;
+      // (the tail of a time range runs with some of a wave's lanes switched off - for_elements, f1:
+      // a shuffle would read what such a lane does not hold)
+      const bool whole_wave = __ballot(true) == ~0ull;
       for (int k = kb + 1; k < ke; ++k) {
         // (further jobs of a level are rare: the wave's smallest candidate straight to memory)
         unsigned long long b = key > g.prefix[g.act[k]] ? key : ~0ull;
         if (__ballot(b != ~0ull) == 0) continue;
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long w = __shfl_xor(b, o);
-          b = w < b ? w : b;
+        unsigned long long *dst = &succ[jb + g.act[k]];
+        if (whole_wave) {
+          for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long w = __shfl_xor(b, o);
+            b = w < b ? w : b;
+          }
+          if ((threadIdx.x & 63) == 0 && b < *dst) atomicMin(dst, b);
+        } else if (b < *dst) {   // lane by lane
+          atomicMin(dst, b);
         }
-        if ((threadIdx.x & 63) == 0 && b < succ[jb + g.act[k]]) atomicMin(&succ[jb + g.act[k]], b);
       }
     }
     succ_level<MI, LVL + 1>(g, jb, t, v, best, succ);

@@ -2642,7 +2642,7 @@ def test_static_program_other_dimensions(fr, monkeypatch, words, D, tmp_path):
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("FRUITS_TEST_RANDOM_CASES", "12"))))
 def test_select_ranks_random(fr, seed):
-    """fr_select_ranks on random row blocks against a sort: sizes on both sides of the 2048
+    """fr_select_ranks on random row blocks against a sort: sizes on both sides of the 4096
     candidates a workgroup settles, heavy ties (one value many times - settled in the gather
     pass; a few values many times - the histogram passes go on), plateaus of a running
     maximum, tiny / huge / negative values, neighbouring ranks (the successor search) and the

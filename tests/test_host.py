@@ -789,6 +789,25 @@ def test_order_key_host(tmp_path):
     assert r.returncode == 0 and "0 checks failed" in r.stdout, r.stdout + r.stderr
 
 
+def test_select_partition_host(tmp_path):
+    """select_partition (csrc/select_partition.h: which series and which part of the time axis a
+    workgroup of the rank selection's data passes takes), compiled for the host
+    (tests/native/select_partition_host.cpp), exhaustively over grid 1 .. 512 and 4096, N 1 .. 600
+    and T in {1, 2, 255, 4096, 4097, 5000, 9000, 40000}: the blocks' intervals tile every series'
+    [0, T) exactly once, no block is idle while another holds several elements, and N >= grid
+    splits no series."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "select_partition_host")
+    subprocess.check_call([gxx, "-std=c++17", "-O2", "-Wall", "-pthread", "-I", os.path.join(ROOT, "fruits_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "native", "select_partition_host.cpp"), "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and " 0 checks failed" in r.stdout, r.stdout + r.stderr
+
+
 def test_build_headers_match_includes():
     """build.py rebuilds a unit when a header it lists for the unit is newer - so the lists must be
     what the sources include: every local header a unit includes, directly or through another
