@@ -24,7 +24,10 @@ FR_SIEVE_MAX, FR_SIEVE_MIN, FR_SIEVE_XPI, FR_SIEVE_LPI, FR_SIEVE_CUR = 3, 4, 5, 
 FR_SIEVE_SERIES_CUTS = 0x100   # OR-ed into a kind: the sieve's cuts are slots of a per-series table
 (FR_INFO_ROWS, FR_INFO_NODES, FR_INFO_LEVELS, FR_INFO_DIMS_USED, FR_INFO_MAX_DIM,
  FR_INFO_ALPHAS, FR_INFO_GROUPS, FR_INFO_SHARED, FR_INFO_STAGED_ROWS, FR_INFO_JIT_PROGRAMS,
- FR_INFO_AOT_PROGRAM, FR_INFO_STATIC_TAIL) = range(12)
+ FR_INFO_AOT_PROGRAM, FR_INFO_STATIC_TAIL, FR_INFO_LAST_LAUNCH, FR_INFO_LAST_WHOLE) = range(14)
+# kernel families of FR_INFO_LAST_LAUNCH (csrc/plan.h, WalkFamily)
+WALK_FAMILIES = (None, "interpreter", "static_aot", "static_jit", "lean", "packed", "fused",
+                 "fused_packed", "fused_jit", "fused_pieces")
 FR_E_ARG, FR_E_DIM, FR_E_HIP, FR_E_NOMEM, FR_E_LIMIT, FR_E_INDEX = -1, -2, -3, -4, -5, -6
 
 EXPORTS = [
@@ -340,6 +343,21 @@ class Plan:
         tail program, behind the whole-series units (0: no mixed launch)."""
         return int(lib().fr_plan_info(self._h, FR_INFO_STATIC_TAIL))
 
+    def last_launch(self) -> dict:
+        """How the most recent ``run`` of this plan - or of a pipeline over it - launched its walk
+        (fr_plan_info, FR_INFO_LAST_LAUNCH): ``family`` (one of WALK_FAMILIES; None: no walk
+        yet), ``G`` groups per series, ``persistent``, ``xcd_map``, ``nt_input``, ``wt``,
+        ``lds_pad`` (one was asked for), ``carry_in_lds``, ``tail_series`` and ``n_whole`` of a
+        mixed static launch, and the resident rounds the choice was made from: ``resident`` (the
+        groups) and ``mixed_resident`` (the tail), 0 where they were not asked."""
+        w = int(lib().fr_plan_info(self._h, FR_INFO_LAST_LAUNCH))
+        return {"family": WALK_FAMILIES[w & 15], "G": w >> 4 & 255, "persistent": w >> 12 & 15,
+                "xcd_map": w >> 16 & 1, "nt_input": w >> 17 & 1, "wt": w >> 18 & 1,
+                "lds_pad": w >> 19 & 1, "carry_in_lds": w >> 20 & 1,
+                "resident": w >> 21 & 0xfffff, "mixed_resident": w >> 41 & 0xfffff,
+                "tail_series": self.static_tail_series(),
+                "n_whole": int(lib().fr_plan_info(self._h, FR_INFO_LAST_WHOLE))}
+
     def jit_loaded(self) -> int:
         """Number of run-time compiled static programs this plan holds on the device."""
         return int(lib().fr_plan_info(self._h, FR_INFO_JIT_PROGRAMS))
@@ -651,6 +669,10 @@ class Pipeline:
     def pieces_loaded(self) -> int:
         """Kernels of piece types this pipeline holds (a large plan in pieces)."""
         return int(lib().fr_pipeline_info(self._h, 5))
+
+    def last_launch(self) -> dict:
+        """``Plan.last_launch`` of the pipeline's plan: ``run`` launches its walk."""
+        return self.plan.last_launch()
 
     def run(self, Xd, lookup_d, feats=None, groups: int = 0, work=None):
         t = torch()

@@ -325,6 +325,13 @@ int64_t fr_plan_info(const fr_plan_t *plan, int32_t what) {
       std::lock_guard<std::mutex> lock(q.mu);
       return q.last_tail_series;
     }
+    case FR_INFO_LAST_LAUNCH:
+    case FR_INFO_LAST_WHOLE: {
+      fr::Plan &q = *plan->p;
+      std::lock_guard<std::mutex> lock(q.mu);
+      return what == FR_INFO_LAST_WHOLE ? (int64_t)q.last_launch.choice.n_whole
+                                        : fr::pack_last_launch(q.last_launch);
+    }
     default: return fail(FR_E_ARG, "fr_plan_info: unknown selector");
   }
 }

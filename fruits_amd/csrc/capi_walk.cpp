@@ -357,11 +357,17 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   const bool vec_ok = (T % 2 == 0) && aligned16(d_X) &&
                       (fu || (aligned16(d_out) && (out_k_stride % 2 == 0) && (out_n_stride % 2 == 0)));
   fr::WalkChoice ch;
+  fr::LastLaunch rec;
   fr::GroupedProgram *gp = nullptr;
   const fr::JitProgram *jit_prog = nullptr;
   {
     std::lock_guard<std::mutex> lock(p.mu);
-    ch = fr::choose_walk_launch(p, gather_walk_facts(c, vec_ok, k), k);
+    fr::WalkFacts f = gather_walk_facts(c, vec_ok, k);
+    if (f.mixed_resident) {   // (the record keeps what the mixed instance reported)
+      f.mixed_resident = [&rec, ask = f.mixed_resident] { return rec.mixed_resident = ask(); };
+    }
+    ch = fr::choose_walk_launch(p, f, k);
+    rec.resident = f.resident;
     gp = &fr::grouped(p, ch.G);   // (map nodes are stable: the pointer outlives the lock)
     if (ch.static_prog < 0) jit_prog = &static_cast<JitState *>(p.jit)->progs[ch.G];
     if (!ch.static_prog) {   // (a static program reads no device tables)
@@ -372,15 +378,26 @@ int run_walk(const char *who, fr::Plan &p, const double *d_X, int64_t N, int64_t
   fr::IssArgs a = c.args();
   rc = fill_walk_args(c, *gp, ch, vec_ok, k, a);
   if (rc != FR_OK) return rc;
-  {
+  rec.choice = ch;
+  rec.family = fr::walk_family(ch, fu != nullptr);
+  auto keep_record = [&p, &rec] {   // FR_INFO_STATIC_TAIL, FR_INFO_LAST_LAUNCH
     std::lock_guard<std::mutex> lock(p.mu);
-    p.last_tail_series = ch.tail_series;
-  }
+    p.last_tail_series = rec.choice.tail_series;
+    p.last_launch = rec;
+  };
   if (fu && fu->pl && !ch.packed) {
     rc = launch_pieces(c, a, done);
-    if (rc == FR_OK && !done) rc = launch_own_kernel(c, *gp, a, done);
-    if (rc != FR_OK || done) return rc;
+    if (done) rec.family = fr::kWalkFusedPieces;
+    if (rc == FR_OK && !done) {
+      rc = launch_own_kernel(c, *gp, a, done);
+      if (done) rec.family = fr::kWalkFusedJit;
+    }
+    if (rc != FR_OK || done) {
+      if (done) keep_record();
+      return rc;
+    }
   }
+  keep_record();
   hipError_t e = jit_prog ? fr::jit_launch(*jit_prog, a, st) : fr::launch_iss_walk(a, p.levels, st);
   if (e != hipSuccess) return hip_fail(e, "iss_walk launch");
   return FR_OK;

@@ -51,21 +51,7 @@ struct WalkFacts {
   std::function<int(int)> largest_group;   // records of the largest group of the node order for G groups
 };
 
-struct WalkChoice {
-  bool packed = false;       // wave-per-series kernel (short series)
-  int G = 1;                 // groups of root sub-tries per series
-  int static_prog = 0;       // > 0: ahead-of-time static program, -1: run-time compiled, 0: none
-  int wt = 0;                // 1: the ahead-of-time program's write-through instance
-  int lds_pad = 0;           // unused LDS per workgroup (fewer resident ones)
-  bool cache_sized = false;  // a static-program shape whose input + output are about the Infinity Cache
-  int lean = 0;              // materialising launch through the fused walk's node loop
-  int persistent = 0;        // grid = one resident round of workgroups (> 1: the knob's cap per CU)
-  int nt_input = 0;          // the interpreter stages X with non-temporal loads
-  int carry_slots = 0, carry_per_node = 3, carry_in_lds = 0;
-  int64_t tail_series = 0;   // mixed launch: the last series run as the tail program's finer units
-  int32_t n_whole = 0;       // ... and the whole-series units in front of them (N: no finer units)
-  int xcd_map = 0;           // the groups of one series share an XCD
-};
+// (struct WalkChoice, what choose_walk_launch returns: plan.h - a plan keeps its most recent one)
 
 inline int choose_groups(const Plan &p, int64_t N, int requested, const WalkKnobs &k) {
   const int U = p.units();
@@ -358,6 +344,46 @@ inline WalkChoice choose_walk_launch(const Plan &p, const WalkFacts &f, const Wa
                                             : (R > 0 && R < N && N < 2 * R) ? N - R : 0;
   c.n_whole = (int32_t)(std::min<int64_t>(N, 0x7fffffff) - c.tail_series);
   return c;
+}
+
+// The family of kernels that the choice `c` names; a fused launch that the pipeline's own
+// run-time compiled kernels took over is kWalkFusedJit / kWalkFusedPieces (capi_walk.cpp).
+inline int walk_family(const WalkChoice &c, bool fused) {
+  if (fused) return c.packed ? kWalkFusedPacked : kWalkFused;
+  if (c.packed) return kWalkPacked;
+  if (c.static_prog) return c.static_prog > 0 ? kWalkStaticAot : kWalkStaticJit;
+  return c.lean ? kWalkLean : kWalkInterpreter;
+}
+
+// FR_INFO_LAST_LAUNCH: the launch as one word (0: the plan has not run a walk).  From bit 0:
+// family (4 bits), G (8), persistent (4), xcd_map, nt_input, wt, an LDS pad was asked for,
+// carry_in_lds (1 each); from bit 21 the resident round of the group choice and from bit 41 that
+// of the mixed instance (20 bits each, 0: not asked).  Counts beyond their field read as its
+// largest value.  tail_series and n_whole have words of their own (FR_INFO_STATIC_TAIL,
+// FR_INFO_LAST_WHOLE): a batch may hold 2^31 series.
+inline int64_t pack_last_launch(const LastLaunch &l) {
+  auto field = [](int64_t v, int bits) { return std::max<int64_t>(0, std::min<int64_t>(v, (int64_t(1) << bits) - 1)); };
+  const WalkChoice &c = l.choice;
+  if (l.family == kWalkNone) return 0;
+  return field(l.family, 4) | field(c.G, 8) << 4 | field(c.persistent, 4) << 12 |
+         int64_t(c.xcd_map != 0) << 16 | int64_t(c.nt_input != 0) << 17 | int64_t(c.wt != 0) << 18 |
+         int64_t(c.lds_pad != 0) << 19 | int64_t(c.carry_in_lds != 0) << 20 |
+         field(l.resident, 20) << 21 | field(l.mixed_resident, 20) << 41;
+}
+// (the fields pack_last_launch keeps; lds_pad reads 1 where a pad was asked for)
+inline LastLaunch unpack_last_launch(int64_t w) {
+  LastLaunch l;
+  l.family = (int)(w & 15);
+  l.choice.G = (int)(w >> 4 & 255);
+  l.choice.persistent = (int)(w >> 12 & 15);
+  l.choice.xcd_map = (int)(w >> 16 & 1);
+  l.choice.nt_input = (int)(w >> 17 & 1);
+  l.choice.wt = (int)(w >> 18 & 1);
+  l.choice.lds_pad = (int)(w >> 19 & 1);
+  l.choice.carry_in_lds = (int)(w >> 20 & 1);
+  l.resident = w >> 21 & 0xfffff;
+  l.mixed_resident = w >> 41 & 0xfffff;
+  return l;
 }
 
 }  // namespace fr

@@ -109,6 +109,44 @@ struct PiecedProgram {
   int chain_nodes = 0;                // node executions spent in chains (all types, per series)
 };
 
+// How a trie walk is launched: what choose_walk_launch (launch_choice.h) returns and capi_walk.cpp
+// carries out.  Here because a plan keeps its most recent one (Plan::last_launch).
+struct WalkChoice {
+  bool packed = false;       // wave-per-series kernel (short series)
+  int G = 1;                 // groups of root sub-tries per series
+  int static_prog = 0;       // > 0: ahead-of-time static program, -1: run-time compiled, 0: none
+  int wt = 0;                // 1: the ahead-of-time program's write-through instance
+  int lds_pad = 0;           // unused LDS per workgroup (fewer resident ones)
+  bool cache_sized = false;  // a static-program shape whose input + output are about the Infinity Cache
+  int lean = 0;              // materialising launch through the fused walk's node loop
+  int persistent = 0;        // grid = one resident round of workgroups (> 1: the knob's cap per CU)
+  int nt_input = 0;          // the interpreter stages X with non-temporal loads
+  int carry_slots = 0, carry_per_node = 3, carry_in_lds = 0;
+  int64_t tail_series = 0;   // mixed launch: the last series run as the tail program's finer units
+  int32_t n_whole = 0;       // ... and the whole-series units in front of them (N: no finer units)
+  int xcd_map = 0;           // the groups of one series share an XCD
+};
+
+// The kernel family a launch ran (FR_INFO_LAST_LAUNCH).
+enum WalkFamily {
+  kWalkNone = 0,          // the plan has not run a walk
+  kWalkInterpreter = 1,   // walk_device.h, iss_walk_kernel
+  kWalkStaticAot = 2,     // ahead-of-time static program (walk_static_inst.hip)
+  kWalkStaticJit = 3,     // static program compiled at run time
+  kWalkLean = 4,          // materialising launch of the fused walk's node loop (walk_fused.h)
+  kWalkPacked = 5,        // wave per series (walk_packed.h)
+  kWalkFused = 6,         // fused with the sieves: the built-in cooperative kernel
+  kWalkFusedPacked = 7,   // ... wave per series
+  kWalkFusedJit = 8,      // ... the pipeline's own run-time compiled kernel
+  kWalkFusedPieces = 9,   // ... the pipeline's kernels of a plan in pieces
+};
+struct LastLaunch {
+  WalkChoice choice;
+  int family = kWalkNone;
+  int64_t resident = 0;         // the resident round the groups were chosen from (0: not asked)
+  int64_t mixed_resident = 0;   // ... and the mixed instance's, which sets the tail (0: not asked)
+};
+
 struct Plan {
   CosProgram *cos = nullptr;  // non-null: a CosWISS program (no trie, K = W*F)
   int W = 0;
@@ -142,6 +180,7 @@ struct Plan {
   // -1: not looked up yet)
   int static_prog[4] = {-1, -1, -1, -1};
   int64_t last_tail_series = 0;   // FR_INFO_STATIC_TAIL: the most recent materialising launch (under mu)
+  LastLaunch last_launch;         // FR_INFO_LAST_LAUNCH: the most recent run_walk, fused ones too (under mu)
   void *jit = nullptr;   // run-time compiled static programs (capi_plan.h: JitState), or nullptr
   int device = -1;     // HIP device the uploaded tables live on (-1: nothing uploaded yet)
   std::mutex mu;       // guards `programs`, `cos->d_blob` and `device` (uploads at run time)

@@ -14,6 +14,7 @@
 // group); there is no contraction anywhere, so no MFMA.
 #pragma once
 #include "walk_types.h"
+#include "walk_units.h"
 #include "walk_scan.h"
 
 namespace fr {
@@ -1209,22 +1210,11 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_static_kernel(const Iss
       cx.out_base = a.out + (int64_t)b * a.out_n_stride;
       static_run_group<C, PG, 0>(cx, rg, lds, b, 0);
     } else {
-      constexpr int GT = PGT::groups;
-      const int j = b - n_whole;
-      const int S = (int)a.N - n_whole;
-      int64_t n;
-      int g;
-      if (S % 8 == 0) {   // the groups of one series meet in one XCD's L2
-        const int q = j >> 3, r = j & 7;
-        n = n_whole + (int64_t)(q / GT) * 8 + r;
-        g = q % GT;
-      } else {
-        n = n_whole + j / GT;
-        g = j % GT;
-      }
-      if (n < a.N) {   // (the host launches exactly n_whole + GT * S workgroups)
-        cx.out_base = a.out + n * a.out_n_stride;
-        static_run_group<C, PGT, 0>(cx, rg, lds, n, g);
+      // (S % 8 == 0: the groups of one series meet in one XCD's L2)
+      const WalkUnit w = walk_tail_unit(b - n_whole, PGT::groups, n_whole, (int)a.N - n_whole);
+      if (w.n < a.N) {   // (the host launches exactly n_whole + GT * S workgroups)
+        cx.out_base = a.out + w.n * a.out_n_stride;
+        static_run_group<C, PGT, 0>(cx, rg, lds, w.n, w.g);
       }
     }
   } else {
@@ -1234,15 +1224,10 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_static_kernel(const Iss
     for (int u = blockIdx.x; u < u_end; u += gridDim.x) {
       int64_t n = u;
       int g = 0;
-      if constexpr (G > 1) {
-        if (a.xcd_map) {   // the groups of one series meet in one XCD's L2
-          const int q = u >> 3, r = u & 7;
-          n = (int64_t)(q / G) * 8 + r;
-          g = q % G;
-        } else {
-          n = u / G;
-          g = u - (int)n * G;
-        }
+      if constexpr (G > 1) {   // (xcd_map: the groups of one series meet in one XCD's L2)
+        const WalkUnit w = walk_unit(u, G, a.xcd_map != 0);
+        n = w.n;
+        g = w.g;
       }
       cx.out_base = a.out + n * a.out_n_stride;
       cx.next_unit = u + (int)gridDim.x;
@@ -1338,17 +1323,9 @@ __global__ __launch_bounds__(kWalkThreads) WALK_KERNEL_ATTR void iss_walk_kernel
   }
   const int u_end = (int)(a.N * a.G);  // (the host checks < 2^31)
   for (int u = blockIdx.x; u < u_end; u += gridDim.x) {
-    int64_t n;
-    int g0;
-    if (a.xcd_map) {
-      const int q = u >> 3, r = u & 7;
-      n = (int64_t)(q / a.G) * 8 + r;
-      g0 = q % a.G;
-    } else {
-      const int ni = u / a.G;
-      n = ni;
-      g0 = u - ni * a.G;
-    }
+    const WalkUnit unit = walk_unit(u, a.G, a.xcd_map != 0);
+    const int64_t n = unit.n;
+    const int g0 = unit.g;
     const int node_begin = as_const(a.group_begin)[g0];
     if constexpr (C::MULTI == 1)
       cx.carry = lds + (int64_t)a.R * C::CHUNK + 4 * C::NW;
@@ -1416,8 +1393,7 @@ __global__ __launch_bounds__(kWalkThreads) WALK_KERNEL_ATTR void iss_walk_kernel
           const int n_rec = as_const(a.group_begin)[g0 + 1] - node_begin;
           const int un = u + (int)gridDim.x;
           if (un < u_end && n_rec <= a.prefetch_next && pf_off >= 0) {
-            const int64_t n_next =
-                a.xcd_map ? (int64_t)((un >> 3) / a.G) * 8 + (un & 7) : (int64_t)(un / a.G);
+            const int64_t n_next = walk_unit_series(un, a.G, a.xcd_map != 0);
             pf_val = *reinterpret_cast<const int *>(a.X + n_next * a.D * a.T + pf_off);
           }
         }

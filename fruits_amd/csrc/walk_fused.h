@@ -1197,18 +1197,9 @@ __global__ __launch_bounds__(kWalkThreads) void iss_fused_kernel(const IssArgs a
   }
   // one workgroup per unit (series n, group g0); with the xcd numbering the groups of one
   // series meet in one XCD's L2 (speed only)
-  const int u = blockIdx.x;
-  int64_t n;
-  int g0;
-  if (a.xcd_map) {
-    const int q = u >> 3, r = u & 7;
-    n = (int64_t)(q / a.G) * 8 + r;
-    g0 = q % a.G;
-  } else {
-    const int ni = u / a.G;
-    n = ni;
-    g0 = u - ni * a.G;
-  }
+  const WalkUnit unit = walk_unit((int)blockIdx.x, a.G, a.xcd_map != 0);
+  const int64_t n = unit.n;
+  const int g0 = unit.g;
   int node_begin = 0;
   if constexpr (!PG::is_piece) node_begin = as_const(a.group_begin)[g0];
   int sink = 0;

@@ -36,10 +36,11 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_packed_kernel(const Iss
   cx.full_chunk = C::CHUNK <= a.T;
   cx.slot = 0;
   const int64_t units = a.N * a.G;
-  for (int64_t u = (int64_t)blockIdx.x * C::TEAMS + cx.team; u < units;
-       u += (int64_t)gridDim.x * C::TEAMS) {
-    const int64_t n = u / a.G;
-    const int g = (int)(u % a.G);
+  for (int64_t u = packed_first_unit(blockIdx.x, C::TEAMS, cx.team); u < units;
+       u += packed_unit_stride(gridDim.x, C::TEAMS)) {
+    const WalkUnit unit = packed_unit(u, a.G);
+    const int64_t n = unit.n;
+    const int g = unit.g;
     const int node_begin = as_const(a.group_begin)[g];
     cx.pc_begin = node_begin;
     cx.out_base = a.out + n * a.out_n_stride;

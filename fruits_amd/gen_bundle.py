@@ -102,7 +102,8 @@ def manifest_key() -> str:
     """What the bundle depends on: the device sources the kernels are generated from, this file,
     the plan compiler, the JIT's source generator and the pipeline's op table and compilers."""
     h = hashlib.sha256()
-    for f in ("csrc/walk_types.h", "csrc/walk_scan.h", "csrc/walk_device.h", "csrc/walk_fused.h",
+    for f in ("csrc/walk_types.h", "csrc/walk_units.h", "csrc/walk_scan.h", "csrc/walk_device.h",
+              "csrc/walk_fused.h",
               "csrc/jit.cpp", "csrc/plan.cpp", "csrc/capi_pipeline.cpp", "csrc/capi_pipeline.h",
               "gen_bundle.py"):
         with open(os.path.join(HERE, f), "rb") as fh:

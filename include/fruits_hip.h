@@ -83,6 +83,18 @@ extern "C" {
 #define FR_INFO_STATIC_TAIL 11 /* series that the plan's most recent fr_iss_run launch ran as the finer
                                   units of a tail program behind the whole-series units (the mixed
                                   static launch), 0: none */
+#define FR_INFO_LAST_LAUNCH 12 /* how the plan's most recent fr_iss_run / fr_pipeline_run launched its
+                                  walk, 0: it has not run one.  From bit 0: the kernel family (4 bits;
+                                  1 interpreter, 2 ahead-of-time static program, 3 run-time compiled
+                                  static program, 4 lean walk, 5 wave per series, 6 fused, 7 fused wave
+                                  per series, 8 fused run-time compiled, 9 fused in pieces), groups per
+                                  series (8), persistent grid (4), then one bit each: XCD-aware
+                                  numbering, non-temporal input loads, write-through instance, an LDS
+                                  pad was asked for, chunk carries in LDS; from bit 21 the resident
+                                  round the groups were chosen from, from bit 41 that of the mixed
+                                  static instance (20 bits each, 0: not asked) */
+#define FR_INFO_LAST_WHOLE 13  /* ... and the series it ran as whole-series units (all of them unless
+                                  FR_INFO_STATIC_TAIL reports finer ones behind them) */
 
 /* sieve kinds of fr_sieve_* and the fused pipeline */
 #define FR_SIEVE_NPI 0 /* fruits/sieving/increment.py:101-129 */

@@ -6,7 +6,9 @@
 //   plan N T groups fused total_inc carry_per_node vec_ok resident aot1 aot2 aot3 jit_mask
 //   tail_groups mixed_R | knobs: groups persist packed lean wt tail static_cache_x100
 //   static_min_T FRUITS_HIP_STATIC
-// and prints every field of the WalkChoice, and how often the mixed instance was asked.
+// and prints every field of the WalkChoice, and how often the mixed instance was asked; then, on a
+// line of its own, the launch as fr_plan_info reports it (pack_last_launch) and what reads back from
+// that word (unpack_last_launch).  A field that does not read back as it went in ends the run.
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -80,6 +82,45 @@ int main() {
            c, ch.packed ? 1 : 0, ch.G, ch.static_prog, ch.wt, ch.lds_pad, ch.cache_sized ? 1 : 0, ch.lean,
            ch.persistent, ch.nt_input, ch.carry_slots, ch.carry_per_node, ch.carry_in_lds,
            (long long)ch.tail_series, ch.n_whole, ch.xcd_map, asked);
+    fr::LastLaunch rec;
+    rec.choice = ch;
+    rec.family = fr::walk_family(ch, f.fused);
+    rec.resident = f.resident;
+    rec.mixed_resident = asked ? mixed_R : 0;
+    const int64_t word = fr::pack_last_launch(rec);
+    const fr::LastLaunch back = fr::unpack_last_launch(word);
+    printf("launch %d: word=%lld family=%d G=%d persistent=%d xcd=%d nt=%d wt=%d pad=%d in_lds=%d "
+           "resident=%lld mixed=%lld\n",
+           c, (long long)word, back.family, back.choice.G, back.choice.persistent, back.choice.xcd_map,
+           back.choice.nt_input, back.choice.wt, back.choice.lds_pad, back.choice.carry_in_lds,
+           (long long)back.resident, (long long)back.mixed_resident);
+    auto sat = [](int64_t v, int bits) { return v < 0 ? 0 : (v >> bits ? (int64_t(1) << bits) - 1 : v); };
+    if (word <= 0 || back.family != rec.family || back.choice.G != sat(ch.G, 8) ||
+        back.choice.persistent != sat(ch.persistent, 4) || back.choice.xcd_map != (ch.xcd_map != 0) ||
+        back.choice.nt_input != (ch.nt_input != 0) || back.choice.wt != (ch.wt != 0) ||
+        back.choice.lds_pad != (ch.lds_pad != 0) || back.choice.carry_in_lds != (ch.carry_in_lds != 0) ||
+        back.resident != sat(rec.resident, 20) || back.mixed_resident != sat(rec.mixed_resident, 20)) {
+      printf("launch %d: the word does not read back\n", c);
+      return 4;
+    }
+  }
+  // fields beyond their width read as the width's largest value and disturb no neighbour
+  {
+    fr::LastLaunch big;
+    big.family = fr::kWalkFusedPieces;
+    big.choice.G = 1000;
+    big.choice.persistent = 99;
+    big.resident = int64_t(1) << 40;
+    big.mixed_resident = -5;
+    const fr::LastLaunch back = fr::unpack_last_launch(fr::pack_last_launch(big));
+    if (back.family != fr::kWalkFusedPieces || back.choice.G != 255 || back.choice.persistent != 15 ||
+        back.resident != 0xfffff || back.mixed_resident != 0 || back.choice.xcd_map || back.choice.wt ||
+        back.choice.nt_input || back.choice.lds_pad || back.choice.carry_in_lds != 0 ||
+        fr::pack_last_launch(fr::LastLaunch{}) != 0) {
+      printf("saturation: the word does not read back\n");
+      return 4;
+    }
+    printf("saturation: ok\n");
   }
   for (fr::Plan *p : plans) delete p;
   return 0;

@@ -724,6 +724,16 @@ def test_launch_choice_table(tmp_path):
          "packed=0 G=3 static=0 wt=0 pad=0 cache=0 lean=0"
          " persistent=0 nt=0 slots=90 per_node=3 in_lds=1 tail=0 whole=8192 xcd=1 mixed_asked=0"),
     ]
+    launches = {   # row of the table -> family (csrc/plan.h, WalkFamily) and the flags of its word
+        0: "family=2 G=3 persistent=0 xcd=1 nt=0 wt=0 pad=0 in_lds=1 resident=1536 mixed=0",
+        3: "family=2 G=1 persistent=0 xcd=0 nt=1 wt=1 pad=0 in_lds=1 resident=1536 mixed=1536",
+        5: "family=2 G=3 persistent=0 xcd=1 nt=0 wt=1 pad=1 in_lds=1 resident=1536 mixed=0",
+        8: "family=4 G=3 persistent=0 xcd=1 nt=0 wt=0 pad=1 in_lds=1 resident=1536 mixed=0",
+        9: "family=5 G=4 persistent=1 xcd=1 nt=0 wt=0 pad=0 in_lds=1 resident=1536 mixed=0",
+        12: "family=1 G=1 persistent=1 xcd=0 nt=1 wt=0 pad=0 in_lds=1 resident=1536 mixed=0",
+        19: "family=4 G=2 persistent=0 xcd=1 nt=0 wt=0 pad=0 in_lds=1 resident=0 mixed=0",
+        24: "family=6 G=2 persistent=0 xcd=1 nt=0 wt=0 pad=0 in_lds=1 resident=1536 mixed=0",
+    }
     text = (f"{len(plans)}\n" + "\n".join(plans) + f"\n{len(table)}\n"
             + "\n".join(c for c, _ in table) + "\n")
     for flags in ([], ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]):
@@ -740,6 +750,12 @@ def test_launch_choice_table(tmp_path):
         got = dict(re.findall(r"^case (\d+): (.*)$", r.stdout, re.M))
         for i, (c, want) in enumerate(table):
             assert got[str(i)] == want, (i, c)
+        # the same launches as fr_plan_info reports them (FR_INFO_LAST_LAUNCH: pack_last_launch,
+        # read back by unpack_last_launch; the program itself compares every field of every case)
+        word = dict(re.findall(r"^launch (\d+): word=\d+ (.*)$", r.stdout, re.M))
+        assert len(word) == len(table) and "saturation: ok" in r.stdout
+        for i, want in launches.items():
+            assert word[str(i)] == want, (i, table[i][0])
 
 
 def test_numpy_sum_model(tmp_path):
@@ -806,6 +822,32 @@ def test_select_partition_host(tmp_path):
                            os.path.join(ROOT, "tests", "native", "select_partition_host.cpp"), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 checks failed" in r.stdout, r.stdout + r.stderr
+
+
+def test_walk_units_host(tmp_path):
+    """The unit decode of the walk kernels (csrc/walk_units.h - the functions the kernels call),
+    compiled for the host (tests/native/walk_units_host.cpp): for N 1 .. 600 and around 1536 /
+    3072, G 1 .. 12, the strided grids (every grid up to 2 N G for N <= 32), every split of the
+    mixed static launch and the wave-per-series kernels' teams, every (series, group) is produced
+    exactly once and nothing else - XCD-aware numbering where the host sets it.  Built a second
+    time under AddressSanitizer + UBSan where the runtime exists (host code only)."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    src = os.path.join(ROOT, "tests", "native", "walk_units_host.cpp")
+    for flags in ([], ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]):
+        exe = str(tmp_path / ("walk_units" + ("_san" if flags else "")))
+        r = subprocess.run([gxx, "-std=c++17", "-O2", "-Wall"] + flags + [src, "-o", exe],
+                           capture_output=True, text=True)
+        if flags and r.returncode != 0 and "sanitize" in r.stderr:
+            pytest.skip("sanitizer runtime not available: " + r.stderr[-200:])
+        assert r.returncode == 0, r.stderr
+        assert "warning" not in r.stderr, r.stderr
+        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+        r = subprocess.run([exe], capture_output=True, text=True, env=env)
+        assert r.returncode == 0 and "every unit exactly once" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 def test_build_headers_match_includes():
