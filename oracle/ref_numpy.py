@@ -225,8 +225,19 @@ def lookup_l1(X_for_l1, relative=False, scale=50.0):
 # the ISS operator
 # --------------------------------------------------------------------------
 
+def require_extended_precision():
+    """``dtype=np.longdouble`` below is the high-precision side of the derived bounds
+    (tests/iss_bounds.py): it has to carry at least the 64-bit significand of the x87
+    format.  Where numpy's longdouble is a plain double this FAILS - a bound checked
+    against a reference of the same precision would prove nothing."""
+    eps = float(np.finfo(np.longdouble).eps)
+    assert eps <= 2.0 ** -63, (
+        "np.longdouble has eps = %g > 2^-63: no extended precision on this platform" % eps)
+
+
 def _letters(tmp, Z, el):
     # fruits/iss/semiring.py:111-117 / :143-149 : repeated multiply / divide
+    # (in the dtype of tmp and Z; a magnitude run hands in |Z|)
     for d, occ in enumerate(el):
         if occ > 0:
             for _ in range(occ):
@@ -238,28 +249,40 @@ def _letters(tmp, Z, el):
 
 
 def _shift(tmp):
-    # np.roll(tmp, 1); tmp[0] = 0   (semiring.py:109-110, :155-156)
+    # np.roll(tmp, 1); tmp[0] = 0   (semiring.py:109-110, :155-156); keeps tmp's dtype
     out = np.empty_like(tmp)
     out[:, 1:] = tmp[:, :-1]
     out[:, 0] = 0
     return out
 
 
-def iterated_sum_fast(Z, word, alpha, lookup, extended, total_weighting):
+def iterated_sum_fast(Z, word, alpha, lookup, extended, total_weighting,
+                      dtype=np.float64, magnitude=False):
     """fruits/iss/semiring.py:167-201 (Reals._iterated_sum_fast) with its two
     per-series bodies ``_total_weighted_reals_single`` (:128-158) and
     ``_reals_single`` (:93-125), vectorised over N.
 
-    Z (N,D,T) f8, word (L,Dw) i4, alpha (L,) f4, lookup (N,T) f8 -> (N,E,T)."""
+    Z (N,D,T) f8, word (L,Dw) i4, alpha (L,) f4, lookup (N,T) f8 -> (N,E,T).
+
+    ``dtype=np.longdouble`` evaluates every operation (letters, ``exp``, sums) in extended
+    precision from the same float64 inputs; ``magnitude=True`` runs the same computation on
+    ``|Z|`` - the exp weights are positive - which is the sum of the magnitudes of the terms
+    of every output element (test helpers; the defaults are the reference's arithmetic)."""
+    dtype = np.dtype(dtype).type
+    if dtype is not np.float64:
+        require_extended_precision()
     N, _, T = Z.shape
     L = len(word)
     word = np.asarray(word, dtype=np.int32).reshape(L, -1)
     alpha = np.asarray(alpha, dtype=np.float32)
-    out = np.zeros((N, extended, T))
-    tmp = np.ones((N, T))
+    Z = np.asarray(Z).astype(dtype, copy=False)
+    if magnitude:
+        Z = np.abs(Z)
+    out = np.zeros((N, extended, T), dtype=dtype)
+    tmp = np.ones((N, T), dtype=dtype)
     # the reference indexes lookup[j] for j < N (semiring.py:185-199): a lookup
     # with more rows than Z (fit on a sub-sample, see fruit_fit) is cut by position
-    lookup = lookup[:N]
+    lookup = np.asarray(lookup[:N]).astype(dtype, copy=False)
     if total_weighting:
         for k in range(L):
             tmp = _letters(tmp, Z, word[k])
@@ -397,9 +420,10 @@ def bayesian_iterated_sum_fast(Z, word, alpha, lookup, extended, total_weighting
 
 
 def iterated_sums(Z, word_rows, alpha=None, lookup=None, extended=1, total=False,
-                  semiring="Reals"):
+                  semiring="Reals", dtype=np.float64, magnitude=False):
     """fruits/iss/semiring.py:14-41 (Semiring.iterated_sums) for a SimpleWord:
-    no weighting => zero alpha, zero lookup, total=True (:27-28, :35)."""
+    no weighting => zero alpha, zero lookup, total=True (:27-28, :35).
+    ``dtype`` / ``magnitude``: see iterated_sum_fast (Reals only)."""
     L = len(word_rows)
     if lookup is None:
         alpha_ = np.zeros((L,), dtype=np.float32)
@@ -412,14 +436,25 @@ def iterated_sums(Z, word_rows, alpha=None, lookup=None, extended=1, total=False
         total_ = total
     fn = {"Reals": iterated_sum_fast, "Arctic": arctic_iterated_sum_fast,
           "Bayesian": bayesian_iterated_sum_fast}[semiring]
+    dtype = np.dtype(dtype).type
+    if dtype is not np.float64 or magnitude:
+        if semiring != "Reals":
+            raise NotImplementedError("dtype / magnitude runs are for the Reals semiring")
+        return fn(Z, np.array(word_rows, dtype=np.int32), alpha_, lookup_, extended, total_,
+                  dtype=dtype, magnitude=magnitude)
     return fn(Z, np.array(word_rows, dtype=np.int32), alpha_, lookup_, extended, total_)
 
 
 def iss_transform(X, word_strings, mode="SINGLE", alphas=None, lookup=None,
-                  total=False, semiring="Reals", argmax=False):
+                  total=False, semiring="Reals", argmax=False, dtype=np.float64,
+                  magnitude=False):
     """fruits/iss/iss.py:21-67 (_calculate_ISS, one batch of all words)
-    -> (K, N, T) in the reference's row order."""
+    -> (K, N, T) in the reference's row order.
+    ``dtype`` / ``magnitude``: see iterated_sum_fast (Reals only, not argmax)."""
     X = np.asarray(X, dtype=np.float64)
+    dtype = np.dtype(dtype).type
+    if argmax and (dtype is not np.float64 or magnitude):
+        raise NotImplementedError("dtype / magnitude runs are for the Reals semiring")
     if argmax:
         # iss.py:37-47: L + L(L+1)/2 rows per word, EXTENDED mode only
         if mode != "EXTENDED":
@@ -443,12 +478,12 @@ def iss_transform(X, word_strings, mode="SINGLE", alphas=None, lookup=None,
     else:
         plan = [1] * len(word_strings)
     K = sum(plan)
-    out = np.zeros((K, X.shape[0], X.shape[2]))
+    out = np.zeros((K, X.shape[0], X.shape[2]), dtype=dtype)
     idx = 0
     for i, s in enumerate(word_strings):
         rows = parse_word(s)
         a = None if alphas is None else alphas[i]
-        r = iterated_sums(X, rows, a, lookup, plan[i], total, semiring)
+        r = iterated_sums(X, rows, a, lookup, plan[i], total, semiring, dtype, magnitude)
         out[idx:idx + plan[i]] = np.swapaxes(r, 0, 1)
         idx += plan[i]
     return out
@@ -481,14 +516,35 @@ def coswiss_weightings(n_letters, exponent, total):
     return W
 
 
-def coswiss_trig(T, freq):
+def coswiss_angles(T, freq, dtype=np.float64):
+    """g_t = pi t / (f (T-1)) of fruits/iss/cos.py:23-24 in ``dtype`` (pi itself too)."""
+    f = float(np.float32(freq))
+    dtype = np.dtype(dtype).type
+    if dtype is np.float64:
+        return np.pi * np.arange(T) / (f * (T - 1))
+    require_extended_precision()
+    pi = dtype(4) * np.arctan(dtype(1))
+    return pi * np.arange(T).astype(dtype) / (dtype(f) * dtype(T - 1))
+
+
+def coswiss_trig(T, freq, dtype=np.float64, magnitude=False):
     """sin / cos tables of fruits/iss/cos.py:23-24.  ``freq`` is float32 in the
     reference's numba signature (f4) and is promoted to float64 before the product
     with (T-1); this follows numba's typing (the un-jitted code would multiply in
-    float32) - the goldens use frequencies for which both agree."""
-    f = float(np.float32(freq))
-    ang = np.pi * np.arange(T) / (f * (T - 1))
-    return np.sin(ang), np.cos(ang)
+    float32) - the goldens use frequencies for which both agree.
+
+    ``magnitude=True``: ``|sin| + tau`` and ``|cos| + tau`` with
+    ``tau[t] = (4 + 4 |g_t|) 2^-53`` - the absolute error a float64 table entry may carry
+    (sin / cos to 2 ulp <= 4 * 2^-53; g_t = pi t / (f (T-1)) with three roundings and the
+    rounding of pi itself, each moving sin / cos by at most |g_t| 2^-53): the relative
+    error of an entry is unbounded near its zeros, the padded magnitude keeps the terms
+    through such an entry from vanishing out of the bound."""
+    dtype = np.dtype(dtype).type
+    ang = coswiss_angles(T, freq, dtype)
+    if not magnitude:
+        return np.sin(ang), np.cos(ang)
+    tau = (4 + 4 * np.abs(ang)) * dtype(2.0 ** -53)
+    return np.abs(np.sin(ang)) + tau, np.abs(np.cos(ang)) + tau
 
 
 def coswiss_ffn(X, A, b, C):
@@ -513,26 +569,38 @@ def coswiss_ffn(X, A, b, C):
 
 
 def coswiss_transform(X, word_strings, freqs, exponent=2, total=False, ffn=None,
-                      dropout_indices=None):
+                      dropout_indices=None, dtype=np.float64, magnitude=False):
     """fruits/iss/cos.py:11-49,167-181,289-330 (_coswiss_single, _coswiss,
     CosWISS.batch_transform) -> (W*F, N, T), rows word-major.  ``ffn`` = (A, b, C) of
     CosWISS._fit (:250-257): the input of (word, frequency) is first sent through
     ``_ffn`` (:93-113, :128-135); ``dropout_indices`` (W, F, Lmax, rate) (:258-263): the
-    summand of letter k is zeroed at these indices before its cumsum (:80)."""
+    summand of letter k is zeroed at these indices before its cumsum (:80).
+
+    ``dtype=np.longdouble``: everything in extended precision (pi, the promoted frequency,
+    sin / cos, the sums) from the same float64 input; ``magnitude=True``: the same terms on
+    ``|X|`` with the padded ``|sin|``, ``|cos|`` tables of coswiss_trig - their coefficients
+    are products of binomials, positive (test helpers; not with ``ffn``)."""
+    dtype = np.dtype(dtype).type
+    if (dtype is not np.float64 or magnitude) and ffn is not None:
+        raise NotImplementedError("dtype / magnitude runs do not cover the ffn variant")
     N, _, T = X.shape
-    out = np.zeros((len(word_strings) * len(freqs), N, T))
+    if dtype is not np.float64:
+        X = np.asarray(X).astype(dtype)
+    if magnitude:
+        X = np.abs(X)
+    out = np.zeros((len(word_strings) * len(freqs), N, T), dtype=dtype)
     X_in = X
     for w, ws in enumerate(word_strings):
         word = parse_word(ws)
         L = len(word)
         Wt = coswiss_weightings(L, exponent, total)
         for f, freq in enumerate(freqs):
-            sin_w, cos_w = coswiss_trig(T, freq)
+            sin_w, cos_w = coswiss_trig(T, freq, dtype, magnitude)
             if ffn is not None:
                 X = coswiss_ffn(X_in, ffn[0][w, f], ffn[1][w, f], ffn[2][w, f])
-            res = np.zeros((N, T))
+            res = np.zeros((N, T), dtype=dtype)
             for i in range(Wt.shape[0]):
-                tmp = np.ones((N, T))
+                tmp = np.ones((N, T), dtype=dtype)
                 for k in range(L):
                     if k > 0:
                         tmp = _shift(tmp)

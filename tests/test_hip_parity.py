@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import iss_bounds as ib
 from conftest import load_golden, gen_input
 from oracle import c_oracle as corc
 from oracle import ref_numpy as orc
@@ -28,7 +29,8 @@ def fr():
     import fruits_amd
     from fruits_amd import _native as nat
     nat.require_device()
-    return fruits_amd
+    yield fruits_amd
+    ib.print_ratios()
 
 
 def rowwise_close(got, ref, rtol=RTOL):
@@ -557,7 +559,12 @@ def test_ragged_lengths(fr, T):
                      weighting=make_weighting(fr, weighting))
         lookup, total = orc._weight_lookup(weighting, X, X)
         ref = corc.iss_transform(X, words, "EXTENDED", None, lookup, total)
-        np.testing.assert_allclose(iss.fit_transform(X), ref, rtol=RTOL)
+        got = iss.fit_transform(X)
+        np.testing.assert_allclose(got, ref, rtol=RTOL)
+        # (the Indices lookup is one row formed on the host, bit-identical to the oracle's:
+        # test_other_lookups)
+        ib.check_reals(got, X, words, "EXTENDED", None, lookup, total,
+                       what=f"ragged T={T} {weighting}", family="ragged_lengths")
 
 
 def test_empty_batch(fr):
@@ -739,6 +746,9 @@ def test_coswiss_long_series(fr, T, total):
         ref = orc.coswiss_transform(X, words, freqs, exponent, total)
         scale = np.abs(ref).max(axis=2, keepdims=True)
         assert np.all(np.abs(out - ref) <= RTOL * np.maximum(np.abs(ref), 1e-3 * scale))
+        ib.check_coswiss(out, X, words, freqs, exponent, total,
+                         what=f"coswiss_long_series T={T} total={total} exponent={exponent}",
+                         family="coswiss_long_series")
 
 
 def test_coswiss_short_series_cooperative(fr, monkeypatch):
@@ -2449,6 +2459,8 @@ def test_static_programs(fr, monkeypatch, wd, mode):
             rowwise_close(got, ref)
             if dist == "uniform":
                 np.testing.assert_allclose(got, ref, rtol=RTOL)
+            ib.check_reals(got, X, strs, mode, what=f"static_programs {wd} {mode} N={N} T={T}",
+                           family="static_programs", most=32)
 
 
 def test_static_program_is_what_runs(fr, monkeypatch):

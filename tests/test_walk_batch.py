@@ -13,7 +13,8 @@ it is about, asserts through ``Plan.last_launch()`` that this branch ran, and ch
     groups, one round, trivial numbering - so the big launch has to reproduce it per series
     whatever its grid does (DESIGN.md 4.1b/c: groups agree, static = interpreter = lean);
 (d) the slabs agree with the oracle over the whole batch, by the bar of test_hip_parity.py for the
-    semiring and weighting.
+    semiring and weighting; the Reals rows of 96 of the series (one slab whole) also by the derived
+    elementwise bound of iss_bounds.py.
 
 The series are independent draws: a row computed from another series' input is off by O(1).
 Shapes that are defined against one resident round R of workgroups take R from the record of a
@@ -34,6 +35,7 @@ import time
 import numpy as np
 import pytest
 
+import iss_bounds as ib
 from conftest import gen_input
 from test_hip_parity import build_fruit, rowwise_close, sieve_kinds
 
@@ -47,7 +49,8 @@ def fr():
     import fruits_amd
     from fruits_amd import _native as nat
     nat.require_device()
-    return fruits_amd
+    yield fruits_amd
+    ib.print_ratios()
 
 
 def _words(fr, which):
@@ -94,8 +97,13 @@ def _first_difference(big, slab):
     return (flat // (N * T), flat // T % N, flat % T), int(series.sum())
 
 
-def _check_oracle(iss, words, X, got, weighting, semiring):
-    """(d): `got` (K, N, T) against the oracle over the whole batch; returns the deviation."""
+def _check_oracle(iss, words, X, got, weighting, semiring, lookup_dev=None, name=""):
+    """(d): `got` (K, N, T) against the oracle over the whole batch; returns the deviation.
+    Reals rows are held to the derived elementwise bound too (iss_bounds: the long-double oracle
+    with the device's own lookup) - on 96 series: every series of the first slab of 64 and 32
+    spread over the other slabs, the last series among them; a batch of at most 96 series whole.
+    The series outside these are held to the row-wise bar above alone ((c) compares a series
+    with the same series of the big launch, not with another one)."""
     from oracle import c_oracle as corc
     from oracle import ref_numpy as orc
     lookup, total = orc._weight_lookup(weighting, X, X)
@@ -104,7 +112,11 @@ def _check_oracle(iss, words, X, got, weighting, semiring):
     if semiring == "Arctic" or (semiring == "Bayesian" and weighting is None):
         np.testing.assert_array_equal(got, ref)    # max is exact, the letters multiply in order
         return 0.0
-    return rowwise_close(got, ref)
+    dev = rowwise_close(got, ref)
+    if semiring == "Reals":
+        ib.check_reals(got, X, [str(w) for w in words], "EXTENDED", None, lookup_dev, total,
+                       what=f"walk_batch {name}", family="walk_batch", whole=64)
+    return dev
 
 
 def _materialising(fr, monkeypatch, name, which, T, n_of, want, *, env=None, groups=0,
@@ -156,7 +168,8 @@ def _materialising(fr, monkeypatch, name, which, T, n_of, want, *, env=None, gro
     # (d) and those are right
     got = nat.to_host(slab)
     del big, slab
-    dev = _check_oracle(iss, words, X, got, weighting, semiring)
+    dev = _check_oracle(iss, words, X, got, weighting, semiring,
+                        lookup_dev=None if lk is None else nat.to_host(lk), name=name)
     print(f"walk_batch {name}: N={N} T={T} ran={ran} oracle_dev={dev:.3e} "
           f"seconds={time.perf_counter() - t0:.2f}")
 
@@ -299,6 +312,9 @@ def test_coswiss(fr):
         scale = np.abs(ref).max(axis=2, keepdims=True)
         bound = 1e-6 * np.maximum(np.abs(ref), 1e-3 * scale)    # (test_coswiss_long_series' bar)
         assert np.all(np.abs(out - ref) <= bound), exponent
+        # (the first slab of 64 whole and 32 series spread over the others: iss_bounds.series_subset)
+        ib.check_coswiss(out, X, words, freqs, exponent, False, what=f"walk_batch coswiss exponent={exponent}",
+                         family="walk_batch_coswiss", whole=64)
         print(f"walk_batch coswiss exponent={exponent}: oracle_dev="
               f"{np.max(np.abs(out - ref) / np.maximum(np.abs(ref), 1e-3 * scale)):.3e}")
     print(f"walk_batch coswiss: seconds={time.perf_counter() - t0:.2f}")
