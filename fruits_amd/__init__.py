@@ -2,8 +2,8 @@
 
 Same public surface as the reference package for the path
 ``INC -> ISS (Reals, SimpleWords, optional Indices / L1 weighting) -> NPI / END``
-(plus NEW, DIM, STD, NRM, MAV, LAG, FFN, RIN, JLD, the sieves MPI, XPI, LPI, MAX, MIN, CUR, AVG, STD and
-the sieve wrappers INC / INT, the Arctic semiring and CosWISS): ``fruits_amd.ISS(...).fit_transform(X)`` and
+(plus NEW, DIM, STD, NRM, MAV, LAG, FFN, RIN, JLD, the sieves MPI, XPI, LPI, MAX, MIN, CUR, AVG, STD, PPV,
+CPV and the sieve wrappers INC / INT, the Arctic semiring and CosWISS): ``fruits_amd.ISS(...).fit_transform(X)`` and
 ``fruits_amd.Fruit.fit / transform``.  All arithmetic runs in hand-written HIP
 kernels behind the C ABI of ``include/fruits_hip.h``; there is no CPU fallback.
 ``sieving.AVG`` and ``sieving.STD`` return CUR's numbers, as the reference's do

@@ -21,6 +21,8 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("FRUITS_HIP_LIB", "libfruits_hip.s
 FR_W_NONE, FR_W_NONTOTAL, FR_W_TOTAL = 0, 1, 2
 FR_SIEVE_NPI, FR_SIEVE_MPI, FR_SIEVE_END = 0, 1, 2
 FR_SIEVE_MAX, FR_SIEVE_MIN, FR_SIEVE_XPI, FR_SIEVE_LPI, FR_SIEVE_CUR = 3, 4, 5, 6, 7
+FR_SIEVE_PPV, FR_SIEVE_CPV = 16, 17   # numbers of their own: fr_sieve_implicit only
+FR_SIEVE_SEGMENTS = 0x200   # OR-ed into PPV / CPV at fr_pipeline_create: bands q_j <= v < q_(j+1)
 FR_SIEVE_SERIES_CUTS = 0x100   # OR-ed into a kind: the sieve's cuts are slots of a per-series table
 (FR_INFO_ROWS, FR_INFO_NODES, FR_INFO_LEVELS, FR_INFO_DIMS_USED, FR_INFO_MAX_DIM,
  FR_INFO_ALPHAS, FR_INFO_GROUPS, FR_INFO_SHARED, FR_INFO_STAGED_ROWS, FR_INFO_JIT_PROGRAMS,
@@ -35,7 +37,7 @@ EXPORTS = [
     "fr_memcpy_h2d", "fr_memcpy_d2h", "fr_stream_sync", "fr_plan_create",
     "fr_plan_destroy", "fr_plan_info", "fr_plan_dump", "fr_plan_records", "fr_plan_static_schedule", "fr_plan_pieces", "fr_plan_jit", "fr_plan_workspace_bytes",
     "fr_iss_run", "fr_iterated_sum_fast_host", "fr_increments",
-    "fr_pathlen_lookup", "fr_sieve", "fr_pre_transform", "fr_standardize",
+    "fr_pathlen_lookup", "fr_sieve", "fr_sieve_implicit", "fr_pre_transform", "fr_standardize",
     "fr_pipeline_create", "fr_pipeline_destroy", "fr_pipeline_info",
     "fr_pipeline_workspace_bytes", "fr_pipeline_run", "fr_pipeline_set_quantiles",
     "fr_select_ranks", "fr_select_ranks_begin", "fr_select_ranks_end", "fr_coswiss_combine", "fr_plan_create_coswiss", "fr_nan_to_num",
@@ -764,6 +766,20 @@ def sieve(kind: int, Ad, inc: int, cuts_d, q_d, out, out_col: int = 0):
                         C.c_int64(cuts_d.shape[0]), C.c_int32(C1), dptr(q_d), C.c_int32(Q1),
                         C.c_void_p(base), C.c_int64(out.stride(0)), stream_ptr())
     check(rc, "fr_sieve")
+    return out
+
+
+def sieve_implicit(kind: int, Ad, q_d, segments: bool, out, out_col: int = 0):
+    """Writes the features of a PPV / CPV sieve (fr_sieve_implicit) on a (N, T) device array
+    into columns [out_col, out_col + nfeatures) of the (N, F) device tensor ``out``; ``q_d``
+    holds the sieve's thresholds in its own order."""
+    N, T = Ad.shape
+    base = out.data_ptr() + 8 * out_col
+    rc = lib().fr_sieve_implicit(C.c_int32(kind), dptr(Ad), C.c_int64(N), C.c_int64(T),
+                                 C.c_int64(Ad.stride(0)), dptr(q_d), C.c_int32(int(q_d.numel())),
+                                 C.c_int32(1 if segments else 0), C.c_void_p(base),
+                                 C.c_int64(out.stride(0)), stream_ptr())
+    check(rc, "fr_sieve_implicit")
     return out
 
 

@@ -68,6 +68,23 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
   return launched(e, "sieve launch");
 }
 
+int fr_sieve_implicit(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride,
+                      const double *d_q, int32_t Q, int32_t segments, double *d_out,
+                      int64_t out_stride, void *stream) {
+  if (kind != FR_SIEVE_PPV && kind != FR_SIEVE_CPV)
+    return fail(FR_E_ARG, "fr_sieve_implicit: unknown kind");
+  if (N < 0 || T < 1 || N > 0x7fffffffLL) return fail(FR_E_ARG, "fr_sieve_implicit: bad shape");
+  if (Q < 1 || (segments && Q < 2) || !d_q)
+    return fail(FR_E_ARG, "fr_sieve_implicit: bad quantiles");
+  if (Q - (segments ? 1 : 0) > fr::kImplicitMaxFeatures)
+    return fail(FR_E_LIMIT, "fr_sieve_implicit: at most 256 features per sieve");
+  if (N == 0) return FR_OK;
+  if (!d_A || !d_out) return fail(FR_E_ARG, "fr_sieve_implicit: null device pointer");
+  hipError_t e = fr::launch_sieve_implicit(kind, d_A, N, T, a_stride, d_q, Q, segments ? 1 : 0,
+                                           d_out, out_stride, (hipStream_t)stream);
+  return launched(e, "implicit sieve launch");
+}
+
 int fr_pre_transform(const double *d_A, int64_t N, int64_t T, int64_t a_stride, int32_t inc,
                      double *d_out, void *stream) {
   if (N < 0 || T < 0 || inc < 0 || inc > 8) return fail(FR_E_ARG, "fr_pre_transform: bad argument");

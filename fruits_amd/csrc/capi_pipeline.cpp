@@ -291,6 +291,16 @@ void build_pipeline_ops(fr_pipeline_t *pl, const double *h_quant, std::vector<fr
           continue;
         }
         const double *q = h_quant + (size_t)k * pl->q_stride + sv.q_off;
+        if (sv.kind == FR_SIEVE_PPV || sv.kind == FR_SIEVE_CPV) {
+          // one op per feature: v >= q_b, or with segments q_b <= v < q_(b+1) - the thresholds as
+          // fitted, not sorted (an empty band stays empty); the walk leaves the count
+          const int nf = sv.Q1 - (sv.segments ? 1 : 0);
+          for (int b = 0; b < nf; ++b)
+            row.push_back(fr::FeatOp{sv.kind | (sv.segments ? fr::OPF_SEGMENTS : 0),
+                                     k * pl->per_sum + sv.col + b, 0, sv.cuts[1], q[b],
+                                     sv.segments ? q[b + 1] : std::numeric_limits<double>::infinity()});
+          continue;
+        }
         for (int j = 0; j < C; ++j)
           for (int b = 0; b + 1 < sv.Q1; ++b) {
             // the common shapes get a short path in the fused walk (walk_fused.h, OPF_SHAPE_*):
@@ -355,6 +365,13 @@ void set_pipeline_jit_ops(fr_pipeline_t *pl, const std::vector<fr::FeatOp> &ops)
     if (sv.inc > 2) pl->jit_ops.cps = std::max(pl->jit_ops.cps, 3 + 2 * (sv.inc - 2));
     if (sv.inc < 0) pl->jit_ops.cps = std::max(pl->jit_ops.cps, 15 + 2 * (-sv.inc));
   }
+  // CPV: the value of the row in front of a time chunk, one slot behind all the others (the
+  // LAST of the node's slots: walk_fused.h, fop_implicit)
+  for (const PipeSieve &sv : pl->sieves)
+    if (sv.kind == FR_SIEVE_CPV) {
+      pl->jit_ops.cps += 1;
+      break;
+    }
   pl->jit_uniform = K > 0 && pl->n_ops_eff > 0 && pl->cut_slots_needed == 0;
   for (int i = 0; i < pl->n_ops_eff && pl->jit_uniform; ++i) {
     int32_t w0 = ops[i].kind_inc;
@@ -481,18 +498,31 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
     PipeSieve sv;
     sv.kind = kinds[i] & 0xff;
     sv.series_cuts = (kinds[i] & FR_SIEVE_SERIES_CUTS) != 0;
+    const bool implicit = sv.kind == FR_SIEVE_PPV || sv.kind == FR_SIEVE_CPV;
+    sv.segments = implicit && (kinds[i] & FR_SIEVE_SEGMENTS) != 0;
     sv.inc = incs[i];
     sv.Q1 = Q1[i];
     const int c1 = C1[i];
     std::string bad;
     int code = FR_E_ARG;
-    if (sv.kind < 0 || sv.kind > FR_SIEVE_CUR || c1 < 2) bad = "bad sieve " + std::to_string(i);
+    if (sv.kind < 0 || (sv.kind > FR_SIEVE_CUR && !implicit) || c1 < 2 ||
+        ((kinds[i] & FR_SIEVE_SEGMENTS) && !implicit))
+      bad = "bad sieve " + std::to_string(i);
+    else if (implicit) {
+      // PPV / CPV (fruits/sieving/implicit.py): the whole row itself, thresholds in the sieve's order
+      if (sv.series_cuts || c1 != 2 || sv.inc != 0) bad = "PPV / CPV look at the whole row itself (cuts {0, T}, inc 0)";
+      else if (sv.Q1 < (sv.segments ? 2 : 1)) bad = "PPV / CPV need >= 1 thresholds, >= 2 with segments";
+      else if (sv.Q1 - (sv.segments ? 1 : 0) > fr::kImplicitMaxFeatures) {
+        bad = "at most 256 features per PPV / CPV sieve";
+        code = FR_E_LIMIT;
+      }
+    }
     else if (sv.kind == FR_SIEVE_LPI) {
       // (a run crosses lanes, waves and time chunks: the window has no carry for it)
       bad = "LPI is not fused";
       code = FR_E_LIMIT;
     }
-    if (bad.empty() && sv.kind != FR_SIEVE_END) {
+    if (bad.empty() && sv.kind != FR_SIEVE_END && !implicit) {
       if (sv.Q1 < 2) bad = "a band sieve needs >= 2 thresholds";
       else if (sv.inc < -8 || sv.inc > 8) {
         bad = "the fused epilogue supports inc -8 to 8";
@@ -527,7 +557,12 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
       }
       sv.cuts.push_back((int32_t)(c < 0 ? 0 : (c > T ? T : c)));
     }
-    const int nf = sv.kind == FR_SIEVE_END ? c1 - 1 : (c1 - 1) * (sv.Q1 - 1);
+    const int nf = sv.kind == FR_SIEVE_END ? c1 - 1
+                   : implicit ? sv.Q1 - (sv.segments ? 1 : 0) : (c1 - 1) * (sv.Q1 - 1);
+    if (implicit) {   // (the cuts given are not looked at: the whole series)
+      sv.cuts = {0, (int32_t)(T > 0x7fffffffLL ? 0x7fffffff : T)};
+      for (int f = 0; f < nf; ++f) pl->implicit_cols.push_back(sv.kind == FR_SIEVE_CPV ? ~(col + f) : col + f);
+    }
     sv.col = col;
     sv.q_off = qoff;
     // (XPI is MPI of the positions: sum and population, divided by mpi_finalize_kernel)
@@ -560,6 +595,7 @@ void fr_pipeline_destroy(fr_pipeline_t *pl) {
   if (pl->d_ops) (void)hipFree(pl->d_ops);
   if (pl->d_mpi_cols) (void)hipFree(pl->d_mpi_cols);
   if (pl->d_key_cols) (void)hipFree(pl->d_key_cols);
+  if (pl->d_implicit_cols) (void)hipFree(pl->d_implicit_cols);
   if (pl->d_npi_pairs) (void)hipFree(pl->d_npi_pairs);
   if (pl->d_prep) (void)hipFree(pl->d_prep);
   if (pl->d_argmax_words) (void)hipFree(pl->d_argmax_words);
@@ -679,6 +715,11 @@ int fr_pipeline_set_quantiles(fr_pipeline_t *pl, const double *h_quant) {
   if (!pl->key_cols.empty() && !pl->d_key_cols) {
     HIP_TRY(hipMalloc(&pl->d_key_cols, pl->key_cols.size() * 4));
     HIP_TRY(hipMemcpy(pl->d_key_cols, pl->key_cols.data(), pl->key_cols.size() * 4,
+                      hipMemcpyHostToDevice));
+  }
+  if (!pl->implicit_cols.empty() && !pl->d_implicit_cols) {
+    HIP_TRY(hipMalloc(&pl->d_implicit_cols, pl->implicit_cols.size() * 4));
+    HIP_TRY(hipMemcpy(pl->d_implicit_cols, pl->implicit_cols.data(), pl->implicit_cols.size() * 4,
                       hipMemcpyHostToDevice));
   }
   pl->have_quantiles = true;
@@ -981,6 +1022,12 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
                                                   (int)pl->key_cols.size(), pl->per_sum, p.K, st);
       if (e != hipSuccess) return hip_fail(e, "band_key_finalize launch");
     }
+    if (!pl->implicit_cols.empty()) {
+      hipError_t e = fr::launch_implicit_finalize(fu.walk_feats, N, F,
+                                                  static_cast<const int32_t *>(pl->d_implicit_cols),
+                                                  (int)pl->implicit_cols.size(), pl->per_sum, p.K, T, st);
+      if (e != hipSuccess) return hip_fail(e, "implicit_finalize launch");
+    }
     hipError_t e = fr::launch_gather_row_blocks(fu.walk_feats, d_feats, N, F, feat_stride, p.K,
                                                 pl->per_sum, walk_of_row, st);
     if (e != hipSuccess) return hip_fail(e, "gather_row_blocks launch");
@@ -999,6 +1046,12 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
                                                 static_cast<const int32_t *>(pl->d_key_cols),
                                                 (int)pl->key_cols.size(), pl->per_sum, p.K, st);
     if (e != hipSuccess) return hip_fail(e, "band_key_finalize launch");
+  }
+  if (!pl->implicit_cols.empty()) {
+    hipError_t e = fr::launch_implicit_finalize(d_feats, N, feat_stride,
+                                                static_cast<const int32_t *>(pl->d_implicit_cols),
+                                                (int)pl->implicit_cols.size(), pl->per_sum, p.K, T, st);
+    if (e != hipSuccess) return hip_fail(e, "implicit_finalize launch");
   }
   return FR_OK;
 }

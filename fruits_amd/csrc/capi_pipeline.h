@@ -16,6 +16,7 @@ namespace fr::capi {
 struct PipeSieve {
   int32_t kind, inc, Q1, col, q_off;
   bool series_cuts = false;    // cuts are slots of the per-series table (coquantile cuts)
+  bool segments = false;       // PPV / CPV: Q1 - 1 bands q_j <= v < q_(j+1) instead of Q1 tests v >= q_j
   std::vector<int32_t> cuts;   // transformed, clamped to [0, T]
 };
 
@@ -90,6 +91,10 @@ struct fr_pipeline {
   std::vector<int32_t> argmax_words;
   void *d_argmax_words = nullptr;
   int32_t argmax_rows = 0, argmax_max_len = 0;
+  // PPV columns (~column: CPV) inside one iterated sum's block: the walk leaves counts there,
+  // implicit_finalize_kernel divides them
+  std::vector<int32_t> implicit_cols;
+  void *d_implicit_cols = nullptr;
   int rows() const { return argmax_words.empty() ? plan->p->K : argmax_rows; }   // output rows
   void *d_ops = nullptr;           // (rows, n_ops_padded) FeatOp
   void *d_mpi_cols = nullptr;

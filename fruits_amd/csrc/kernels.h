@@ -26,6 +26,8 @@ hipError_t launch_mpi_finalize(double *feats, const double *cnt, int64_t N, int6
                                int per_sum, int K, hipStream_t st);
 hipError_t launch_band_key_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
                                     int n_cols, int per_sum, int K, hipStream_t st);
+hipError_t launch_implicit_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
+                                    int n_cols, int per_sum, int K, int64_t T, hipStream_t st);
 hipError_t launch_gather_row_blocks(const double *src, double *dst, int64_t N, int64_t src_stride,
                                     int64_t dst_stride, int K, int per_sum, const int32_t *walk_of_row,
                                     hipStream_t st);
@@ -39,6 +41,11 @@ hipError_t launch_pathlen_lookup(const double *X, int64_t N, int64_t D, int64_t 
 hipError_t launch_sieve(int kind, const double *A, int64_t N, int64_t T, int64_t a_stride, int inc,
                         const int64_t *cuts, int64_t cut_rows, int C1, const double *q, int Q1,
                         double *out, int64_t out_stride, hipStream_t st);
+// PPV / CPV: Q thresholds, Q - 1 features with `segments`
+constexpr int kImplicitMaxFeatures = 256;   // (8 KiB of integer counters per workgroup)
+hipError_t launch_sieve_implicit(int kind, const double *A, int64_t N, int64_t T, int64_t a_stride,
+                                 const double *q, int Q, int segments, double *out,
+                                 int64_t out_stride, hipStream_t st);
 // jobs sorted so that the jobs of one group (<= kSelGroupMax, same row block) are adjacent;
 // groups = int2 {first job, count}
 constexpr int kSelGroupMax = 8;

@@ -379,6 +379,33 @@ hipError_t launch_band_key_finalize(double *feats, int64_t N, int64_t stride, co
   return hipGetLastError();
 }
 
+// PPV / CPV columns of a fused launch hold COUNTS (the indicator's population, ~column: its
+// rising edges): the one division of fruits/sieving/implicit.py:124-128, 182 - count / T, or
+// 2 * count / n with n = T rounded up to even - exactly as the standalone kernel forms it.
+__global__ void implicit_finalize_kernel(double *__restrict__ feats, int64_t N, int64_t stride,
+                                         const int32_t *__restrict__ cols, int n_cols, int per_sum,
+                                         int K, int64_t T) {
+  const int64_t per_n = (int64_t)K * n_cols;
+  const int64_t total = N * per_n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t n = i / per_n, r = i % per_n;
+    const int64_t k = r / n_cols;
+    const int c = cols[r % n_cols];
+    double *f = feats + n * stride + k * per_sum + (c < 0 ? ~c : c);
+    *f = c < 0 ? (2.0 * *f) / (double)(T + (T & 1)) : *f / (double)T;
+  }
+}
+
+hipError_t launch_implicit_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
+                                    int n_cols, int per_sum, int K, int64_t T, hipStream_t st) {
+  const int64_t total = N * (int64_t)K * n_cols;
+  if (total <= 0) return hipSuccess;
+  hipLaunchKernelGGL(implicit_finalize_kernel, dim3(grid_blocks(total, 4096)), dim3(256), 0, st, feats, N,
+                     stride, cols, n_cols, per_sum, K, T);
+  return hipGetLastError();
+}
+
 // A plan in pieces leaves its features in WALK order (plan.h, PiecedProgram): the blocks of
 // `per_sum` columns of one iterated sum back into the reference's row order,
 // dst[n, k * per_sum + j] = src[n, walk_of_row[k] * per_sum + j].  Writes are coalesced, reads

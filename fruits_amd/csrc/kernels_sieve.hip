@@ -221,6 +221,63 @@ __global__ __launch_bounds__(256) void band_sieve_kernel(int kind, const double 
   }
 }
 
+// PPV / CPV (fruits/sieving/implicit.py:114-129, 169-190) on the same (N,T) rows: one workgroup
+// per series, EVERY threshold of the sieve in one pass over the row.  The indicator of feature j
+// is closed below - v >= q_j, or with `segments` q_j <= v < q_(j+1) evaluated per element (the
+// fitted thresholds are not sorted: a band with q_j > q_(j+1) is empty) - so a NaN never counts
+// and +inf counts against a finite threshold, as in numpy.  PPV counts the indicator, CPV its
+// rising edges at t >= 1 (the first difference is zero-padded, fruits/cache.py:8-13: a component
+// that starts at t = 0 is not counted).  Counts are integers: a wave adds its ballot's population
+// to a counter of its own, the four are added in wave order, and one division forms the feature.
+__device__ __forceinline__ bool implicit_in(double v, const double *__restrict__ q, int j, bool segments) {
+  return segments ? (q[j] <= v && v < q[j + 1]) : (v >= q[j]);
+}
+
+__global__ __launch_bounds__(256) void implicit_sieve_kernel(int kind, const double *__restrict__ A,
+                                                              int64_t T, int64_t a_stride,
+                                                              const double *__restrict__ q, int F,
+                                                              int segments, double *__restrict__ out,
+                                                              int64_t out_stride) {
+  __shared__ unsigned long long sm_cnt[4][kImplicitMaxFeatures];
+  const int64_t n = blockIdx.x;
+  const double *row = A + n * a_stride;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool cpv = kind == FR_SIEVE_CPV_K;
+  for (int j = tid; j < 4 * F; j += blockDim.x) sm_cnt[j / F][j % F] = 0;
+  __syncthreads();
+  // (every lane takes every trip: the ballots are of whole waves)
+  for (int64_t base = 0; base < T; base += blockDim.x) {
+    const int64_t t = base + tid;
+    const bool valid = t < T;
+    const double v = valid ? row[t] : 0.0;
+    const double prev = (valid && t >= 1) ? row[t - 1] : 0.0;
+    for (int j = 0; j < F; ++j) {
+      bool hit = valid && implicit_in(v, q, j, segments != 0);
+      if (cpv) hit = hit && t >= 1 && !implicit_in(prev, q, j, segments != 0);
+      const int c = __popcll(__ballot(hit));
+      if (lane == 0) sm_cnt[wave][j] += (unsigned long long)c;   // (the wave's own counter)
+    }
+  }
+  __syncthreads();
+  // PPV: count / T; CPV: 2 * count / n with n = T rounded up to even (implicit.py:173-175)
+  const double denom = cpv ? (double)(T + (T & 1)) : (double)T;
+  for (int j = tid; j < F; j += blockDim.x) {
+    const unsigned long long c = ((sm_cnt[0][j] + sm_cnt[1][j]) + sm_cnt[2][j]) + sm_cnt[3][j];
+    out[n * out_stride + j] = (double)(cpv ? 2 * c : c) / denom;
+  }
+}
+
+hipError_t launch_sieve_implicit(int kind, const double *A, int64_t N, int64_t T, int64_t a_stride,
+                                 const double *q, int Q, int segments, double *out,
+                                 int64_t out_stride, hipStream_t st) {
+  if (N <= 0) return hipSuccess;
+  const int F = segments ? Q - 1 : Q;
+  if (N > 0x7fffffffLL || F < 1 || F > kImplicitMaxFeatures) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(implicit_sieve_kernel, dim3((unsigned)N), dim3(256), 0, st, kind, A, T, a_stride,
+                     q, F, segments, out, out_stride);
+  return hipGetLastError();
+}
+
 // IncrementSieve._pre_transform (inc >= 0) materialised: out[n,t] = D_inc[n,t]
 __global__ void pre_transform_kernel(const double *__restrict__ A, int64_t N, int64_t T,
                                      int64_t a_stride, int inc, double *__restrict__ out) {

@@ -537,6 +537,9 @@ template <int EP>
 struct FusedScratch {
   double dp[EP];
   bool have_dp = false;
+  // CPV: the value of the row one element to the left, exchanged once per node
+  double cp[EP];
+  bool have_cp = false;
 };
 
 // `s` is the scan input the values came from (c = cumsum(s)) when seq_steps.  Then a
@@ -597,6 +600,38 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
   }
   const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
   const int t_first = (int)cx.t0 + cx.wave * C::SPAN + cx.lane * E;  // element (h=0, e=0)
+  if (kind == FR_SIEVE_PPV_K || kind == FR_SIEVE_CPV_K) {
+    // PPV / CPV (fruits/sieving/implicit.py:114-129, 169-190): the indicator v >= qlo - or with
+    // OPF_SEGMENTS qlo <= v < qhi, per element: the thresholds are not sorted - counted (PPV), or
+    // its rising edges at t >= 1 (CPV; zero-padded first difference, fruits/cache.py:8-13).  The
+    // value at t - 1 is the row's own (c): one neighbour exchange per node (FusedScratch), its
+    // chunk carry in the node's slot 3.  implicit_finalize_kernel divides the counts.
+    const bool cpv = kind == FR_SIEVE_CPV_K, seg = (w[0] & OPF_SEGMENTS) != 0;
+    if (cpv && !sc.have_cp) {
+      prev_first_differences<C>(cx, c, sc.cp, 3);
+      sc.have_cp = true;
+    }
+    int n_in = 0;
+#pragma unroll
+    for (int h = 0; h < P; ++h)
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const int t = t_first + h * C::PIECE + e;
+        const double v = c[h * E + e];
+        bool in = seg ? (qlo <= v && v < qhi) : (v >= qlo);
+        if (cpv) {
+          const double u = sc.cp[h * E + e];
+          const bool before = seg ? (qlo <= u && u < qhi) : (u >= qlo);
+          in = in && !before && t >= 1;
+        }
+        n_in += __popcll(__ballot(in && t < hi));
+      }
+    if (cx.lane == 0) {
+      if constexpr (C::TEAM != 1) lds_add(cx.fl_val + slot, (double)n_in);
+      else cx.feat_row[col] = (double)n_in;
+    }
+    return;
+  }
   double d[EP];
   if (inc <= 0) {
 #pragma unroll

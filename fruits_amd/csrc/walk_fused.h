@@ -308,6 +308,48 @@ __device__ __forceinline__ void end_pick(WalkCtx &cx, int pick, int slot, const 
   lds_store_lane((int)(q / E), lds_offset(cx.fl_val + slot), v);
 }
 
+// PPV / CPV (fruits/sieving/implicit.py:114-129, 169-190): the indicator is closed BELOW -
+// v >= qlo, or with OPF_SEGMENTS qlo <= v < qhi, a conjunction per element (the thresholds are
+// not sorted: a band with qlo > qhi is empty; a NaN is never in, +inf is in above a finite qlo).
+// PPV counts it; CPV counts its rising edges at t >= 1 - the first difference of the indicator
+// is zero-padded (fruits/cache.py:8-13), a component that starts at t = 0 is not counted.  The
+// indicator at t - 1 is taken from the VALUE the row holds there (c, what MODE 2 stores): the
+// lane's own register, the neighbour lane's, the wave's in front through LDS, and across time
+// chunks the node's LAST carry slot (IssArgs::carry_per_node - 1).  The exchange is made once
+// per node and chunk, whatever the number of CPV ops (FusedScratch, like the first differences
+// of the inc = 2 ops), so one slot does.  Counts are integers, one LDS add per wave like NPI's;
+// implicit_finalize_kernel divides them.
+template <class C>
+__device__ __forceinline__ void fop_implicit(WalkCtx &cx, const int32_t *w, int slot,
+                                             const double (&c)[C::EP], FusedScratch<C::EP> &sc) {
+  constexpr int E = C::E;
+  static_assert(C::P == 1, "one piece per wave");
+  const bool cpv = (w[0] & 0xff) == FR_SIEVE_CPV_K, seg = (w[0] & OPF_SEGMENTS) != 0;
+  const int hi = w[3];   // T
+  const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
+  if (cpv && !sc.have_cp) {
+    int at = 0;
+    if constexpr (C::MULTI != 0) at = cold_args()->carry_per_node - 1;
+    prev_first_differences<C>(cx, c, sc.cp, at);   // cp[t] = c[t - 1]
+    sc.have_cp = true;
+  }
+  const int t_first = (int)cx.t0 + cx.wave * C::SPAN + cx.lane * E;
+  int cnt = 0;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const int t = t_first + e;
+    const double v = c[e];
+    bool in = seg ? (qlo <= v && v < qhi) : (v >= qlo);
+    if (cpv) {
+      const double u = sc.cp[e];
+      const bool before = seg ? (qlo <= u && u < qhi) : (u >= qlo);
+      in = in && !before && t >= 1;
+    }
+    cnt += __popcll(__ballot(in && t < hi));
+  }
+  lds_add_lane0(lds_offset(cx.fl_val + slot), (double)cnt);
+}
+
 template <class C>
 __device__ __forceinline__ void fop(WalkCtx &cx, const int32_t *w, int slot, const double (&c)[C::EP],
                                     const double (&x)[C::EP], const double (&s)[C::EP],
@@ -359,6 +401,10 @@ __device__ __forceinline__ void fop(WalkCtx &cx, const int32_t *w, int slot, con
       if (pick < 0) pick += (int)ca->T;
     }
     end_pick<C>(cx, pick, slot, c);
+    return;
+  }
+  if (kind == FR_SIEVE_PPV_K || kind == FR_SIEVE_CPV_K) {
+    if constexpr (C::MODE == 1) fop_implicit<C>(cx, w, slot, c, sc);
     return;
   }
   int lo = w[2], hi = w[3];

@@ -97,6 +97,11 @@ constexpr int FR_SIEVE_MIN_K = 4;
 constexpr int FR_SIEVE_XPI_K = 5;
 constexpr int FR_SIEVE_LPI_K = 6;
 constexpr int FR_SIEVE_CUR_K = 7;
+// (numbers of their own: valid in fr_sieve_implicit only, never in fr_sieve)
+constexpr int FR_SIEVE_PPV_K = 16;
+constexpr int FR_SIEVE_CPV_K = 17;
+// FeatOp::kind_inc bit of a PPV / CPV op: the band qlo <= v < qhi instead of the test v >= qlo
+constexpr int32_t OPF_SEGMENTS = 1 << 17;
 
 #if defined(__HIP__) || defined(__HIPCC_RTC__)
 #define FR_HOST_DEVICE __host__ __device__
@@ -130,7 +135,8 @@ FR_HOST_DEVICE inline double band_key_value(uint64_t k, bool is_min) {
 
 // One feature of one iterated sum, everything resolved on the host (32 bytes, read
 // with one scalar load): END picks the value at index `lo`; NPI / MPI look at
-// t in [lo, hi) and values in (qlo, qhi] of the inc-times differenced row.
+// t in [lo, hi) and values in (qlo, qhi] of the inc-times differenced row; PPV / CPV look at
+// t in [lo, hi) = [0, T) and values >= qlo (OPF_SEGMENTS: in [qlo, qhi)) of the row itself.
 struct FeatOp {
   int32_t kind_inc;   // kind | inc << 8 | per-series cuts << 16 (lo / hi are then slots of the
                       // series' row of IssArgs::series_cuts)

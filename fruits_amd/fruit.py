@@ -127,9 +127,17 @@ def _leaf(sv):
     return sv if form is None else form[0]
 
 
+def _n_thresholds(sv) -> int:
+    """Entries of a sieve's row of the pipeline's threshold table: a band sieve's len(q); PPV /
+    CPV say (their ``_q`` holds the fitted thresholds, sieving/implicit.py)."""
+    return sv._n_thresholds() if hasattr(sv, "_n_thresholds") else len(sv._q)
+
+
 def _interpolated_quantiles(sieve, reqs, lo_vals: np.ndarray, hi_vals: np.ndarray) -> np.ndarray:
     """SegmentSieve._set_quantiles_from_stats for all rows at once: (rows, len(q)) thresholds
     from the (rows, len(reqs)) order statistics np.quantile interpolates between."""
+    if hasattr(sieve, "_thresholds_from_stats"):      # PPV / CPV: their own order, not sorted
+        return sieve._thresholds_from_stats(reqs, lo_vals, hi_vals)
     qs = np.empty((lo_vals.shape[0], len(sieve._q)))
     qs[:] = [np.inf if q == 1.0 else (-np.inf if q == -1.0 else 0.0) for q in sieve._q]
     for j, (i, _, _, gamma) in enumerate(reqs):
@@ -460,7 +468,14 @@ class FruitSlice:
         """Fits the per-iterated-sum sieve copies without moving the fit sample's
         iterated sums to the host: the order statistics np.quantile interpolates
         between are selected on the device (fr_select_ranks).  Returns False when a
-        sieve or the ISS layout needs the host path.  ``deferred``: the selections are only
+        sieve or the ISS layout needs the host path - among them a PPV / CPV with
+        ``sample_size < 1``: every copy of it takes its quantiles of a random subset of its own.
+        With ``sample_size == 1`` the subset is the whole sample, whose order statistics do not
+        depend on the order of the rows; the draws from numpy's global generator the reference
+        makes for it (fruits/sieving/implicit.py:104-108: iterated sum by iterated sum, sieve by
+        sieve, threshold by threshold) are made HERE, when the slice is fitted, never in the
+        deferred closures - the preparateurs of the next slice draw from the same generator.
+        ``deferred``: the selections are only
         QUEUED (fr_select_ranks_begin); a closure per word batch that waits for its selection and
         forms the thresholds is appended - Fruit.fit runs them when every slice has been queued,
         so that the device goes from one slice's selection to the next slice's iterated sums
@@ -473,6 +488,9 @@ class FruitSlice:
         for sv, form in zip(self._sieves, forms):
             if sv.requires_fitting and not (form is not None and 0 <= form[3] <= 8):
                 return False
+            if form is not None and getattr(form[0], "_sample_size", 1.0) != 1.0:
+                return False
+        drawing = [form[0] for form in forms if form is not None and hasattr(form[0], "_fit_draws")]
         # what asks for order statistics, and the differencing order it asks them of
         leaves = [None if form is None else form[0] for form in forms]
         fit_inc = [None if form is None else form[3] for form in forms]
@@ -483,6 +501,9 @@ class FruitSlice:
         self._sieves_extended = _FittedRows(self._sieves, cache)
         for s, e in iss.word_batches(Ns, T):
             block = iss.transform_device(Sd, s, e, lookup)
+            for _ in range(int(block.shape[0]) if drawing else 0):
+                for sv in drawing:
+                    sv._fit_draws(Ns)
             # (what a sieve asks for depends on its q and the sample size only: once per sieve,
             # not once per copy)
             asks = [leaf._quantile_requests(n) if sv.requires_fitting else None
@@ -539,6 +560,7 @@ class FruitSlice:
 
     # ---- fused ISS + sieves (one launch, no (K, N, T) tensor) --------------------
     def _fusable(self) -> bool:
+        from .sieving.implicit import CPV, PPV
         from .sieving.increment import MPI, NPI, XPI
         from .sieving.segment import AVG, CUR, END, MAX, MIN, STD
         from .sieving.wrapper import INC, INT
@@ -575,7 +597,7 @@ class FruitSlice:
             if form is None or form[0] is not inner:
                 return False
             # (LPI is not fused: a run crosses lanes, waves and time chunks - DESIGN 4.3)
-            if type(inner) not in (NPI, MPI, XPI, MAX, MIN, END, CUR, AVG, STD):
+            if type(inner) not in (NPI, MPI, XPI, MAX, MIN, END, CUR, AVG, STD, PPV, CPV):
                 return False
             if type(inner) is not END and not -8 <= form[2] <= 8:
                 return False     # (cumulated rows: series of one time chunk; the pipeline says if not)
@@ -639,8 +661,8 @@ class FruitSlice:
                         if th is None:
                             sv._get_unfitted_quantiles()
                             th = sv._quantiles
-                        quant[:, off:off + len(sv._q)] = th
-                        off += len(sv._q)
+                        quant[:, off:off + _n_thresholds(sv)] = th
+                        off += _n_thresholds(sv)
                 for k, row in enumerate(() if lazy else rows):
                     sieves = self._sieves_extended[row] if self._sieves_extended else self._sieves
                     off = 0
@@ -650,8 +672,8 @@ class FruitSlice:
                             continue
                         if not sv.requires_fitting:
                             sv._get_unfitted_quantiles()
-                        quant[k, off:off + len(sv._q)] = sv._quantiles
-                        off += len(sv._q)
+                        quant[k, off:off + _n_thresholds(sv)] = sv._quantiles
+                        off += _n_thresholds(sv)
                 pipe.set_quantiles(quant)
                 pipe._cut_columns = [(slot0, sv) for slot0, sv in cut_columns.values()]
                 pipe._cut_slots = n_slots
@@ -675,6 +697,11 @@ class FruitSlice:
             sv, kind, inc, _ = _reduced(sv)
             if kind == nat.FR_SIEVE_END:
                 inc = 0
+            if kind in (nat.FR_SIEVE_PPV, nat.FR_SIEVE_CPV):
+                # (the whole row itself; the thresholds in the sieve's own order)
+                specs.append((kind | (nat.FR_SIEVE_SEGMENTS if sv._segments else 0), 0,
+                              np.array([0, T], dtype=np.int64), _n_thresholds(sv)))
+                continue
             if sv._has_float_cuts():
                 cuts_key = (tuple(sv._cut), sv._coquantile_norm)
                 if cuts_key not in cut_columns:

@@ -83,7 +83,9 @@ class _SieveWrapper(FeatureSieve):
         leaf, kind, order, fit_order = inner
         # END reads values, LPI is not fused; the inner sieve's float cuts are coquantiles of the
         # wrapped rows, which no fused launch forms
-        if kind in (nat.FR_SIEVE_END, nat.FR_SIEVE_LPI) or leaf._has_float_cuts():
+        # (no wrappers around PPV / CPV either: such a slice materialises)
+        if kind in (nat.FR_SIEVE_END, nat.FR_SIEVE_LPI, nat.FR_SIEVE_PPV, nat.FR_SIEVE_CPV) \
+                or leaf._has_float_cuts():
             return None
         # increments of increments and sums of sums compose exactly; cumulating increments (or
         # the other way round) is not the identity in floating point

@@ -106,6 +106,13 @@ extern "C" {
 #define FR_SIEVE_LPI 6 /* fruits/sieving/increment.py:201-239 */
 #define FR_SIEVE_CUR 7 /* fruits/sieving/segment.py:228-272: sum of v*v over the in-band elements of the
                           inc-times differenced row (CUR itself: inc = 2); AVG / STD return the same */
+/* the sieves of fruits/sieving/implicit.py: numbers of their own, valid in fr_sieve_implicit and
+ * fr_pipeline_create only (fr_sieve knows neither) */
+#define FR_SIEVE_PPV 16 /* fruits/sieving/implicit.py:11-153  */
+#define FR_SIEVE_CPV 17 /* fruits/sieving/implicit.py:156-213 */
+/* OR-ed into FR_SIEVE_PPV / FR_SIEVE_CPV at fr_pipeline_create: the `segments` form, Q1 - 1
+ * bands q_j <= v < q_(j+1) instead of Q1 tests v >= q_j */
+#define FR_SIEVE_SEGMENTS 0x200
 /* OR-ed into a sieve's kind at fr_pipeline_create: its cuts are PER SERIES (coquantile
  * cuts, fruits/sieving/segment.py:51-64) - the sieve's `cuts` entries then name columns
  * ("slots") of the table given to fr_pipeline_set_series_cuts */
@@ -281,12 +288,34 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
              const double *d_q, int32_t Q1, double *d_out, int64_t out_stride,
              void *stream);
 
+/* Replaces PPV._transform and CPV._transform (fruits/sieving/implicit.py:114-129, 169-190) on a
+ * materialised (N, T) iterated sum: one pass over a row for all thresholds of the sieve.  The
+ * indicator is closed BELOW - v >= q_j, or with `segments` q_j <= v < q_(j+1), evaluated per
+ * element (the thresholds are taken as given, not sorted: a band with q_j > q_(j+1) is empty); a
+ * NaN never counts, +inf counts against a finite threshold.  FR_SIEVE_PPV: count / T.
+ * FR_SIEVE_CPV: 2 * (rising edges of the indicator at t >= 1) / n, n = T rounded up to even (the
+ * first difference is zero-padded, fruits/cache.py:8-13: a component that starts at t = 0 is not
+ * counted).  The counts are integers; the one division is correctly rounded.
+ *
+ *   kind     FR_SIEVE_PPV or FR_SIEVE_CPV (fr_sieve knows neither)
+ *   d_A      (N, T) f64, row stride a_stride elements
+ *   d_q      (Q) f64 thresholds in the sieve's order (implicit.py:99-112), Q >= 1
+ *   segments 0: Q features; else Q - 1 (Q >= 2); at most 256 features (FR_E_LIMIT)
+ *   d_out    feature (n, j) at d_out[n*out_stride + j]
+ */
+int fr_sieve_implicit(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride,
+                      const double *d_q, int32_t Q, int32_t segments, double *d_out,
+                      int64_t out_stride, void *stream);
+
 /* ------------------------------------------------------------------ fused pipeline
  * ISS + sieves in ONE launch: replaces the loop of FruitSlice.transform
  * (fruits/fruit.py:538-550) - for every iterated sum, for every sieve,
  * sieve.transform(itsum) - without ever materialising the (K, N, T) tensor.
  * Sieves: NPI / MPI / XPI / CUR and MAX / MIN with inc -8 to 8, and END; integer cuts or
- * per-series cuts (FR_SIEVE_SERIES_CUTS).  LPI is not fused (FR_E_LIMIT).  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
+ * per-series cuts (FR_SIEVE_SERIES_CUTS).  LPI is not fused (FR_E_LIMIT).  FR_SIEVE_PPV /
+ * FR_SIEVE_CPV (| FR_SIEVE_SEGMENTS): inc 0, C1 = 2 with the cuts {0, T}, Q1 = the number of
+ * thresholds (>= 1; with segments >= 2), which h_quant holds in the SIEVE's order - they are not
+ * sorted; Q1 features, Q1 - 1 with segments, as fr_sieve_implicit computes them.  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
  * column order (iterated sum, then sieve, then segment, then band).
  *
  *   kinds/incs/C1/Q1   per sieve; Q1 is ignored for END
@@ -296,7 +325,7 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
  *                      [-T, T-1] fails with FR_E_INDEX (the reference raises IndexError)
  *   h_quant            HOST (K, q_stride) thresholds of every iterated sum (the fitted
  *                      sieve copies of fruit.py:484-496), q_stride =
- *                      fr_pipeline_info(p, 1) = sum of Q1 over the band sieves (all but END);
+ *                      fr_pipeline_info(p, 1) = sum of Q1 over all sieves but END;
  *                      fr_pipeline_set_quantiles resolves them with the cuts into a
  *                      device table of per-row feature ops (call once after fit; it
  *                      allocates and synchronises)
