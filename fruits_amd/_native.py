@@ -46,7 +46,9 @@ EXPORTS = [
     "fr_coswiss_set_input_stride", "fr_coswiss_ffn",
     "fr_prep_fir", "fr_prep_project", "fr_prep_normalize", "fr_prep_leadlag",
     "fr_prep_mask", "fr_prep_pointwise",
+    "fr_letter_rows", "fr_rows_unshift",
 ]
+FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
 FR_PW_FLAG_SIN = FR_PW_FLAG_LOWER = 1
 
@@ -1073,4 +1075,52 @@ def prep_pointwise(mode: int, Xd, w_d=None, w2_d=None, shift: int = 0, q: float 
                                   C.c_int64(int(shift)), C.c_double(float(q)), C.c_double(float(v)),
                                   C.c_int32(int(flags)), dptr(out), stream_ptr()),
           "fr_prep_pointwise")
+    return out
+
+
+# ----------------------------------------------------------------------- generic words
+def letter_rows(Xd, spec, ext_d=None, one_is_zero: bool = False, out=None, spec_d=None):
+    """fr_letter_rows: the ``(N, Dv, T)`` virtual input rows of lowered generic words
+    (fruits_amd/iss/lowering.py).  ``spec``: ``(Dv, 3)`` int32 host array of
+    ``(kind, source, shift)``, kinds ``FR_ROW_*``; ``ext_d``: ``(N, H, T)`` device tensor of the
+    values the Python letters gave, for the ``FR_ROW_EXT`` rows; ``spec_d``: the device copy of
+    ``spec`` if the caller keeps one (else it is uploaded here)."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    sp = np.ascontiguousarray(spec, dtype=np.int32)
+    if sp.ndim != 2 or sp.shape[1] != 3 or sp.shape[0] < 1:
+        raise ValueError("the row specification must be (Dv, 3) int32")
+    H = 0
+    if ext_d is not None:
+        if ext_d.dtype != t.float64 or ext_d.dim() != 3 or not ext_d.is_contiguous() \
+                or int(ext_d.shape[0]) != N or int(ext_d.shape[2]) != T:
+            raise TypeError("letter values must be a contiguous float64 (N, H, T) device tensor")
+        H = int(ext_d.shape[1])
+    out = _prep_out(out, (N, sp.shape[0], T), Xd)
+    sp_d = spec_d if spec_d is not None else t.from_numpy(sp).to(Xd.device)
+    if sp_d.dtype != t.int32 or tuple(sp_d.shape) != sp.shape or not sp_d.is_contiguous():
+        raise TypeError("the device copy of the row specification must be (Dv, 3) int32")
+    check(lib().fr_letter_rows(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
+                               dptr(ext_d if H else None), C.c_int64(H), dptr(sp_d), _i32p(sp),
+                               C.c_int32(sp.shape[0]), C.c_int32(1 if one_is_zero else 0),
+                               dptr(out), stream_ptr()), "fr_letter_rows")
+    return out
+
+
+def rows_unshift(Ad, shifts, out=None, shifts_d=None):
+    """fr_rows_unshift: ``out[k, n, t] = A[k, n, t - shifts[k]]`` for ``t >= shifts[k]``, +0.0
+    in front; ``Ad`` ``(K, N, T)``, ``out`` a distinct buffer of the same shape."""
+    t = torch()
+    if Ad.dtype != t.float64 or Ad.dim() != 3 or not Ad.is_contiguous():
+        raise TypeError("A must be a contiguous float64 (K, N, T) device tensor")
+    K, N, T = (int(v) for v in Ad.shape)
+    sh = np.ascontiguousarray(shifts, dtype=np.int32)
+    if sh.shape != (K,):
+        raise ValueError("one shift per row")
+    out = _prep_out(out, (K, N, T), Ad)
+    sh_d = shifts_d if shifts_d is not None else t.from_numpy(sh).to(Ad.device)
+    if sh_d.dtype != t.int32 or tuple(sh_d.shape) != (K,) or not sh_d.is_contiguous():
+        raise TypeError("the device copy of the shifts must be (K) int32")
+    check(lib().fr_rows_unshift(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(sh_d),
+                                _i32p(sh), dptr(out), stream_ptr()), "fr_rows_unshift")
     return out

@@ -39,7 +39,9 @@ def units():
            # the sums of RIN / MAV / JLD / FFN round every product like the reference
            ("kernels_prep", "kernels_prep.hip", ["-ffp-contract=off"]),
            # the time masks and pointwise maps: RPE rounds both products of a rotation
-           ("kernels_filter", "kernels_filter.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
+           ("kernels_filter", "kernels_filter.hip", ["-ffp-contract=off"]),
+           # the virtual rows of generic words: moves and fabs, compared bit for bit
+           ("kernels_letters", "kernels_letters.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
            ("jit", "jit.cpp", []),
            # (the registry also holds the mixed kernels of the one-group programs and their
            # tail programs: no contraction, like the programs' own units below)

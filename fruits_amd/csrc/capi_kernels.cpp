@@ -330,4 +330,55 @@ int fr_prep_pointwise(int32_t mode, const double *d_X, int64_t Nx, int64_t D, in
   return launched(e, "prep pointwise launch", "fr_prep_pointwise: grid too large");
 }
 
+// ---------------------------------------------------------------- generic words (kernels_letters.hip)
+namespace {
+// whether the doubles [a, a + na) and [b, b + nb) share an address
+bool overlap(const double *a, int64_t na, const double *b, int64_t nb) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + (uintptr_t)nb * sizeof(double) && pb < pa + (uintptr_t)na * sizeof(double);
+}
+}  // namespace
+
+int fr_letter_rows(const double *d_X, int64_t N, int64_t D, int64_t T, const double *d_ext,
+                   int64_t H, const int32_t *d_spec, const int32_t *h_spec, int32_t Dv,
+                   int32_t one_is_zero, double *d_out, void *stream) {
+  if (N < 0 || D < 1 || T < 1 || H < 0 || Dv < 1) return fail(FR_E_ARG, "fr_letter_rows: bad shape");
+  if (!h_spec) return fail(FR_E_ARG, "fr_letter_rows: null host table");
+  for (int32_t r = 0; r < Dv; ++r) {
+    const int32_t kind = h_spec[3 * r], source = h_spec[3 * r + 1], shift = h_spec[3 * r + 2];
+    const std::string row = "fr_letter_rows: row " + std::to_string(r);
+    if (kind < FR_ROW_DIM || kind > FR_ROW_ONE) return fail(FR_E_ARG, row + " has an unknown kind");
+    if (shift < 0) return fail(FR_E_ARG, row + " has a negative shift");
+    if (kind == FR_ROW_ONE) continue;
+    if (kind == FR_ROW_EXT && (!d_ext || H == 0))
+      return fail(FR_E_ARG, row + " reads letter values but there are none");
+    const int64_t limit = kind == FR_ROW_EXT ? H : D;
+    if (source < 0 || source >= limit)
+      return fail(FR_E_DIM, row + " names source " + std::to_string(source) + " of " +
+                                std::to_string(limit));
+  }
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || !d_spec) return fail(FR_E_ARG, "fr_letter_rows: null or aliased device pointer");
+  if (overlap(d_X, N * D * T, d_out, N * Dv * T) ||
+      (d_ext && H > 0 && overlap(d_ext, N * H * T, d_out, N * Dv * T)))
+    return fail(FR_E_ARG, "fr_letter_rows: null or aliased device pointer");
+  hipError_t e = fr::launch_letter_rows(d_X, N, D, T, d_ext, H, d_spec, Dv, one_is_zero ? 0.0 : 1.0,
+                                        d_out, (hipStream_t)stream);
+  return launched(e, "letter rows launch", "fr_letter_rows: grid too large");
+}
+
+int fr_rows_unshift(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_shift,
+                    const int32_t *h_shift, double *d_out, void *stream) {
+  if (K < 0 || N < 0 || T < 1) return fail(FR_E_ARG, "fr_rows_unshift: bad shape");
+  if (K > 0 && !h_shift) return fail(FR_E_ARG, "fr_rows_unshift: null host table");
+  for (int64_t k = 0; k < K; ++k)
+    if (h_shift[k] < 0)
+      return fail(FR_E_ARG, "fr_rows_unshift: row " + std::to_string(k) + " has a negative shift");
+  if (K == 0 || N == 0) return FR_OK;
+  if (!d_A || !d_out || !d_shift || overlap(d_A, K * N * T, d_out, K * N * T))
+    return fail(FR_E_ARG, "fr_rows_unshift: null or aliased device pointer");
+  hipError_t e = fr::launch_rows_unshift(d_A, K, N, T, d_shift, d_out, (hipStream_t)stream);
+  return launched(e, "rows unshift launch", "fr_rows_unshift: grid too large");
+}
+
 }  // extern "C"

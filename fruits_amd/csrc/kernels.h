@@ -120,5 +120,13 @@ struct PointwiseArgs {
 hipError_t launch_prep_mask(const double *X, int64_t N, int64_t D, int64_t T, const uint32_t *mask,
                             const int64_t *cs, const int64_t *ce, double *out, hipStream_t st);
 hipError_t launch_prep_pointwise(int mode, const PointwiseArgs &a, int64_t N, hipStream_t st);
+// the virtual input rows of lowered generic words and the output unshift (kernels_letters.hip);
+// `spec` = device (Dv, 3) int32 {kind, source, shift}, kinds = FR_ROW_* in fruits_hip.h;
+// hipErrorInvalidValue: a grid limit
+hipError_t launch_letter_rows(const double *X, int64_t N, int64_t D, int64_t T, const double *ext,
+                              int64_t H, const int32_t *spec, int Dv, double one, double *out,
+                              hipStream_t st);
+hipError_t launch_rows_unshift(const double *A, int64_t K, int64_t N, int64_t T,
+                               const int32_t *shift, double *out, hipStream_t st);
 
 }  // namespace fr

@@ -603,7 +603,7 @@ class FruitSlice:
                 return False     # (cumulated rows: series of one time chunk; the pipeline says if not)
         return True
 
-    def _fused(self, T: int, indices=None, chain_row: int = 0):
+    def _fused(self, T: int, indices=None, chain_row: int = 0, D: Optional[int] = None):
         """The fused pipeline for series length T (thresholds of the fitted sieve
         copies already resolved), or None when a sieve or the weighting is outside
         the fused set; cached until the next fit.  ``indices``: only these words
@@ -614,6 +614,20 @@ class FruitSlice:
         key = T if indices is None else (T, tuple(indices))
         if chain_row:
             key = (key, chain_row)
+        # Generic words (iss/lowering.py): the plan runs on virtual rows formed from the prepared
+        # (N, D, T) input, so the pipeline belongs to that D.  Fused are a single ISS over Reals
+        # or Arctic (no output unshift) whose weighting, if any, meets generic words only;
+        # everything else - Bayesian, whose rows come out time-shifted, chains that end in
+        # generic words, generic next to weighted simple words - materialises through
+        # ISS.transform_device.
+        generic = bool(self._iss) and getattr(self._iss[-1], "_has_generic", False)
+        if generic:
+            iss = self._iss[-1]
+            used = range(len(iss.words)) if indices is None else indices
+            if (D is None or len(self._iss) != 1 or iss.needs_unshift() or getattr(iss, "_argmax", False)
+                    or (iss.weighting is not None and len(iss._class_runs(used)) > 1)):
+                return None
+            key = (key, "D", int(D))
         if key in self._fused_cache:
             return self._fused_cache[key]
         entry = None
@@ -626,12 +640,13 @@ class FruitSlice:
             if getattr(iss, "_argmax", False):   # (the pipeline's rows are the argmax rows, not the plan's)
                 argmax = [len(iss.words[i]) for i in (range(len(iss.words)) if indices is None else indices)]
             if indices is None:
-                plan = iss._plan(0, len(iss.words))
+                plan = (iss._plan_indices(range(len(iss.words)), D=D) if generic
+                        else iss._plan(0, len(iss.words)))
                 rows = range(plan.rows if argmax is None else iss._rows_of(0, len(iss.words)))
                 if hasattr(iss, "_arm_plan"):
                     iss._arm_plan(plan, tuple(range(len(iss.words))), T)
             else:
-                plan = iss._plan_indices(indices)
+                plan = iss._plan_indices(indices, D=D) if generic else iss._plan_indices(indices)
                 if hasattr(iss, "_arm_plan"):
                     iss._arm_plan(plan, tuple(indices), T)
                 first = np.concatenate([[0], np.cumsum(
@@ -896,16 +911,24 @@ class FruitSlice:
         self._attach(cache)
         if ffn and not callbacks and self._fusable():
             return self._transform_ffn_fused(Pd, cache)
-        fused = None if callbacks else self._fused(int(Pd.shape[2]))
+        fused = None if callbacks else self._fused(int(Pd.shape[2]), D=int(Pd.shape[1]))
         if fused is not None and len(self._iss) > 1:
             return self._transform_chain_fused(Pd, cache)
         if fused is not None:
+            Vd, iss = Pd, self._iss[0]
+            if getattr(iss, "_has_generic", False):
+                # generic words over Reals / Arctic: still ONE walk + sieve launch, on the virtual rows
+                # formed from the prepared input (no in-launch preparation)
+                low, _ = iss._lowered(range(len(iss.words)), int(Pd.shape[1]))
+                Vd = iss.virtual_rows(Pd, low)
             if fused.raw_dims > 0:       # (was configured for raw input by another call)
-                fused.set_preparation(int(Pd.shape[1]))
+                fused.set_preparation(int(Vd.shape[1]))
                 fused._prep_chain = None
             self._arm_series_cuts(fused, int(Pd.shape[0]), int(Pd.shape[2]), cache)
             self._auto_prepare(fused, int(Pd.shape[0]), int(Pd.shape[2]))
-            return fused.run(Pd, self._iss[0].lookup_device(Pd))
+            # (an unweighted plan - every lowered one - takes no lookup: none is computed)
+            weighted = fused.plan.weighting != nat.FR_W_NONE
+            return fused.run(Vd, iss.lookup_device(Pd) if weighted else None)
         feats = t.zeros((X.shape[0], self.nfeatures()), dtype=t.float64, device=Pd.device)
         col = 0
         for i, itsum in enumerate(self._iterate_iss_device(Pd)):

@@ -6,6 +6,14 @@ in Python and calls one numba kernel per word (fruits/iss/iss.py:49-65), this
 stage compiles the whole word list into ONE device program (a prefix trie in DFS
 order, csrc/plan.cpp) and walks it in one HIP launch; the result has the
 reference's row order and layout (iss.py:46).
+
+Generic words - ``Word``s of named letter functions, which the reference sends down its slow
+path (fruits/iss/semiring.py:54-75) - run through the same program: ``lowering.py`` rewrites
+them as exponent tables over virtual input rows, ``fr_letter_rows`` forms those rows.  ``DIM``
+and ``ABS`` letters are formed on the device; any other letter is a Python callable, so its
+values are computed on the host - the batch is downloaded once, ``letter(Z[i])`` is evaluated
+per series and distinct (letter, dimension), the values are uploaded: the same round trip as
+the ``FUN`` preparateur.  The weighting is ignored for generic words, as in the reference.
 """
 from __future__ import annotations
 
@@ -18,12 +26,13 @@ import numpy as np
 from .. import _native as nat
 from ..cache import SharedSeedCache
 from ..seed import Seed
+from . import lowering
 from .cache import CachePlan
 from .semiring import Arctic, Bayesian, Reals, Semiring
 
 _AUTO_PREPARE_BYTES = 64 << 20   # materialised output from which a plan is prepared unasked
 from .weighting import Weighting
-from .words.word import SimpleWord, Word
+from .words.word import Word
 
 
 class ISSMode(Enum):
@@ -47,6 +56,7 @@ class ISS(Seed):
         self.semiring = semiring if semiring is not None else Reals()
         self._cache_plan = CachePlan(self.words if mode == ISSMode.EXTENDED else [])
         self.weighting = weighting
+        self._generic: Optional[bool] = None
         self._fresh_transients()
 
     def _fresh_transients(self) -> None:
@@ -85,19 +95,139 @@ class ISS(Seed):
             raise NotImplementedError(
                 f"semiring {type(self.semiring).__name__} is not on the MI355X hot path")
         for w in self.words:
-            if not isinstance(w, SimpleWord):
-                raise NotImplementedError(
-                    "only SimpleWord is supported by the MI355X implementation")
+            if not isinstance(w, Word):
+                raise TypeError(f"an ISS takes words, not {type(w).__name__}")
+        if self._argmax and self._has_generic:
+            # the reference's slow path returns one row per prefix, which its argmax layout of
+            # L + L(L+1)/2 rows per word cannot take (fruits/iss/iss.py:37-65): it fails there too
+            raise NotImplementedError(
+                "Arctic(argmax=True) is defined for SimpleWord only: the reference's slow path "
+                "for generic words returns no positions of the maxima")
+
+    @property
+    def _has_generic(self) -> bool:
+        # (decided once, like the cache plan: a word list of simple words pays nothing per call)
+        if getattr(self, "_generic", None) is None:
+            self._generic = any(lowering.is_generic(w) for w in self.words)
+        return self._generic
+
+    def _generic_in(self, indices) -> bool:
+        return any(lowering.is_generic(self.words[i]) for i in indices)
 
     def _plan(self, start: int, stop: int) -> nat.Plan:
         return self._plan_indices(tuple(range(start, stop)))
 
-    def _plan_indices(self, indices) -> nat.Plan:
+    def _lowered(self, indices, D: int):
+        """(lowering, device program) of a subset that holds generic words, for inputs of ``D``
+        dimensions: the words as exponent tables over virtual rows (lowering.py), compiled like
+        any other plan.  Lowered plans are unweighted - the reference ignores the weighting for
+        generic words (fruits/iss/semiring.py:40) - so a weighted ISS lowers subsets of generic
+        words only (``_class_runs``)."""
+        indices = tuple(indices)
+        arctic = isinstance(self.semiring, Arctic)
+        bayesian = isinstance(self.semiring, Bayesian)
+        # The lowering and its plan are kept together, found by what the row specification is a
+        # function of: the words (their strings name every letter and dimension), the semiring
+        # and D.  The entry itself holds the row specification (and its device copy).
+        key = ("lowered", indices, self.mode, arctic, bayesian, int(D),
+               tuple(str(self.words[i]) for i in indices))
+        entry = self._plans.get(key)
+        if entry is None:
+            depths = [self._depth(i) for i in indices]
+            low = lowering.lower([self.words[i] for i in indices], self.semiring, int(D), depths)
+            plan = nat.Plan(low.tables, depths, None, nat.FR_W_NONE, arctic=arctic,
+                            bayesian=bayesian)
+            entry = self._plans[key] = (low, plan)
+        return entry
+
+    def _class_runs(self, indices):
+        """``indices`` cut into maximal runs of words of one class (generic / simple).  A
+        weighted ISS runs them as separate plans into slices of one output: the simple words
+        weighted on the input itself, exactly as without generic neighbours, the generic ones
+        unweighted on their virtual rows.  (The alternative, one plan with ``alpha = 0`` for
+        the generic words, stages the exp tables of the simple words next to the virtual rows
+        of the generic ones: two smaller plans fit a workgroup's LDS more often.)"""
+        runs = []
+        for i in indices:
+            g = lowering.is_generic(self.words[i])
+            if runs and runs[-1][0] == g:
+                runs[-1][1].append(i)
+            else:
+                runs.append((g, [i]))
+        return [tuple(r) for _, r in runs]
+
+    def needs_unshift(self) -> bool:
+        """Whether rows of this ISS come out of the walk time-shifted (generic words under
+        Bayesian): such an ISS materialises, it cannot feed fused sieves."""
+        return self._has_generic and isinstance(self.semiring, Bayesian)
+
+    def virtual_rows(self, Xd, low, host=None):
+        """The ``(N, Dv, T)`` input of a lowered plan (fr_letter_rows).  Letters other than DIM
+        and ABS are Python callables: the batch is downloaded ONCE (``host``: a list that keeps
+        the copy for the other plans of the same call), ``letter(Z[i])`` is evaluated per series
+        and distinct (letter, dimension) on the host, and the values are uploaded - the same
+        documented round trip as FUN."""
+        ext_d = None
+        if low.ext:
+            host = [] if host is None else host
+            if not host:
+                host.append(nat.to_host(Xd))
+            ext_d = nat.to_device(lowering.letter_values(low, host[0]))
+        return nat.letter_rows(Xd, low.spec, ext_d, one_is_zero=low.one_is_zero,
+                               spec_d=low.device_tables(Xd.device)[0])
+
+    def _transform_lowered(self, Xd, indices, lookup_d, out, groups: int, host=None):
+        t = nat.torch()
+        N, D, T = (int(v) for v in Xd.shape)
+        K = sum(self._depth(i) for i in indices)
+        if out is None:
+            out = t.empty((K, N, T), dtype=t.float64, device=Xd.device)
+        runs = self._class_runs(indices)
+        if self.weighting is not None and len(runs) > 1:
+            host = [] if host is None else host
+            k0 = 0
+            for run in runs:
+                k1 = k0 + sum(self._depth(i) for i in run)
+                if self._generic_in(run):
+                    self._transform_lowered(Xd, run, lookup_d, out[k0:k1], groups, host)
+                else:
+                    self.transform_device(Xd, lookup_d=lookup_d, out=out[k0:k1], groups=groups,
+                                          indices=run)
+                k0 = k1
+            return out
+        low, plan = self._lowered(indices, D)
+        if not plan.fits(T):
+            if len(indices) == 1:
+                raise NotImplementedError(
+                    f"word {self.words[indices[0]]} alone needs {plan.staged_rows} staged rows: "
+                    "more than the LDS of a workgroup holds")
+            host = [] if host is None else host
+            half = len(indices) // 2
+            k0 = sum(self._depth(i) for i in indices[:half])
+            for part, dst in ((indices[:half], out[:k0]), (indices[half:], out[k0:])):
+                if self._generic_in(part):
+                    self._transform_lowered(Xd, part, lookup_d, dst, groups, host)
+                else:
+                    self.transform_device(Xd, lookup_d=lookup_d, out=dst, groups=groups,
+                                          indices=part)
+            return out
+        V = self.virtual_rows(Xd, low, host)
+        if not low.shifted:
+            return plan.run(V, None, out=out, layout="KNT", groups=groups)
+        return nat.rows_unshift(plan.run(V, None, layout="KNT", groups=groups), low.out_shifts,
+                                out=out, shifts_d=low.device_tables(Xd.device)[1])
+
+    def _plan_indices(self, indices, D: Optional[int] = None) -> nat.Plan:
         """Device program of an arbitrary subset of the words (in the given
         order).  Output depths come from the cache plan of the FULL word list, so
         shards of a word list (fruits_amd.parallel) emit exactly their share of
-        the rows."""
+        the rows.  A subset that holds generic words is lowered for inputs of ``D``
+        dimensions (``_lowered``)."""
         indices = tuple(indices)
+        if self._has_generic and self._generic_in(indices):
+            if D is None:
+                raise ValueError("the plan of generic words depends on the input's dimensions")
+            return self._lowered(indices, D)[1]
         if self.weighting is None:
             wmode, alphas = nat.FR_W_NONE, None
         else:
@@ -184,6 +314,14 @@ class ISS(Seed):
                 out.copy_(res)
                 return out
             return res
+        if self._has_generic:
+            idx = tuple(range(start, stop)) if indices is None else tuple(indices)
+            if self._generic_in(idx):
+                if isinstance(lookup_d, str):
+                    lookup_d = self.lookup_device(Xd) if len(self._class_runs(idx)) > 1 else None
+                if out is not None and not out.is_contiguous():
+                    raise TypeError("out must be contiguous")
+                return self._transform_lowered(Xd, idx, lookup_d, out, groups)
         plan = self._plan(start, stop) if indices is None else self._plan_indices(indices)
         if plan.max_dim > Xd.shape[1]:
             raise IndexError(

@@ -4,7 +4,10 @@ from __future__ import annotations
 import itertools
 from collections.abc import Sequence
 
-from .word import SimpleWord
+import numpy as np
+
+from .letters import ExtendedLetter
+from .word import SimpleWord, Word
 
 
 def _compositions_seed(n: int, smallest: int = 1):
@@ -54,6 +57,16 @@ def alternate_sign(words: Sequence[SimpleWord]) -> list[SimpleWord]:
     return out
 
 
-def replace_letters(word, letter_gen):
-    raise NotImplementedError(
-        "named letter functions are outside the MI355X hot path (SimpleWord only)")
+def replace_letters(word: SimpleWord, letter_gen) -> Word:
+    """A generic word with every letter of the simple ``word`` replaced by the next name
+    ``letter_gen`` yields; once the iterator runs dry the remaining letters stay ``DIM``
+    (fruits/iss/words/creation.py:53-83)."""
+    names = iter(letter_gen)
+    out = Word()
+    for exponents in word.table():
+        el = ExtendedLetter()
+        # (one letter per unit of a positive exponent, dimensions in ascending order)
+        for dim in np.repeat(np.arange(exponents.size), np.maximum(exponents, 0)):
+            el.append(next(names, "DIM"), int(dim))
+        out.multiply(el)
+    return out

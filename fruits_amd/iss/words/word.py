@@ -1,10 +1,10 @@
 """Words of the iterated-sums signature (mirrors fruits/iss/words/word.py).
 
-Only :class:`SimpleWord` is on the MI355X hot path: a word whose letters pick
-single input dimensions, stored as an integer exponent table that crosses the
-C ABI as ``(L, Dw) int32``.  The generic :class:`Word` of named Python letter
-functions (fruits/iss/words/letters.py) cannot cross a C ABI and is out of
-scope; it exists here as the common base type only.
+A :class:`SimpleWord` is a word whose letters pick single input dimensions,
+stored as an integer exponent table that crosses the C ABI as ``(L, Dw) int32``.
+The generic :class:`Word` of named letter functions (letters.py) reaches the
+device through the same door: ``fruits_amd/iss/lowering.py`` rewrites it as an
+exponent table over virtual input rows, one per distinct ``(letter, dimension)``.
 """
 from __future__ import annotations
 
@@ -13,8 +13,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from .letters import ExtendedLetter
+
 _SIMPLE_WORD = re.compile(r"(\[(-?\d|\(-?\d+\))+\])+")
 _LETTER = re.compile(r"\((-?\d+)\)|(-?\d)")
+_BRACKETS = re.compile(r"\[([^\]]*)\]")     # the bodies of a generic word's extended letters
 
 
 class Word:
@@ -42,12 +45,24 @@ class Word:
         self._alpha = np.array(alpha, dtype=np.float32)
 
     def multiply(self, other) -> None:
-        raise NotImplementedError(
-            "generic words of named letter functions are not supported by the "
-            "MI355X implementation; use SimpleWord")
+        """Appends an extended letter, the extended letters of another word, or those of a
+        string like ``"[ABS(1)DIM(2)][ABS(1)]"`` - one extended letter per bracket pair, a
+        string without brackets names none."""
+        if isinstance(other, str):
+            new = [ExtendedLetter(body) for body in _BRACKETS.findall(other)]
+        elif isinstance(other, ExtendedLetter):
+            new = [other]
+        elif isinstance(other, Word):
+            new = list(other._extended_letters)
+        else:
+            raise TypeError(f"Cannot multiply Word with {type(other)}")
+        self._extended_letters.extend(new)
 
     def copy(self) -> "Word":
-        raise NotImplementedError
+        dup = Word()
+        for el in self._extended_letters:
+            dup.multiply(el.copy())
+        return dup
 
     def __len__(self) -> int:
         return len(self._extended_letters)

@@ -614,6 +614,37 @@ int fr_prep_pointwise(int32_t mode, const double *d_X, int64_t Nx, int64_t D, in
                       const double *d_w, int64_t Nw, const double *d_w2, int64_t shift, double q,
                       double v, int32_t flags, double *d_out, void *stream);
 
+/* ------------------------------------------------------------------ generic words
+ * A generic word (fruits/iss/words/word.py, Word: extended letters of named letter functions)
+ * is lowered on the host to an ordinary exponent table over VIRTUAL input rows
+ * (fruits_amd/iss/lowering.py); these two entries form those rows and undo the time shift the
+ * lowering gives the max-plus / max-times semirings.  Both only move data and take fabs.
+ *
+ * fr_letter_rows: d_out (N, Dv, T) with, for row r = (kind, source, shift) of the table,
+ *   out[n,r,t] = f(src[n,source,t + shift])  where t + shift < T,  +0.0 past the end;
+ *   FR_ROW_DIM: f = identity on d_X (N, D, T);  FR_ROW_ABS: f = fabs on d_X;
+ *   FR_ROW_EXT: f = identity on d_ext (N, H, T), values a letter function gave on the host;
+ *   FR_ROW_ONE: f = 1.0, or 0.0 with one_is_zero != 0 (the semiring's one of an empty extended
+ *     letter); `source` is ignored.
+ * The table is (Dv, 3) int32, given twice like the tables of fr_prep_fir: h_spec on the host
+ * (every entry is checked: FR_E_ARG for an unknown kind, a negative shift or an EXT row without
+ * d_ext, FR_E_DIM for a source outside its tensor) and d_spec, the copy the kernel reads.
+ * d_out must not alias d_X or d_ext. */
+#define FR_ROW_DIM 0
+#define FR_ROW_ABS 1
+#define FR_ROW_EXT 2
+#define FR_ROW_ONE 3
+int fr_letter_rows(const double *d_X, int64_t N, int64_t D, int64_t T, const double *d_ext,
+                   int64_t H, const int32_t *d_spec, const int32_t *h_spec, int32_t Dv,
+                   int32_t one_is_zero, double *d_out, void *stream);
+
+/* fr_rows_unshift: d_A (K, N, T) -> d_out (K, N, T), a distinct buffer, with
+ *   out[k,n,t] = t >= s_k ? A[k,n,t - s_k] : +0.0;
+ * s_k >= 0 per row k (h_shift on the host, checked; d_shift the device copy), s_k >= T gives an
+ * all-zero row.  FR_E_ARG when the two buffers overlap. */
+int fr_rows_unshift(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_shift,
+                    const int32_t *h_shift, double *d_out, void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest
