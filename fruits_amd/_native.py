@@ -47,6 +47,7 @@ EXPORTS = [
     "fr_prep_fir", "fr_prep_project", "fr_prep_normalize", "fr_prep_leadlag",
     "fr_prep_mask", "fr_prep_pointwise",
     "fr_letter_rows", "fr_rows_unshift",
+    "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -112,6 +113,7 @@ def lib():
     L.fr_pipeline_compile_plan.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     L.fr_pipeline_prepare_cached.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     L.fr_pipeline_set_series_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    L.fr_pipeline_set_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.fr_pipeline_set_argmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.fr_select_ranks_begin.restype = C.c_void_p
     L.fr_select_ranks_end.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -583,6 +585,20 @@ class Pipeline:
               "fr_pipeline_set_series_cuts")
         self._series_cuts = table    # (keeps the tensor alive while the pipeline points at it)
 
+    def set_lengths(self, lengths) -> None:
+        """``lengths`` (N,) int32 device tensor: the per-series lengths of the following runs on
+        exactly N series (fr_pipeline_set_lengths); None: every series is T long again."""
+        t = torch()
+        if lengths is None:
+            check(lib().fr_pipeline_set_lengths(self._h, None, 0), "fr_pipeline_set_lengths")
+        else:
+            if lengths.dtype != t.int32 or lengths.dim() != 1 or not lengths.is_contiguous():
+                raise TypeError("the lengths must be a contiguous int32 (N,) device tensor")
+            check(lib().fr_pipeline_set_lengths(self._h, C.c_void_p(lengths.data_ptr()),
+                                                C.c_int64(lengths.shape[0])),
+                  "fr_pipeline_set_lengths")
+        self._lengths = lengths      # (keeps the tensor alive while the pipeline points at it)
+
     def set_preparation(self, D: int, inc_lag: int = 0, as_new: bool = False,
                         standardize: int = 0, std_eps: float = 1e-5) -> bool:
         """fr_pipeline_set_preparation: ``run`` then takes the RAW (N, D, T) input and forms
@@ -771,12 +787,22 @@ def sieve(kind: int, Ad, inc: int, cuts_d, q_d, out, out_col: int = 0):
     return out
 
 
-def sieve_implicit(kind: int, Ad, q_d, segments: bool, out, out_col: int = 0):
+def sieve_implicit(kind: int, Ad, q_d, segments: bool, out, out_col: int = 0, lengths_d=None):
     """Writes the features of a PPV / CPV sieve (fr_sieve_implicit) on a (N, T) device array
     into columns [out_col, out_col + nfeatures) of the (N, F) device tensor ``out``; ``q_d``
-    holds the sieve's thresholds in its own order."""
+    holds the sieve's thresholds in its own order.  ``lengths_d``: (N,) int32 device tensor,
+    series n is its first ``lengths_d[n]`` elements (fr_sieve_implicit_lengths)."""
     N, T = Ad.shape
     base = out.data_ptr() + 8 * out_col
+    if lengths_d is not None:
+        _check_lengths_d(lengths_d, N)
+        rc = lib().fr_sieve_implicit_lengths(
+            C.c_int32(kind), dptr(Ad), C.c_int64(N), C.c_int64(T), C.c_int64(Ad.stride(0)),
+            dptr(lengths_d), dptr(q_d), C.c_int32(int(q_d.numel())),
+            C.c_int32(1 if segments else 0), C.c_void_p(base), C.c_int64(out.stride(0)),
+            stream_ptr())
+        check(rc, "fr_sieve_implicit_lengths")
+        return out
     rc = lib().fr_sieve_implicit(C.c_int32(kind), dptr(Ad), C.c_int64(N), C.c_int64(T),
                                  C.c_int64(Ad.stride(0)), dptr(q_d), C.c_int32(int(q_d.numel())),
                                  C.c_int32(1 if segments else 0), C.c_void_p(base),
@@ -860,11 +886,30 @@ class Selection:
             pass
 
 
-def standardize(Xd, div_std: bool, eps: float):
+def _check_lengths_d(lengths_d, N: int) -> None:
+    if (lengths_d.dtype != torch().int32 or lengths_d.dim() != 1 or int(lengths_d.shape[0]) != N
+            or not lengths_d.is_contiguous()):
+        raise TypeError("the lengths must be a contiguous int32 (N,) device tensor")
+
+
+def standardize(Xd, div_std: bool, eps: float, lengths_d=None):
+    """STD per row; ``lengths_d``: (N,) int32 device tensor for an (N, D, T) ``Xd`` - the
+    statistics of series n are those of its first ``lengths_d[n]`` elements
+    (fr_standardize_lengths)."""
     t = torch()
     out = t.empty_like(Xd)
     T = Xd.shape[-1]
     rows = Xd.numel() // T if T else 0
+    if lengths_d is not None:
+        if Xd.dim() != 3 or not Xd.is_contiguous():
+            raise TypeError("X must be a contiguous (N, D, T) device tensor")
+        _check_lengths_d(lengths_d, int(Xd.shape[0]))
+        rc = lib().fr_standardize_lengths(dptr(Xd), C.c_int64(Xd.shape[0]), C.c_int64(Xd.shape[1]),
+                                          C.c_int64(T), dptr(lengths_d),
+                                          C.c_int32(1 if div_std else 0), C.c_double(eps),
+                                          dptr(out), stream_ptr())
+        check(rc, "fr_standardize_lengths")
+        return out
     rc = lib().fr_standardize(dptr(Xd), C.c_int64(rows), C.c_int64(T),
                               C.c_int32(1 if div_std else 0), C.c_double(eps), dptr(out),
                               stream_ptr())

@@ -80,7 +80,25 @@ int fr_sieve_implicit(int32_t kind, const double *d_A, int64_t N, int64_t T, int
     return fail(FR_E_LIMIT, "fr_sieve_implicit: at most 256 features per sieve");
   if (N == 0) return FR_OK;
   if (!d_A || !d_out) return fail(FR_E_ARG, "fr_sieve_implicit: null device pointer");
-  hipError_t e = fr::launch_sieve_implicit(kind, d_A, N, T, a_stride, d_q, Q, segments ? 1 : 0,
+  hipError_t e = fr::launch_sieve_implicit(kind, d_A, N, T, a_stride, nullptr, d_q, Q, segments ? 1 : 0,
+                                           d_out, out_stride, (hipStream_t)stream);
+  return launched(e, "implicit sieve launch");
+}
+
+int fr_sieve_implicit_lengths(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride,
+                              const int32_t *d_lengths, const double *d_q, int32_t Q, int32_t segments,
+                              double *d_out, int64_t out_stride, void *stream) {
+  if (kind != FR_SIEVE_PPV && kind != FR_SIEVE_CPV)
+    return fail(FR_E_ARG, "fr_sieve_implicit_lengths: unknown kind");
+  if (N < 0 || T < 1 || N > 0x7fffffffLL || T > 0x7fffffffLL)
+    return fail(FR_E_ARG, "fr_sieve_implicit_lengths: bad shape");
+  if (Q < 1 || (segments && Q < 2) || !d_q)
+    return fail(FR_E_ARG, "fr_sieve_implicit_lengths: bad quantiles");
+  if (Q - (segments ? 1 : 0) > fr::kImplicitMaxFeatures)
+    return fail(FR_E_LIMIT, "fr_sieve_implicit_lengths: at most 256 features per sieve");
+  if (N == 0) return FR_OK;
+  if (!d_A || !d_out || !d_lengths) return fail(FR_E_ARG, "fr_sieve_implicit_lengths: null device pointer");
+  hipError_t e = fr::launch_sieve_implicit(kind, d_A, N, T, a_stride, d_lengths, d_q, Q, segments ? 1 : 0,
                                            d_out, out_stride, (hipStream_t)stream);
   return launched(e, "implicit sieve launch");
 }
@@ -99,7 +117,17 @@ int fr_standardize(const double *d_X, int64_t rows, int64_t T, int32_t div_std, 
   if (rows < 0 || T < 0) return fail(FR_E_ARG, "fr_standardize: bad shape");
   if (rows == 0 || T == 0) return FR_OK;
   if (!d_X || !d_out) return fail(FR_E_ARG, "fr_standardize: null device pointer");
-  hipError_t e = fr::launch_standardize(d_X, rows, T, div_std, eps, d_out, (hipStream_t)stream);
+  hipError_t e = fr::launch_standardize(d_X, rows, T, nullptr, 1, div_std, eps, d_out, (hipStream_t)stream);
+  return launched(e, "standardize launch");
+}
+
+int fr_standardize_lengths(const double *d_X, int64_t N, int64_t D, int64_t T, const int32_t *d_lengths,
+                           int32_t div_std, double eps, double *d_out, void *stream) {
+  if (N < 0 || D < 1 || T < 1 || T > 0x7fffffffLL || N * D > 0x7fffffffLL)
+    return fail(FR_E_ARG, "fr_standardize_lengths: bad shape");
+  if (N == 0) return FR_OK;
+  if (!d_X || !d_out || !d_lengths) return fail(FR_E_ARG, "fr_standardize_lengths: null device pointer");
+  hipError_t e = fr::launch_standardize(d_X, N * D, T, d_lengths, D, div_std, eps, d_out, (hipStream_t)stream);
   return launched(e, "standardize launch");
 }
 

@@ -295,9 +295,11 @@ void build_pipeline_ops(fr_pipeline_t *pl, const double *h_quant, std::vector<fr
           // one op per feature: v >= q_b, or with segments q_b <= v < q_(b+1) - the thresholds as
           // fitted, not sorted (an empty band stays empty); the walk leaves the count
           const int nf = sv.Q1 - (sv.segments ? 1 : 0);
+          // (per-series cuts: `hi` is the slot that holds the series' own length)
           for (int b = 0; b < nf; ++b)
-            row.push_back(fr::FeatOp{sv.kind | (sv.segments ? fr::OPF_SEGMENTS : 0),
-                                     k * pl->per_sum + sv.col + b, 0, sv.cuts[1], q[b],
+            row.push_back(fr::FeatOp{sv.kind | (sv.segments ? fr::OPF_SEGMENTS : 0) |
+                                         (sv.series_cuts ? (1 << 16) : 0),
+                                     k * pl->per_sum + sv.col + b, sv.cuts[0], sv.cuts[1], q[b],
                                      sv.segments ? q[b + 1] : std::numeric_limits<double>::infinity()});
           continue;
         }
@@ -510,7 +512,8 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
       bad = "bad sieve " + std::to_string(i);
     else if (implicit) {
       // PPV / CPV (fruits/sieving/implicit.py): the whole row itself, thresholds in the sieve's order
-      if (sv.series_cuts || c1 != 2 || sv.inc != 0) bad = "PPV / CPV look at the whole row itself (cuts {0, T}, inc 0)";
+      // (with FR_SIEVE_SERIES_CUTS: of the series' first cut_row[slot 1] elements - its own length)
+      if (c1 != 2 || sv.inc != 0) bad = "PPV / CPV look at the whole row itself (cuts {0, T}, inc 0)";
       else if (sv.Q1 < (sv.segments ? 2 : 1)) bad = "PPV / CPV need >= 1 thresholds, >= 2 with segments";
       else if (sv.Q1 - (sv.segments ? 1 : 0) > fr::kImplicitMaxFeatures) {
         bad = "at most 256 features per PPV / CPV sieve";
@@ -559,8 +562,9 @@ fr_pipeline_t *fr_pipeline_create(fr_plan_t *plan, int32_t n_sieves, const int32
     }
     const int nf = sv.kind == FR_SIEVE_END ? c1 - 1
                    : implicit ? sv.Q1 - (sv.segments ? 1 : 0) : (c1 - 1) * (sv.Q1 - 1);
-    if (implicit) {   // (the cuts given are not looked at: the whole series)
-      sv.cuts = {0, (int32_t)(T > 0x7fffffffLL ? 0x7fffffff : T)};
+    if (implicit) {   // (the cuts given are not looked at: the whole series - or they are slots)
+      if (sv.series_cuts) pl->implicit_series_cuts = true;
+      else sv.cuts = {0, (int32_t)(T > 0x7fffffffLL ? 0x7fffffff : T)};
       for (int f = 0; f < nf; ++f) pl->implicit_cols.push_back(sv.kind == FR_SIEVE_CPV ? ~(col + f) : col + f);
     }
     sv.col = col;
@@ -899,6 +903,13 @@ int fr_pipeline_set_series_cuts(fr_pipeline_t *pl, const int32_t *d_cuts, int64_
   return FR_OK;
 }
 
+int fr_pipeline_set_lengths(fr_pipeline_t *pl, const int32_t *d_lengths, int64_t N) {
+  if (!pl || N < 0) return fail(FR_E_ARG, "fr_pipeline_set_lengths: bad argument");
+  pl->d_lengths = d_lengths;
+  pl->lengths_N = d_lengths ? N : 0;
+  return FR_OK;
+}
+
 int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, int64_t T,
                     const double *d_lookup, int64_t lookup_rows, double *d_feats,
                     int64_t feat_stride, void *d_work, int64_t work_bytes, int32_t groups,
@@ -935,6 +946,14 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
     fu.series_cuts = pl->d_series_cuts;
     fu.cut_slots = pl->cut_slots;
   }
+  if (pl->d_lengths && pl->lengths_N != N)
+    return fail(FR_E_ARG, "fr_pipeline_run: fr_pipeline_set_lengths was called for " +
+                              std::to_string(pl->lengths_N) + " series, the input has " + std::to_string(N));
+  // (a PPV / CPV that counts up to the series' own length is divided by it)
+  if (pl->implicit_series_cuts && !pl->d_lengths)
+    return fail(FR_E_ARG, "fr_pipeline_run: a PPV / CPV sieve has per-series cuts - call "
+                          "fr_pipeline_set_lengths first");
+  const int32_t *implicit_lengths = pl->implicit_series_cuts ? pl->d_lengths : nullptr;
   // (the population table of MPI features shares the feature row stride)
   if (!pl->mpi_cols.empty() && feat_stride != F)
     return fail(FR_E_ARG, "fr_pipeline_run: MPI needs feat_stride == F");
@@ -966,7 +985,7 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
       size_t off = plan_ws;
       if (!pl->mpi_cols.empty()) off += align_up((size_t)N * F * 8, 256);
       double *stats = reinterpret_cast<double *>(static_cast<char *>(d_work) + off);
-      hipError_t e = fr::launch_row_stats(d_X, N, D, T, fu.prep, pl->prep_n,
+      hipError_t e = fr::launch_row_stats(d_X, N, D, T, pl->d_lengths, fu.prep, pl->prep_n,
                                           pl->prep_std == 2 ? 1 : 0, pl->prep_eps, stats, st);
       if (e != hipSuccess) return hip_fail(e, "row_stats launch");
       fu.stats = stats;
@@ -1025,7 +1044,8 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
     if (!pl->implicit_cols.empty()) {
       hipError_t e = fr::launch_implicit_finalize(fu.walk_feats, N, F,
                                                   static_cast<const int32_t *>(pl->d_implicit_cols),
-                                                  (int)pl->implicit_cols.size(), pl->per_sum, p.K, T, st);
+                                                  (int)pl->implicit_cols.size(), pl->per_sum, p.K, T,
+                                                  implicit_lengths, st);
       if (e != hipSuccess) return hip_fail(e, "implicit_finalize launch");
     }
     hipError_t e = fr::launch_gather_row_blocks(fu.walk_feats, d_feats, N, F, feat_stride, p.K,
@@ -1050,7 +1070,8 @@ int fr_pipeline_run(fr_pipeline_t *pl, const double *d_X, int64_t N, int64_t D, 
   if (!pl->implicit_cols.empty()) {
     hipError_t e = fr::launch_implicit_finalize(d_feats, N, feat_stride,
                                                 static_cast<const int32_t *>(pl->d_implicit_cols),
-                                                (int)pl->implicit_cols.size(), pl->per_sum, p.K, T, st);
+                                                (int)pl->implicit_cols.size(), pl->per_sum, p.K, T,
+                                                  implicit_lengths, st);
     if (e != hipSuccess) return hip_fail(e, "implicit_finalize launch");
   }
   return FR_OK;

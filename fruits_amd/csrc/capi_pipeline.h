@@ -105,6 +105,12 @@ struct fr_pipeline {
   const int32_t *d_series_cuts = nullptr;
   int64_t cuts_N = 0;
   int32_t cut_slots = 0, cut_slots_needed = 0;
+  // per-series lengths (fr_pipeline_set_lengths): device (lengths_N,) int32 in [1, T], owned by
+  // the caller; nullptr: every series is T long.  Read by STD's statistics pre-pass and by the
+  // divisions of PPV / CPV; `implicit_series_cuts`: a PPV / CPV counts up to a slot of the cut table
+  const int32_t *d_lengths = nullptr;
+  int64_t lengths_N = 0;
+  bool implicit_series_cuts = false;
   // fused preparation (fr_pipeline_set_preparation): 0 dims = none
   int32_t prep_D = 0, prep_n = 0, prep_std = 0;
   double prep_eps = 0.0;

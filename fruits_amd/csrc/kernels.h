@@ -27,7 +27,8 @@ hipError_t launch_mpi_finalize(double *feats, const double *cnt, int64_t N, int6
 hipError_t launch_band_key_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
                                     int n_cols, int per_sum, int K, hipStream_t st);
 hipError_t launch_implicit_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
-                                    int n_cols, int per_sum, int K, int64_t T, hipStream_t st);
+                                    int n_cols, int per_sum, int K, int64_t T, const int32_t *lengths,
+                                    hipStream_t st);
 hipError_t launch_gather_row_blocks(const double *src, double *dst, int64_t N, int64_t src_stride,
                                     int64_t dst_stride, int K, int per_sum, const int32_t *walk_of_row,
                                     hipStream_t st);
@@ -43,9 +44,10 @@ hipError_t launch_sieve(int kind, const double *A, int64_t N, int64_t T, int64_t
                         double *out, int64_t out_stride, hipStream_t st);
 // PPV / CPV: Q thresholds, Q - 1 features with `segments`
 constexpr int kImplicitMaxFeatures = 256;   // (8 KiB of integer counters per workgroup)
+// (`lengths`, here and below: per-series lengths in [1, T], or nullptr - every series is T long)
 hipError_t launch_sieve_implicit(int kind, const double *A, int64_t N, int64_t T, int64_t a_stride,
-                                 const double *q, int Q, int segments, double *out,
-                                 int64_t out_stride, hipStream_t st);
+                                 const int32_t *lengths, const double *q, int Q, int segments,
+                                 double *out, int64_t out_stride, hipStream_t st);
 // jobs sorted so that the jobs of one group (<= kSelGroupMax, same row block) are adjacent;
 // groups = int2 {first job, count}
 constexpr int kSelGroupMax = 8;
@@ -74,8 +76,9 @@ hipError_t launch_coswiss_combine(const double *A, int64_t N, int64_t T, int n_o
                                   const double *trig, double *out, int64_t out_row_stride,
                                   hipStream_t st);
 hipError_t launch_nan_to_num(double *x, int64_t count, hipStream_t st);
-hipError_t launch_standardize(const double *X, int64_t rows, int64_t T, int div_std, double eps,
-                              double *out, hipStream_t st);
+// (rows = series x D; `lengths` is per series)
+hipError_t launch_standardize(const double *X, int64_t rows, int64_t T, const int32_t *lengths,
+                              int64_t D, int div_std, double eps, double *out, hipStream_t st);
 // Arctic argmax rows -> features (kernels_sieve.hip, argmax_sieve_kernel): `words` = device
 // (n_words, 4) int32 {first V row, letters, first output row, 0}; the dynamic LDS of a workgroup
 // (one row of V, the positions of a word's prefixes) must fit kArgmaxSieveLds
@@ -87,8 +90,9 @@ hipError_t launch_argmax_sieves(const double *V, int64_t N, int64_t T, const voi
                                 const int32_t *series_cuts, int cut_slots, hipStream_t st);
 hipError_t launch_arctic_argmax(const double *V, int64_t rows, int64_t N, int64_t T, int n_jobs,
                                 const int32_t *jobs, double *P, double *out, hipStream_t st);
-hipError_t launch_row_stats(const double *X, int64_t N, int64_t D, int64_t T, const int32_t *prep,
-                            int n_prep, int div_std, double eps, double *stats, hipStream_t st);
+hipError_t launch_row_stats(const double *X, int64_t N, int64_t D, int64_t T, const int32_t *lengths,
+                            const int32_t *prep, int n_prep, int div_std, double eps, double *stats,
+                            hipStream_t st);
 // the preparateurs of kernels_prep.hip (RIN / MAV, JLD / FFN, NRM, LAG); hipErrorInvalidValue:
 // a grid limit, or an FFN of more than 16 input / output dimensions
 hipError_t launch_prep_fir(const double *X, int64_t N, int64_t D, int64_t T, const double *taps,

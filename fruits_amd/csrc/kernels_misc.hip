@@ -186,13 +186,18 @@ __global__ __launch_bounds__(256) void pathlen_lookup_kernel(const double *__res
 // the statistics, and with them every standardised value, are bit-identical to the
 // reference's - a last-bit difference here flips the plateau ties of the max-plus
 // semirings behind it.
-__global__ __launch_bounds__(256) void standardize_kernel(const double *__restrict__ X, int64_t T,
+// `lengths` (per series, D rows each; nullptr: every row is T long): the statistics of row r are
+// those of its first L = lengths[r / D] elements, summed in numpy's order FOR THAT LENGTH - what a
+// call on the truncated series computes, bit for bit; the tail [L, T) of the output is 0.
+__global__ __launch_bounds__(256) void standardize_kernel(const double *__restrict__ X, int64_t row_len,
+                                                           const int32_t *__restrict__ lengths, int64_t D,
                                                            int div_std, double eps,
                                                            double *__restrict__ out) {
 #pragma clang fp contract(off)
   __shared__ PairwiseShared sh;
-  const double *x = X + (int64_t)blockIdx.x * T;
-  double *o = out + (int64_t)blockIdx.x * T;
+  const double *x = X + (int64_t)blockIdx.x * row_len;
+  double *o = out + (int64_t)blockIdx.x * row_len;
+  const int64_t T = lengths ? (int64_t)lengths[(int64_t)blockIdx.x / D] : row_len;
   const double mean = np_sum_row([&](int64_t t) { return x[t]; }, T, sh) / (double)T;
   double sd = 1.0;
   if (div_std) {
@@ -206,6 +211,7 @@ __global__ __launch_bounds__(256) void standardize_kernel(const double *__restri
   }
   const double den = sd + eps;
   for (int64_t t = threadIdx.x; t < T; t += blockDim.x) o[t] = (x[t] - mean) / den;
+  for (int64_t t = T + threadIdx.x; t < row_len; t += blockDim.x) o[t] = 0.0;
 }
 
 // Statistics of the PREPARED rows for the fused preparation of the walk kernel (walk.h):
@@ -213,8 +219,10 @@ __global__ __launch_bounds__(256) void standardize_kernel(const double *__restri
 // The same sums in the same order as standardize_kernel over the materialised rows (numpy's),
 // so the fused pipeline reproduces the unfused one, and both the reference, bit for bit.
 // stats[(n * n_prep + d') * 2] = mean, [.. + 1] = std + eps (1 + eps when div_std == 0).
+// `lengths` (nullptr: none): series n is its first lengths[n] elements (standardize_kernel).
 __global__ __launch_bounds__(256) void row_stats_kernel(const double *__restrict__ X, int64_t D,
-                                                         int64_t T, const int32_t *__restrict__ prep,
+                                                         int64_t row_len, const int32_t *__restrict__ lengths,
+                                                         const int32_t *__restrict__ prep,
                                                          int n_prep, int div_std, double eps,
                                                          double *__restrict__ stats) {
 #pragma clang fp contract(off)
@@ -222,7 +230,8 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const double *__restrict
   const int64_t n = blockIdx.x / n_prep;
   const int dp = (int)(blockIdx.x % n_prep);
   const int raw = prep[4 * dp], lag = prep[4 * dp + 1];
-  const double *x = X + (n * D + raw) * T;
+  const double *x = X + (n * D + raw) * row_len;
+  const int64_t T = lengths ? (int64_t)lengths[n] : row_len;
   auto value = [&](int64_t t) -> double {
     if (lag <= 0) return x[t];
     return t >= lag ? x[t] - x[t - lag] : 0.0;
@@ -244,12 +253,13 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const double *__restrict
   }
 }
 
-hipError_t launch_row_stats(const double *X, int64_t N, int64_t D, int64_t T, const int32_t *prep,
-                            int n_prep, int div_std, double eps, double *stats, hipStream_t st) {
+hipError_t launch_row_stats(const double *X, int64_t N, int64_t D, int64_t T, const int32_t *lengths,
+                            const int32_t *prep, int n_prep, int div_std, double eps, double *stats,
+                            hipStream_t st) {
   if (N <= 0 || T <= 0 || n_prep <= 0) return hipSuccess;
   if (N * n_prep > 0x7fffffffLL) return hipErrorInvalidValue;
   hipLaunchKernelGGL(row_stats_kernel, dim3((unsigned)(N * n_prep)), dim3(256), 0, st, X, D, T,
-                     prep, n_prep, div_std, eps, stats);
+                     lengths, prep, n_prep, div_std, eps, stats);
   return hipGetLastError();
 }
 
@@ -382,9 +392,11 @@ hipError_t launch_band_key_finalize(double *feats, int64_t N, int64_t stride, co
 // PPV / CPV columns of a fused launch hold COUNTS (the indicator's population, ~column: its
 // rising edges): the one division of fruits/sieving/implicit.py:124-128, 182 - count / T, or
 // 2 * count / n with n = T rounded up to even - exactly as the standalone kernel forms it.
+// `lengths` (nullptr: none): series n was counted over its first lengths[n] elements, which is
+// then the T of its divisions.
 __global__ void implicit_finalize_kernel(double *__restrict__ feats, int64_t N, int64_t stride,
                                          const int32_t *__restrict__ cols, int n_cols, int per_sum,
-                                         int K, int64_t T) {
+                                         int K, int64_t row_len, const int32_t *__restrict__ lengths) {
   const int64_t per_n = (int64_t)K * n_cols;
   const int64_t total = N * per_n;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -392,17 +404,19 @@ __global__ void implicit_finalize_kernel(double *__restrict__ feats, int64_t N, 
     const int64_t n = i / per_n, r = i % per_n;
     const int64_t k = r / n_cols;
     const int c = cols[r % n_cols];
+    const int64_t T = lengths ? (int64_t)lengths[n] : row_len;
     double *f = feats + n * stride + k * per_sum + (c < 0 ? ~c : c);
     *f = c < 0 ? (2.0 * *f) / (double)(T + (T & 1)) : *f / (double)T;
   }
 }
 
 hipError_t launch_implicit_finalize(double *feats, int64_t N, int64_t stride, const int32_t *cols,
-                                    int n_cols, int per_sum, int K, int64_t T, hipStream_t st) {
+                                    int n_cols, int per_sum, int K, int64_t T, const int32_t *lengths,
+                                    hipStream_t st) {
   const int64_t total = N * (int64_t)K * n_cols;
   if (total <= 0) return hipSuccess;
   hipLaunchKernelGGL(implicit_finalize_kernel, dim3(grid_blocks(total, 4096)), dim3(256), 0, st, feats, N,
-                     stride, cols, n_cols, per_sum, K, T);
+                     stride, cols, n_cols, per_sum, K, T, lengths);
   return hipGetLastError();
 }
 
@@ -513,11 +527,11 @@ hipError_t launch_nan_to_num(double *x, int64_t count, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_standardize(const double *X, int64_t rows, int64_t T, int div_std, double eps,
-                              double *out, hipStream_t st) {
+hipError_t launch_standardize(const double *X, int64_t rows, int64_t T, const int32_t *lengths,
+                              int64_t D, int div_std, double eps, double *out, hipStream_t st) {
   if (rows <= 0 || T <= 0) return hipSuccess;
-  hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)rows), dim3(256), 0, st, X, T, div_std,
-                     eps, out);
+  hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)rows), dim3(256), 0, st, X, T, lengths,
+                     D > 0 ? D : 1, div_std, eps, out);
   return hipGetLastError();
 }
 

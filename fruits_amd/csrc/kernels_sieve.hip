@@ -229,18 +229,22 @@ __global__ __launch_bounds__(256) void band_sieve_kernel(int kind, const double 
 // rising edges at t >= 1 (the first difference is zero-padded, fruits/cache.py:8-13: a component
 // that starts at t = 0 is not counted).  Counts are integers: a wave adds its ballot's population
 // to a counter of its own, the four are added in wave order, and one division forms the feature.
+// `lengths` (nullptr: none): series n is its first lengths[n] elements - counted there, divided
+// by that length (CPV: rounded up to even).
 __device__ __forceinline__ bool implicit_in(double v, const double *__restrict__ q, int j, bool segments) {
   return segments ? (q[j] <= v && v < q[j + 1]) : (v >= q[j]);
 }
 
 __global__ __launch_bounds__(256) void implicit_sieve_kernel(int kind, const double *__restrict__ A,
-                                                              int64_t T, int64_t a_stride,
+                                                              int64_t row_len, int64_t a_stride,
+                                                              const int32_t *__restrict__ lengths,
                                                               const double *__restrict__ q, int F,
                                                               int segments, double *__restrict__ out,
                                                               int64_t out_stride) {
   __shared__ unsigned long long sm_cnt[4][kImplicitMaxFeatures];
   const int64_t n = blockIdx.x;
   const double *row = A + n * a_stride;
+  const int64_t T = lengths ? (int64_t)lengths[n] : row_len;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool cpv = kind == FR_SIEVE_CPV_K;
   for (int j = tid; j < 4 * F; j += blockDim.x) sm_cnt[j / F][j % F] = 0;
@@ -268,13 +272,13 @@ __global__ __launch_bounds__(256) void implicit_sieve_kernel(int kind, const dou
 }
 
 hipError_t launch_sieve_implicit(int kind, const double *A, int64_t N, int64_t T, int64_t a_stride,
-                                 const double *q, int Q, int segments, double *out,
-                                 int64_t out_stride, hipStream_t st) {
+                                 const int32_t *lengths, const double *q, int Q, int segments,
+                                 double *out, int64_t out_stride, hipStream_t st) {
   if (N <= 0) return hipSuccess;
   const int F = segments ? Q - 1 : Q;
   if (N > 0x7fffffffLL || F < 1 || F > kImplicitMaxFeatures) return hipErrorInvalidValue;
   hipLaunchKernelGGL(implicit_sieve_kernel, dim3((unsigned)N), dim3(256), 0, st, kind, A, T, a_stride,
-                     q, F, segments, out, out_stride);
+                     lengths, q, F, segments, out, out_stride);
   return hipGetLastError();
 }
 

@@ -325,7 +325,11 @@ __device__ __forceinline__ void fop_implicit(WalkCtx &cx, const int32_t *w, int 
   constexpr int E = C::E;
   static_assert(C::P == 1, "one piece per wave");
   const bool cpv = (w[0] & 0xff) == FR_SIEVE_CPV_K, seg = (w[0] & OPF_SEGMENTS) != 0;
-  const int hi = w[3];   // T
+  int hi = w[3];   // T, or the slot of the series' own length
+  if ((w[0] & OPF_SERIES_CUTS) != 0) {
+    cptr<IssArgs> ca = cold_args();
+    hi = as_const(ca->series_cuts + cx.series * ca->cut_slots)[w[3]];
+  }
   const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
   if (cpv && !sc.have_cp) {
     int at = 0;

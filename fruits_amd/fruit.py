@@ -20,6 +20,7 @@ from . import _native as nat
 from .cache import SharedSeedCache
 from .callback import AbstractCallback
 from .iss.iss import ISS
+from .lengths import check_lengths, require_support
 from .preparation.abstract import Preparateur
 from .seed import Seed
 from .sieving.abstract import FeatureSieve
@@ -200,7 +201,9 @@ class Fruit:
         return sum(slc.nfeatures() for slc in self._slices)
 
     # ---- fit / transform ----------------------------------------------------
-    def fit(self, X: np.ndarray, cache: Optional[SharedSeedCache] = None) -> None:
+    def fit(self, X: np.ndarray, cache: Optional[SharedSeedCache] = None, lengths=None) -> None:
+        """``lengths``: integer array (N,), series n is ``X[n, :, :lengths[n]]`` (DESIGN.md,
+        "Per-series lengths"); None: every series is T long."""
         X = _check_batch(X)
         cache_ = SharedSeedCache(X) if cache is None else cache
         # the slices are started one after the other; the device-side selections of a slice's
@@ -208,7 +211,7 @@ class Fruit:
         deferred: list = []
         try:
             for slc in self._slices:
-                slc.fit(X, cache=cache_, deferred=deferred)
+                slc.fit(X, cache=cache_, deferred=deferred, lengths=lengths)
         finally:
             for finish in deferred:
                 finish()
@@ -220,11 +223,14 @@ class Fruit:
 
     def transform(self, X: np.ndarray,
                   callbacks: Optional[list[AbstractCallback]] = None,
-                  cache: Optional[SharedSeedCache] = None) -> np.ndarray:
-        """``(N, nfeatures)`` features of all slices.
+                  cache: Optional[SharedSeedCache] = None, lengths=None) -> np.ndarray:
+        """``(N, nfeatures)`` features of all slices.  ``lengths``: integer array (N,) - row n
+        is then what ``transform(X[n:n+1, :, :lengths[n]])[0]`` returns; the values behind a
+        series' length must be finite and influence nothing.
 
         Raises:
             RuntimeError: if :meth:`fit` was not called.
+            NotImplementedError: with ``lengths``, for a seed that does not take them.
         """
         callbacks = callbacks or []
         if not self._fitted:
@@ -236,15 +242,16 @@ class Fruit:
         for slc in self._slices:
             for cb in callbacks:
                 cb.on_next_slice()
-            blocks.append(slc.transform_device(X, callbacks, cache_))
+            blocks.append(slc.transform_device(X, callbacks, cache_, lengths=lengths))
         # assembled on the device: one download instead of a strided host copy per slice
         result = blocks[0] if len(blocks) == 1 else t.cat(blocks, dim=1)
         return nat.to_host(nat.nan_to_num(result.contiguous()))
 
     def fit_transform(self, X: np.ndarray,
-                      callbacks: Optional[list[AbstractCallback]] = None) -> np.ndarray:
-        self.fit(X)
-        return self.transform(X, callbacks=callbacks)
+                      callbacks: Optional[list[AbstractCallback]] = None,
+                      lengths=None) -> np.ndarray:
+        self.fit(X, lengths=lengths)
+        return self.transform(X, callbacks=callbacks, lengths=lengths)
 
     # ---- the fitted state, to be handed to other processes (fruits_amd.parallel) ----
     def fit_state(self) -> bytes:
@@ -427,7 +434,7 @@ class FruitSlice:
         return X[self._select_fit_indices(X), :, :]
 
     # ---- device pipeline --------------------------------------------------------
-    def _prepare_device(self, Xd, cache, callbacks=(), fit_on=None):
+    def _prepare_device(self, Xd, cache, callbacks=(), fit_on=None, lengths_d=None):
         for prep in self._preparateurs:
             prep._cache = cache
             if fit_on is not None:
@@ -437,12 +444,14 @@ class FruitSlice:
                     prep.fit(np.broadcast_to(0.0, tuple(int(v) for v in Xd.shape)))
                 else:
                     prep.fit(fit_on)
-            Xd = prep._transform_device(Xd)
+            Xd = (prep._transform_device(Xd) if lengths_d is None
+                  else prep._transform_device(Xd, lengths_d=lengths_d))
             for cb in callbacks:
                 cb.on_preparateur(nat.to_host(Xd))
         return Xd
 
-    def _iterate_iss_device(self, Xd, iss_index: int = 0, upto: Optional[int] = None) -> Generator:
+    def _iterate_iss_device(self, Xd, iss_index: int = 0, upto: Optional[int] = None,
+                            lengths=None) -> Generator:
         """Yields every iterated sum as an (N, T) device tensor, in the order of
         fruits/fruit.py:440-454 (chained ISS feed each row to the next ISS).  ``upto``: stop in
         front of that ISS of the chain and yield its (N, 1, T) INPUTS instead."""
@@ -453,7 +462,8 @@ class FruitSlice:
             yield Xd[:, 0, :]
             return
         iss = self._iss[iss_index]
-        lookup = iss.lookup_device(Xd)
+        # (``lengths``: a single ISS - the gate of a ragged batch has seen to that)
+        lookup = iss.lookup_device(Xd) if lengths is None else iss.lookup_device(Xd, lengths=lengths)
         for s, e in iss.word_batches(int(Xd.shape[0]), int(Xd.shape[2])):
             block = iss.transform_device(Xd, s, e, lookup)
             for k in range(block.shape[0]):
@@ -603,17 +613,22 @@ class FruitSlice:
                 return False     # (cumulated rows: series of one time chunk; the pipeline says if not)
         return True
 
-    def _fused(self, T: int, indices=None, chain_row: int = 0, D: Optional[int] = None):
+    def _fused(self, T: int, indices=None, chain_row: int = 0, D: Optional[int] = None,
+               ragged: bool = False):
         """The fused pipeline for series length T (thresholds of the fitted sieve
         copies already resolved), or None when a sieve or the weighting is outside
         the fused set; cached until the next fit.  ``indices``: only these words
         (a rank's share of a word-sharded slice, fruits_amd.parallel); the pipeline
         then produces the feature columns of their iterated sums, in that order.
         ``chain_row`` (chained ISS): the pipeline of the LAST ISS for the ``chain_row``-th row of
-        the chain in front of it - the same program, that row's thresholds."""
+        the chain in front of it - the same program, that row's thresholds.
+        ``ragged``: the pipeline for a batch with per-series lengths - every sieve's cuts are
+        slots of the per-series table (_arm_lengths); an entry of its own, never the dense one."""
         key = T if indices is None else (T, tuple(indices))
         if chain_row:
             key = (key, chain_row)
+        if ragged:
+            key = (key, "ragged")
         # Generic words (iss/lowering.py): the plan runs on virtual rows formed from the prepared
         # (N, D, T) input, so the pipeline belongs to that D.  Fused are a single ISS over Reals
         # or Arctic (no output unshift) whose weighting, if any, meets generic words only;
@@ -656,7 +671,7 @@ class FruitSlice:
                 rows = [chain_row * iss.n_iterated_sums() + r for r in rows]
             acting = (self._sieves_extended[rows[0]] if self._sieves_extended and len(rows)
                       else self._sieves)
-            specs, cut_columns, n_slots = self._pipeline_specs(acting, T)
+            specs, cut_columns, n_slots = self._pipeline_specs(acting, T, ragged)
             try:
                 pipe = (nat.Pipeline(plan, specs, T, argmax_lengths=argmax)
                         if len(rows) and plan.fits(T) else None)
@@ -697,9 +712,11 @@ class FruitSlice:
         return entry
 
     @staticmethod
-    def _pipeline_specs(acting, T: int):
+    def _pipeline_specs(acting, T: int, ragged: bool = False):
         """What fr_pipeline_create is told about the sieves ``acting`` for series of length T:
-        (specs, cut columns, slots of the per-series cut table)."""
+        (specs, cut columns, slots of the per-series cut table).  ``ragged``: integer cuts name
+        slots too - they resolve per series length (lengths.resolve_cuts; END's own table,
+        lengths.resolve_end_cuts) - and PPV / CPV the slot pair {0, length} (cut column None)."""
         # float ("coquantile") cuts differ from series to series: such a sieve names
         # columns of a per-series table instead of indices; sieves with the same cuts
         # share their columns (so NPI / MPI pairs still merge)
@@ -714,11 +731,22 @@ class FruitSlice:
                 inc = 0
             if kind in (nat.FR_SIEVE_PPV, nat.FR_SIEVE_CPV):
                 # (the whole row itself; the thresholds in the sieve's own order)
-                specs.append((kind | (nat.FR_SIEVE_SEGMENTS if sv._segments else 0), 0,
+                segments = nat.FR_SIEVE_SEGMENTS if sv._segments else 0
+                if ragged:
+                    if "length" not in cut_columns:
+                        cut_columns["length"] = (n_slots, None)
+                        n_slots += 2
+                    slot0 = cut_columns["length"][0]
+                    specs.append((kind | segments | nat.FR_SIEVE_SERIES_CUTS, 0,
+                                  np.array([slot0, slot0 + 1], dtype=np.int64), _n_thresholds(sv)))
+                    continue
+                specs.append((kind | segments, 0,
                               np.array([0, T], dtype=np.int64), _n_thresholds(sv)))
                 continue
-            if sv._has_float_cuts():
+            if sv._has_float_cuts() or ragged:
                 cuts_key = (tuple(sv._cut), sv._coquantile_norm)
+                if ragged:
+                    cuts_key = ("int", tuple(sv._cut), kind == nat.FR_SIEVE_END)
                 if cuts_key not in cut_columns:
                     cut_columns[cuts_key] = (n_slots, sv)
                     n_slots += len(sv._cut) + 1
@@ -776,6 +804,21 @@ class FruitSlice:
             table[:, first:first + rows.shape[1]] = np.clip(rows, 0, T)
         pipe.set_series_cuts(nat.to_device(table, dtype=np.int32))
 
+    @staticmethod
+    def _arm_lengths(pipe, lengths: np.ndarray, lengths_d) -> None:
+        """Uploads the per-series boundaries of a ragged pipeline - every sieve's integer cuts
+        resolved for each series' length - and hands it the lengths (STD's statistics, the
+        divisions of PPV / CPV).  END's IndexError for a series too short is raised here."""
+        table = np.zeros((len(lengths), pipe._cut_slots), dtype=np.int32)
+        for first, sv in pipe._cut_columns:
+            if sv is None:
+                table[:, first + 1] = lengths
+            else:
+                rows = sv._series_cut_rows(lengths)
+                table[:, first:first + rows.shape[1]] = rows
+        pipe.set_series_cuts(nat.to_device(table, dtype=np.int32))
+        pipe.set_lengths(lengths_d)
+
     def _fusable_preparation(self, T: int):
         """(inc_lag, as_new, standardize, eps) when the preparateur chain is one the fused
         launch forms while staging the raw input - [INC | NEW(INC)] [STD], the chains of the
@@ -828,11 +871,23 @@ class FruitSlice:
             iss._attach_cache(None)
 
     # ---- fit / transform ----------------------------------------------------
+    def _ragged_lengths(self, X: np.ndarray, lengths) -> Optional[np.ndarray]:
+        """The validated ``lengths`` of a call, None when there are none; the gate: every seed
+        of the slice is asked (``_supports_lengths``) before anything is launched."""
+        lengths = check_lengths(lengths, X.shape[0], X.shape[2])
+        if lengths is None:
+            return None
+        if len(self._iss) > 1:
+            raise NotImplementedError("chained ISS do not support per-series lengths")
+        require_support((*self._preparateurs, *self._iss, *self._sieves))
+        return lengths
+
     def fit(self, X: np.ndarray, cache: Optional[SharedSeedCache] = None,
-            deferred: Optional[list] = None) -> None:
+            deferred: Optional[list] = None, lengths=None) -> None:
         self._compile()
         self._fused_cache = {}
         X = _check_batch(X)
+        lengths = self._ragged_lengths(X, lengths)
         if cache is None:
             cache = SharedSeedCache(X)
         # the fit sample: rows of the input, gathered ON THE DEVICE from the cache's one upload of
@@ -840,6 +895,19 @@ class FruitSlice:
         # gather + upload per slice otherwise); the host copy only for a preparateur whose fit
         # looks at the data
         indices = self._select_fit_indices(X)
+        if lengths is not None and not (lengths == X.shape[2]).all():
+            # The sample is drawn as ever.  Series of ONE length (the default sample of one
+            # series among them) are truncated to it and fitted as the ordinary batch they are;
+            # a sample of unequal lengths is fitted on the host, every threshold from the valid
+            # parts of its rows (_fit_valid).
+            sample_lengths = lengths[indices]
+            if (sample_lengths == sample_lengths[0]).all():
+                X = np.ascontiguousarray(X[indices, :, :int(sample_lengths[0])])
+                indices, sample_lengths = np.arange(X.shape[0]), None
+                cache = SharedSeedCache(X)
+            else:
+                self._fit_unequal(X[indices, :, :], sample_lengths, cache)
+                return
         needs_host = any(prep._fit_needs_data() for prep in self._preparateurs)
         whole = cache._input_dev is not None or 2 * len(indices) >= X.shape[0]   # (else: upload the sample alone)
         if cache._input is X and not needs_host and whole:
@@ -872,21 +940,91 @@ class FruitSlice:
             self._sieves_extended.append(fitted)
         self._fitted = True
 
+    def _fit_unequal(self, sample: np.ndarray, lengths: np.ndarray, cache) -> None:
+        """Fits the sieves on a sample whose series differ in length, on the host: the sample is
+        prepared and its iterated sums are formed with the tails in place (both are causal), and
+        every sieve copy takes its quantiles over the concatenated VALID parts of its
+        pre-transformed rows (``_fit_valid``; PPV / CPV raise NotImplementedError there)."""
+        for sieve in self._sieves:
+            if sieve.requires_fitting and not hasattr(sieve, "_fit_valid"):
+                raise NotImplementedError(
+                    f"{type(sieve).__name__} ({sieve}) cannot be fitted on a sample of unequal lengths")
+        lengths_d = nat.to_device(lengths.astype(np.int32), dtype=np.int32)
+        Sd = self._prepare_device(nat.to_device(sample), cache, fit_on=sample, lengths_d=lengths_d)
+        self._attach(cache)
+        self._sieves_extended = []
+        if any(sieve.requires_fitting for sieve in self._sieves):
+            for itsum in self._iterate_iss_device(Sd, lengths=lengths):
+                host = nat.to_host(itsum)
+                fitted = [sieve.copy() for sieve in self._sieves]
+                for sieve in fitted:
+                    sieve._cache = cache
+                    if sieve.requires_fitting:
+                        sieve._fit_valid(host, lengths)
+                self._sieves_extended.append(fitted)
+        self._fitted = True
+
     def transform(self, X: np.ndarray,
                   callbacks: Optional[list[AbstractCallback]] = None,
-                  cache: Optional[SharedSeedCache] = None) -> np.ndarray:
-        return nat.to_host(self.transform_device(X, callbacks, cache))
+                  cache: Optional[SharedSeedCache] = None, lengths=None) -> np.ndarray:
+        return nat.to_host(self.transform_device(X, callbacks, cache, lengths=lengths))
+
+    def _transform_ragged(self, X: np.ndarray, lengths: np.ndarray, cache):
+        """``transform_device`` for a batch with per-series lengths: the launches of the dense
+        call - one fused launch where the slice fuses, on the ragged entry of ``_fused_cache``
+        (generic kernel instances: a pipeline with per-series cuts has no compiled one) - with
+        every extent, statistic and divisor taken per series."""
+        t = nat.torch()
+        iss = self._iss[0]
+        Xd = cache.input_device(X) if cache._input is X else nat.to_device(X)
+        N, T = int(Xd.shape[0]), int(Xd.shape[2])
+        lengths_d = nat.to_device(lengths.astype(np.int32), dtype=np.int32)
+        chain = self._fusable_preparation(T)
+        fused = self._fused(T, ragged=True) if chain is not None else None
+        if fused is not None:
+            if getattr(fused, "_prep_chain", None) != (chain, int(Xd.shape[1])):
+                fused.set_preparation(int(Xd.shape[1]), chain[0], chain[1], chain[2], chain[3])
+                fused._prep_chain = (chain, int(Xd.shape[1]))
+            if fused.raw_dims > 0:
+                self._attach(cache)
+                self._arm_lengths(fused, lengths, lengths_d)
+                return fused.run(Xd, iss.lookup_device(Xd, lengths=lengths))
+        Pd = self._prepare_device(Xd, cache, lengths_d=lengths_d)
+        self._attach(cache)
+        fused = self._fused(T, D=int(Pd.shape[1]), ragged=True)
+        if fused is not None:
+            if fused.raw_dims > 0:       # (was configured for raw input by another call)
+                fused.set_preparation(int(Pd.shape[1]))
+                fused._prep_chain = None
+            self._arm_lengths(fused, lengths, lengths_d)
+            weighted = fused.plan.weighting != nat.FR_W_NONE
+            return fused.run(Pd, iss.lookup_device(Pd, lengths=lengths) if weighted else None)
+        feats = t.zeros((N, self.nfeatures()), dtype=t.float64, device=Pd.device)
+        col = 0
+        for i, itsum in enumerate(self._iterate_iss_device(Pd, lengths=lengths)):
+            sieves = self._sieves_extended[i] if self._sieves_extended else self._sieves
+            for sieve in sieves:
+                sieve._cache = cache
+                sieve.transform_device(itsum, feats, col, lengths=lengths)
+                col += sieve.nfeatures()
+        return feats
 
     def transform_device(self, X: np.ndarray,
                          callbacks: Optional[list[AbstractCallback]] = None,
-                         cache: Optional[SharedSeedCache] = None):
+                         cache: Optional[SharedSeedCache] = None, lengths=None):
         """``transform`` with the ``(N, nfeatures)`` result left on the device."""
         callbacks = callbacks or []
         if not self._fitted:
             raise RuntimeError("Missing call of self.fit")
         X = _check_batch(X)
+        lengths = self._ragged_lengths(X, lengths)
         if cache is None:
             cache = SharedSeedCache(X)
+        # (lengths that all equal T: the dense call itself, bit for bit)
+        if lengths is not None and not (lengths == X.shape[2]).all():
+            if callbacks:
+                raise NotImplementedError("callbacks do not support per-series lengths")
+            return self._transform_ragged(X, lengths, cache)
         t = nat.torch()
         Xd = cache.input_device(X) if cache._input is X else nat.to_device(X)
         ffn = getattr(self._iss[-1], "_ffn_size", None) is not None
@@ -993,9 +1131,9 @@ class FruitSlice:
             feats[:, slot * width:(slot + 1) * width] = pipe.run(Z[0], None)
         return feats
 
-    def fit_transform(self, X: np.ndarray) -> np.ndarray:
-        self.fit(X)
-        return self.transform(X)
+    def fit_transform(self, X: np.ndarray, lengths=None) -> np.ndarray:
+        self.fit(X, lengths=lengths)
+        return self.transform(X, lengths=lengths)
 
     # ---- introspection ------------------------------------------------------
     def summary(self) -> str:

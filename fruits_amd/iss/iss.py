@@ -25,6 +25,7 @@ import numpy as np
 
 from .. import _native as nat
 from ..cache import SharedSeedCache
+from ..lengths import lookup_rows
 from ..seed import Seed
 from . import lowering
 from .cache import CachePlan
@@ -259,13 +260,27 @@ class ISS(Seed):
         else:
             self.weighting._cache = SharedSeedCache(X)
 
-    def lookup_device(self, Xd):
+    def _supports_lengths(self) -> bool:
+        """Per-series lengths: simple words over Reals, Arctic (without argmax) or Bayesian,
+        unweighted or with a weighting whose row is a function of the series length (Indices,
+        Plateaus - one row per distinct length, lengths.lookup_rows).  A subclass says for
+        itself."""
+        if type(self) is not ISS or self._argmax or self._has_generic:
+            return False
+        if not isinstance(self.semiring, (Reals, Arctic, Bayesian)):
+            return False
+        return self.weighting is None or self.weighting._supports_lengths()
+
+    def lookup_device(self, Xd, lengths=None):
         """(rows, T) device lookup of the weighting, rows in {1, N}; when the
         cache holds more series than Xd (fit on a sub-sample) the leading rows
         are used - the reference indexes ``lookup[j]`` by position
-        (fruits/iss/semiring.py:185-199)."""
+        (fruits/iss/semiring.py:185-199).  ``lengths`` (host array): the (N, T) lookup whose
+        row n is the weighting's row for a series of ``lengths[n]`` elements."""
         if self.weighting is None:
             return None
+        if lengths is not None:
+            return nat.to_device(lookup_rows(self.weighting._row, lengths, int(Xd.shape[2])))
         # (max-plus results meet fitted quantiles in exact ties: bit-exact lookup there)
         lk = self.weighting.lookup_device(Xd, exact=not isinstance(self.semiring, Reals))
         n = int(Xd.shape[0])

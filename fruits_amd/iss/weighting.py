@@ -47,6 +47,10 @@ class Weighting(ABC):
     def get_lookup(self, X: np.ndarray) -> np.ndarray:
         ...
 
+    def _supports_lengths(self) -> bool:
+        """Whether g for a series of length L is a function of L alone (fruits_amd/lengths.py)."""
+        return False
+
     def lookup_device(self, Xd, exact: bool = True):
         """Device lookup for the prepared device input ``Xd`` (N, D, T).  ``exact``:
         bit-identical to the reference (needed where exact ties matter: max-plus
@@ -58,6 +62,9 @@ class Weighting(ABC):
 class _SeriesIndependent(Weighting):
     def _row(self, T: int) -> np.ndarray:
         raise NotImplementedError
+
+    def _supports_lengths(self) -> bool:
+        return True
 
     def get_lookup(self, X: np.ndarray) -> np.ndarray:
         n, _, T = X.shape

@@ -55,7 +55,12 @@ class INC(Preparateur):
             return int(self._shift(T))
         raise TypeError(f"Type {type(self._shift)} not supported for argument shift")
 
-    def _transform_device(self, Xd):
+    def _supports_lengths(self) -> bool:
+        # (an integer lag: a float or a callable is a function of the padded length)
+        return isinstance(self._shift, (int, np.integer)) and not isinstance(self._shift, bool)
+
+    def _transform_device(self, Xd, lengths_d=None):
+        # (increments are causal: the valid part of a series does not see its tail)
         lag = self._lag(int(Xd.shape[2]))
         out = Xd
         for _ in range(self._depth):
@@ -100,9 +105,13 @@ class STD(Preparateur):
             self._mean = np.mean(X)
             self._std = np.std(X) if self._div_std else 1
 
-    def _transform_device(self, Xd):
+    def _supports_lengths(self) -> bool:
+        # (separately=False: one mean / deviation of the whole fit sample, tails included)
+        return bool(self._separately)
+
+    def _transform_device(self, Xd, lengths_d=None):
         if self._separately:
-            return nat.standardize(Xd, self._div_std, float(self._eps))
+            return nat.standardize(Xd, self._div_std, float(self._eps), lengths_d=lengths_d)
         if self._mean is None or self._std is None:
             raise RuntimeError("Missing call of self.fit()")
         return (Xd - float(self._mean)) / (float(self._std) + float(self._eps))

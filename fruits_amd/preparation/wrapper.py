@@ -42,13 +42,17 @@ class DIM(Preparateur):
     def _check_fitted(self) -> None:
         self._preparateur._check_fitted()
 
-    def _transform_device(self, Xd):
+    def _supports_lengths(self) -> bool:
+        return self._preparateur._supports_lengths()
+
+    def _transform_device(self, Xd, lengths_d=None):
         t = nat.torch()
         D = int(Xd.shape[1])
         dim = np.arange(D)[self._dim]      # (numpy's index rules: negative entries, range errors)
         idx = nat.to_device(np.ascontiguousarray(dim, dtype=np.int64), dtype=np.int64)
-        transformed = self._preparateur._transform_device(
-            t.index_select(Xd, 1, idx).contiguous())
+        sub = t.index_select(Xd, 1, idx).contiguous()
+        transformed = (self._preparateur._transform_device(sub) if lengths_d is None
+                       else self._preparateur._transform_device(sub, lengths_d=lengths_d))
         rest = np.delete(np.arange(D), self._dim)
         if rest.size == 0:
             return transformed
@@ -89,9 +93,17 @@ class NEW(Preparateur):
         if self._preparateur is not None:
             self._preparateur._check_fitted()
 
-    def _transform_device(self, Xd):
+    def _supports_lengths(self) -> bool:
+        return self._preparateur is None or self._preparateur._supports_lengths()
+
+    def _transform_device(self, Xd, lengths_d=None):
         t = nat.torch()
-        extra = Xd if self._preparateur is None else self._preparateur._transform_device(Xd)
+        if self._preparateur is None:
+            extra = Xd
+        elif lengths_d is None:
+            extra = self._preparateur._transform_device(Xd)
+        else:
+            extra = self._preparateur._transform_device(Xd, lengths_d=lengths_d)
         return t.cat((Xd, extra), dim=1).contiguous()
 
     def _copy(self) -> "NEW":

@@ -37,6 +37,12 @@ class Seed(ABC):
     def requires_fitting(self) -> bool:
         return True
 
+    def _supports_lengths(self) -> bool:
+        """Whether this seed, as configured, takes per-series lengths (fruits_amd/lengths.py): a
+        fruit asks every seed of a slice before it launches anything for a ragged batch, and
+        hands ``lengths`` only to seeds that said yes."""
+        return False
+
     @abstractmethod
     def _fit(self, X: np.ndarray) -> None:
         ...

@@ -166,10 +166,17 @@ class PPV(FeatureSieve):
         # (the device tensor is the process's, like the cache: Seed._TRANSIENT)
         return {k: v for k, v in super().__getstate__().items() if k != "_q_dev"}
 
-    def transform_device(self, Ad, out, col: int):
+    def _supports_lengths(self) -> bool:
+        return True
+
+    def transform_device(self, Ad, out, col: int, lengths=None):
         """Writes this sieve's features of the (N, T) device array ``Ad`` into columns
-        [col, col + nfeatures) of the (N, F) device tensor ``out``."""
-        nat.sieve_implicit(self._kind, Ad, self.thresholds_device(), self._segments, out, col)
+        [col, col + nfeatures) of the (N, F) device tensor ``out``.  ``lengths``: host array
+        (N,), series n is its first ``lengths[n]`` elements (fr_sieve_implicit_lengths)."""
+        lengths_d = None if lengths is None else nat.to_device(
+            np.ascontiguousarray(lengths, dtype=np.int32), dtype=np.int32)
+        nat.sieve_implicit(self._kind, Ad, self.thresholds_device(), self._segments, out, col,
+                           lengths_d=lengths_d)
 
     def _transform(self, X: np.ndarray) -> np.ndarray:
         if not hasattr(self, "_q"):

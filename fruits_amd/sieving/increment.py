@@ -40,13 +40,17 @@ class IncrementSieve(SegmentSieve):
         # np.quantile over the whole pre-transformed fit sample (segment.py:66-75)
         super()._fit(self._pre_transform(X))
 
-    def transform_device(self, Ad, out, col: int):
+    def _fit_rows(self, X: np.ndarray) -> np.ndarray:
+        return self._pre_transform(X)
+
+    def transform_device(self, Ad, out, col: int, lengths=None):
+        # (cumulated rows are causal, like the increments: no length needed in front of the sieve)
         if self._inc < 0:
             src, inc = self._pre_transform_device(Ad), 0
         else:
             src, inc = Ad, self._inc
         N, T = src.shape
-        nat.sieve(self._kind, src, inc, self.cuts_device(N, T), self.quantiles_device(),
+        nat.sieve(self._kind, src, inc, self.cuts_device(N, T, lengths), self.quantiles_device(),
                   out, col)
 
     def _copy(self):

@@ -16,6 +16,7 @@ import numpy as np
 
 from .. import _native as nat
 from ..cache import CacheType
+from ..lengths import resolve_cuts, resolve_end_cuts
 from .abstract import FeatureSieve
 
 __all__ = ["MAX", "MIN", "END", "CUR", "AVG", "STD"]
@@ -70,8 +71,19 @@ class SegmentSieve(FeatureSieve, ABC):
                 cuts[:, i + 1] = c if c >= 0 else T + c + 1
         return np.sort(cuts).astype(np.int64)
 
-    def cuts_device(self, N: int, T: int):
-        """Device cut table: one broadcast row for integer cuts, else (N, C+1)."""
+    def _supports_lengths(self) -> bool:
+        # (a float cut is a coquantile of the padded input's path length)
+        return not self._has_float_cuts()
+
+    def _series_cut_rows(self, lengths) -> np.ndarray:
+        """(N, C+1) boundaries of integer cuts for series of these lengths (lengths.py)."""
+        return resolve_cuts(self._cut, lengths)
+
+    def cuts_device(self, N: int, T: int, lengths=None):
+        """Device cut table: one broadcast row for integer cuts, else (N, C+1) - of which one
+        row per series with ``lengths`` (host array), every row resolved for its length."""
+        if lengths is not None:
+            return nat.to_device(self._series_cut_rows(lengths), dtype=np.int64)
         if not self._has_float_cuts():
             return nat.to_device(self._int_cut_row(T)[np.newaxis, :], dtype=np.int64)
         return nat.to_device(self._get_transformed_cuts(np.empty((N, T))), dtype=np.int64)
@@ -87,6 +99,16 @@ class SegmentSieve(FeatureSieve, ABC):
             elif q != 0:
                 qs[i] = np.quantile(X, q)
         self._quantiles = np.sort(qs)
+
+    def _fit_rows(self, X: np.ndarray) -> np.ndarray:
+        """The rows ``fit`` takes its quantiles of."""
+        return X
+
+    def _fit_valid(self, X: np.ndarray, lengths) -> None:
+        """``fit`` on series of unequal lengths: np.quantile over the concatenation of the valid
+        parts ``rows[n, :lengths[n]]`` of the pre-transformed rows."""
+        rows = self._fit_rows(X)
+        SegmentSieve._fit(self, np.concatenate([rows[n, :int(L)] for n, L in enumerate(lengths)]))
 
     # device-side fit: np.quantile's two order statistics come from fr_select_ranks
     def _quantile_requests(self, n: int):
@@ -144,11 +166,12 @@ class SegmentSieve(FeatureSieve, ABC):
         return nat.to_device(np.asarray(self._quantiles, dtype=np.float64))
 
     # ---- transform ------------------------------------------------------------
-    def transform_device(self, Ad, out, col: int):
+    def transform_device(self, Ad, out, col: int, lengths=None):
         """Writes this sieve's features of the (N, T) device array ``Ad`` into
-        columns [col, col + nfeatures) of the (N, F) device tensor ``out``."""
+        columns [col, col + nfeatures) of the (N, F) device tensor ``out``.  ``lengths``: host
+        array (N,), series n is its first ``lengths[n]`` elements."""
         N, T = Ad.shape
-        nat.sieve(self._kind, Ad, self._inc, self.cuts_device(N, T),
+        nat.sieve(self._kind, Ad, self._inc, self.cuts_device(N, T, lengths),
                   self.quantiles_device(), out, col)
 
     def _transform(self, X: np.ndarray) -> np.ndarray:
@@ -221,6 +244,9 @@ class END(SegmentSieve):
         row = super()._int_cut_row(T)
         self._check_cuts(row, T)
         return row
+
+    def _series_cut_rows(self, lengths) -> np.ndarray:
+        return resolve_end_cuts(self._cut, lengths)
 
     def _get_transformed_cuts(self, X: np.ndarray) -> np.ndarray:
         cuts = super()._get_transformed_cuts(X)

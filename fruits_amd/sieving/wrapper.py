@@ -45,11 +45,19 @@ class _SieveWrapper(FeatureSieve):
             if own:
                 del inner._cache
 
-    def transform_device(self, Ad, out, col: int):
+    def _supports_lengths(self) -> bool:
+        # (where the wrapper is its inner sieve at another differencing order: the rows it forms
+        # otherwise - a shift > 1, sums of increments - are causal too, but only this is tested)
+        return self._reduced() is not None and self._sieve._supports_lengths()
+
+    def transform_device(self, Ad, out, col: int, lengths=None):
         """Writes the inner sieve's features of the pre-transformed (N, T) device array ``Ad``
         into columns [col, col + nfeatures) of the (N, F) device tensor ``out``."""
         Yd = self._pre_transform_device(Ad)
-        self._inner_on(Yd, lambda: self._sieve.transform_device(Yd, out, col))
+        if lengths is None:
+            self._inner_on(Yd, lambda: self._sieve.transform_device(Yd, out, col))
+        else:
+            self._inner_on(Yd, lambda: self._sieve.transform_device(Yd, out, col, lengths=lengths))
 
     def _checked(self, X: np.ndarray):
         if not isinstance(X, np.ndarray) or X.dtype != np.float64 or X.ndim != 2:
@@ -60,6 +68,11 @@ class _SieveWrapper(FeatureSieve):
         Yd = self._pre_transform_device(self._checked(X))
         if self._sieve.requires_fitting:
             self._inner_on(Yd, lambda: self._sieve.fit(nat.to_host(Yd)))
+
+    def _fit_valid(self, X: np.ndarray, lengths) -> None:
+        Yd = self._pre_transform_device(self._checked(X))
+        if self._sieve.requires_fitting:
+            self._sieve._fit_valid(nat.to_host(Yd), lengths)
 
     def _transform(self, X: np.ndarray) -> np.ndarray:
         t = nat.torch()

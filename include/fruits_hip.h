@@ -306,6 +306,13 @@ int fr_sieve(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_st
 int fr_sieve_implicit(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride,
                       const double *d_q, int32_t Q, int32_t segments, double *d_out,
                       int64_t out_stride, void *stream);
+/* The same on series of their own lengths: series n is d_A[n, :d_lengths[n]] ((N) int32 on the
+ * device, 1 <= d_lengths[n] <= T, not checked); the indicator is counted there, PPV divides by
+ * d_lengths[n], CPV by d_lengths[n] rounded up to even - what fr_sieve_implicit returns for the
+ * truncated row.  The elements behind a series' length are never read. */
+int fr_sieve_implicit_lengths(int32_t kind, const double *d_A, int64_t N, int64_t T, int64_t a_stride,
+                              const int32_t *d_lengths, const double *d_q, int32_t Q,
+                              int32_t segments, double *d_out, int64_t out_stride, void *stream);
 
 /* ------------------------------------------------------------------ fused pipeline
  * ISS + sieves in ONE launch: replaces the loop of FruitSlice.transform
@@ -315,7 +322,9 @@ int fr_sieve_implicit(int32_t kind, const double *d_A, int64_t N, int64_t T, int
  * per-series cuts (FR_SIEVE_SERIES_CUTS).  LPI is not fused (FR_E_LIMIT).  FR_SIEVE_PPV /
  * FR_SIEVE_CPV (| FR_SIEVE_SEGMENTS): inc 0, C1 = 2 with the cuts {0, T}, Q1 = the number of
  * thresholds (>= 1; with segments >= 2), which h_quant holds in the SIEVE's order - they are not
- * sorted; Q1 features, Q1 - 1 with segments, as fr_sieve_implicit computes them.  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
+ * sorted; Q1 features, Q1 - 1 with segments, as fr_sieve_implicit computes them.  With
+ * FR_SIEVE_SERIES_CUTS the two cuts of a PPV / CPV are slots of the per-series table, the second
+ * one holding the series' own length (fr_pipeline_set_lengths).  Feature (n, k*per_sum + col_s + j*(Q1_s-1) + q) is the reference's
  * column order (iterated sum, then sieve, then segment, then band).
  *
  *   kinds/incs/C1/Q1   per sieve; Q1 is ignored for END
@@ -406,6 +415,20 @@ int fr_pipeline_prepare_cached(fr_pipeline_t *pipeline, int64_t N, int32_t group
  * N series. */
 int fr_pipeline_set_series_cuts(fr_pipeline_t *pipeline, const int32_t *d_cuts, int64_t N,
                                 int32_t slots);
+/* Per-series lengths for the following fr_pipeline_run calls with exactly N series: device (N)
+ * int32, 1 <= d_lengths[n] <= T (not checked); series n is its first d_lengths[n] elements, what
+ * lies behind them must be finite and influences no feature.  The iterated sums need nothing (they
+ * are causal); the lengths are read by
+ *   - the statistics pre-pass of a fused STD (fr_pipeline_set_preparation): mean and deviation of
+ *     the first d_lengths[n] prepared elements, in numpy's summation order for that length;
+ *   - the divisions of PPV / CPV sieves created with FR_SIEVE_SERIES_CUTS (C1 = 2; the second
+ *     slot holds the series' length, up to which the indicator is counted): count / length, and
+ *     2 * count / (length rounded up to even).  Running such a pipeline without lengths fails.
+ * The band sieves and END take a series' extent from the cut table alone
+ * (fr_pipeline_set_series_cuts: cuts resolved for that length).  A pipeline with per-series cuts
+ * has no run-time compiled kernel: it runs the generic instance.  The array belongs to the caller
+ * and must stay valid until the runs that use it have finished; NULL: every series is T long. */
+int fr_pipeline_set_lengths(fr_pipeline_t *pipeline, const int32_t *d_lengths, int64_t N);
 int fr_pipeline_run(fr_pipeline_t *pipeline, const double *d_X, int64_t N, int64_t D, int64_t T,
                     const double *d_lookup, int64_t lookup_rows, double *d_feats,
                     int64_t feat_stride, void *d_work, int64_t work_bytes, int32_t groups,
@@ -450,6 +473,13 @@ int fr_release_scratch(void);
  * population standard deviation (np.std), or 1 when div_std == 0. */
 int fr_standardize(const double *d_X, int64_t rows, int64_t T, int32_t div_std, double eps,
                    double *d_out, void *stream);
+/* The same on series of their own lengths: d_X is (N, D, T), row (n, d) is standardised with the
+ * mean and deviation of its first d_lengths[n] elements ((N) int32 on the device, 1 <=
+ * d_lengths[n] <= T, not checked), summed in numpy's order for that length - bit for bit what
+ * fr_standardize returns for the truncated row.  The tail [d_lengths[n], T) of d_out is 0. */
+int fr_standardize_lengths(const double *d_X, int64_t N, int64_t D, int64_t T,
+                           const int32_t *d_lengths, int32_t div_std, double eps, double *d_out,
+                           void *stream);
 
 /* ------------------------------------------------------------------ CosWISS ("next" row)
  * CosWISS.batch_transform without ffn / dropout (fruits/iss/cos.py:11-49,167-181,
