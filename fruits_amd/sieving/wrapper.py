@@ -46,8 +46,11 @@ class _SieveWrapper(FeatureSieve):
                 del inner._cache
 
     def _supports_lengths(self) -> bool:
-        # (where the wrapper is its inner sieve at another differencing order: the rows it forms
-        # otherwise - a shift > 1, sums of increments - are causal too, but only this is tested)
+        # (where the wrapper is its inner sieve at another differencing order - INC(NPI),
+        # INC(MAX, depth=0), INT(NPI(inc=-1)), INT(MAX) run fused and materialising, over every
+        # preparateur, semiring and weighting of the gate's list, in tests/test_lengths_batch_gpu.py.
+        # The rows it forms otherwise - a shift > 1, sums of increments - are causal too, but no
+        # test runs them with lengths, so they stay outside.)
         return self._reduced() is not None and self._sieve._supports_lengths()
 
     def transform_device(self, Ad, out, col: int, lengths=None):
