@@ -14,8 +14,13 @@ n u / (1 - n u) against n u and the 2^-64 of the extended-precision side the res
 with.  No measured number enters: R and A come from ``dtype=np.longdouble`` runs of the oracle
 on the inputs (and, for a weighted plan, on the lookup) the code under test was given.
 
+A fused launch leaves features, not rows: ``probe_positions`` says where to read the rows
+through ``END``, ``feature_reference`` carries the elementwise bound over to the features the
+fused epilogue forms (``MAX`` / ``MIN`` selections, ``MPI`` band means of the rows and of their
+first increments), ``check_features`` asserts it (tests/test_fused_bounds_gpu.py).
+
 Not a conftest: the modules that need it import it by name.  The largest ``err / bound`` of
-every family that went through ``check_bound`` is kept in ``RATIOS``; ``print_ratios`` (called
+every family that went through ``check_bound`` / ``check_features`` is kept in ``RATIOS``; ``print_ratios`` (called
 by a module fixture's teardown) prints them as ``ISS-RATIO family: ...`` and clears them.
 """
 import math
@@ -203,6 +208,146 @@ def check_bound(got, hp, A, n, what, family=None):
 def violates(got, hp, A, n):
     """Whether ``got`` lies outside the bound somewhere (the sensitivity checks)."""
     return bool((ratio(got, hp, A, n) > 1.0).any())
+
+
+# ------------------------------------------------------------------ features of a fused launch
+# A fused launch never writes the rows: what it leaves are features.  The bounds below carry the
+# elementwise bound b = bound(n, A) of the rows over to the features the fused epilogue forms.
+_PROBES = (0, 1, 2, 3, 4, 5, 7, 8, 63, 64, 127, 128, 129, 255, 256, 257, 383, 384, 511, 512, 513,
+           767, 768, 1023, 1024, 1025, 2047, 2048, 2049)
+FEATURE_KINDS = ("END", "MAX", "MIN", "MPI0", "MPI1")
+
+
+def probe_positions(T):
+    """The sorted 0-based positions in [0, T) where the parts of a scan meet: the lane boundaries
+    for 2 and 4 elements per lane (1 ... 8), the wave boundaries of both chunk sizes (a wave of 64
+    lanes: 128 / 256 elements; 63, 64), the piece boundaries of the wave-per-series kernel (128,
+    256, 384), the chunk boundaries (512 / 1024 and their multiples up to 2048), each with its
+    neighbours, and T // 3, T // 2 and the two last elements of the series.  An ``END`` sieve reads
+    position p with the cut p + 1."""
+    return sorted({p for p in _PROBES + (T // 3, T // 2, T - 2, T - 1) if 0 <= p < T})
+
+
+def segments(T, cut):
+    """[(lo, hi)] - the element sets [lo, hi) of a segment sieve with the integer cuts ``cut`` on
+    series of T elements (oracle/ref_numpy.py transformed_cuts: sorted, a leading 0)."""
+    c = orc.transformed_cuts(1, T, list(cut) if isinstance(cut, (list, tuple)) else cut)[0]
+    return [(int(c[j]), int(c[j + 1])) for j in range(len(c) - 1)]
+
+
+def open_band(A):
+    """The finite threshold pair (-2 max A, +2 max A) of a band that takes every element: every
+    |value| and every |increment| <= 2 max|row| lies strictly inside, none near a threshold
+    (any row within the bound of hp has |row| <= (1 + c n u) A)."""
+    w = 2.0 * float(np.max(A)) if np.size(A) else 1.0
+    return np.array([-w, w]) if w > 0 else np.array([-1.0, 1.0])
+
+
+def feature_reference(kind, hp, A, n, cut):
+    """(ref, bnd): what a feature of the rows is compared with and the bound on the difference, both
+    (K, N, C) in extended precision, one column per segment of ``cut``; from (hp, A, n) of
+    ``reals_reference`` / ``coswiss_reference``.  Write b = bound(n, A) (elementwise: |row - hp|
+    <= b), S = [lo, hi) for the elements of a segment, m = |S|.  An empty segment gives 0 on every
+    side (oracle/ref_numpy.py band_value): ref 0, bound 0.  The bands are open (``open_band``):
+    every element of S takes part, on the device as in the reference.
+
+    ``END``   the row at hi - 1: ref hp[hi-1], bound b[hi-1] - the element itself.
+    ``MAX`` / ``MIN``   ref max / min of hp over S.  With |row_t - hp_t| <= b_t for every t in S,
+              max row <= max (hp_t + b_t) <= max hp + max b and max row >= row at hp's argmax
+              >= max hp - max b (MIN alike): bound max_{t in S} b_t.  A selection rounds nothing.
+    ``MPI0``  the mean of the row over S: ref mean hp_t.  The device sums m rounded elements in
+              some order - m - 1 additions, each of relative u on a partial sum of magnitude <=
+              sum |row_t| - and divides once: m roundings on sum |row_t| / m <= (1 + c n u) mean
+              A_t; plus the elements' own error, mean b_t:
+                  bound = mean b_t + c m u mean A_t
+              (c = 2 takes gamma_m against m u and the factor 1 + c n u, as in ``bound``).
+    ``MPI1``  the mean over S of the zero-padded first increments d_t = row_t - row_(t-1), d_0 = 0:
+              ref the mean of hp's.  The device takes d_t as the difference of two emitted values
+              - error b_t + b_(t-1), and one rounding of the subtraction, u |d_t| <= u (A_t +
+              A_(t-1)) - or as the summand of the row's last cumulative sum before it is added:
+              that summand's term paths are those of row_t without the additions of that sum, so
+              its error is below b_t.  Either way |d_t - d_t(hp)| <= b_t + b_(t-1) + u (A_t +
+              A_(t-1)), and the mean adds m roundings on mean |d_t| <= mean (A_t + A_(t-1)):
+                  bound = mean (b_t + b_(t-1)) + c (m + 1) u mean (A_t + A_(t-1))
+              The padded d_0 is the constant 0 on both sides: its terms are b = A = 0.
+    """
+    hp = np.asarray(hp, dtype=HP)
+    A = np.asarray(A, dtype=HP)
+    b = bound(n, A)
+    if kind == "MPI1":
+        d, bd, Ad = np.zeros_like(hp), np.zeros_like(hp), np.zeros_like(hp)
+        d[..., 1:] = hp[..., 1:] - hp[..., :-1]
+        bd[..., 1:] = b[..., 1:] + b[..., :-1]
+        Ad[..., 1:] = A[..., 1:] + A[..., :-1]
+    segs = segments(hp.shape[-1], cut)
+    ref = np.zeros(hp.shape[:-1] + (len(segs),), dtype=HP)
+    bnd = np.zeros_like(ref)
+    for j, (lo, hi) in enumerate(segs):
+        m = hi - lo
+        if m <= 0:
+            continue
+        if kind == "END":
+            ref[..., j], bnd[..., j] = hp[..., hi - 1], b[..., hi - 1]
+        elif kind in ("MAX", "MIN"):
+            ref[..., j] = (np.max if kind == "MAX" else np.min)(hp[..., lo:hi], axis=-1)
+            bnd[..., j] = np.max(b[..., lo:hi], axis=-1)
+        elif kind == "MPI0":
+            ref[..., j] = np.mean(hp[..., lo:hi], axis=-1)
+            bnd[..., j] = np.mean(b[..., lo:hi], axis=-1) + HP(C * m * U) * np.mean(A[..., lo:hi], axis=-1)
+        elif kind == "MPI1":
+            ref[..., j] = np.mean(d[..., lo:hi], axis=-1)
+            bnd[..., j] = (np.mean(bd[..., lo:hi], axis=-1)
+                           + HP(C * (m + 1) * U) * np.mean(Ad[..., lo:hi], axis=-1))
+        else:
+            raise ValueError("no feature bound for %r" % (kind,))
+    return ref, bnd
+
+
+def oracle_features(kind, rows, cut, band):
+    """The float64 numpy oracle's features ((K, N, C)) of float64 rows (K, N, T): its sieve
+    backends with the thresholds ``band`` (the sensitivity and CPU checks; ``END`` takes none)."""
+    rows = np.asarray(rows, dtype=np.float64)
+    K, N, T = rows.shape
+    cuts = orc.transformed_cuts(N, T, list(cut) if isinstance(cut, (list, tuple)) else cut)
+    out = []
+    for k in range(K):
+        if kind == "END":
+            out.append(orc.end_transform(rows[k], cuts))
+        elif kind in ("MAX", "MIN"):
+            out.append(orc.BACKENDS[kind](rows[k], cuts, band))
+        else:
+            out.append(orc.mpi_backend(orc.pre_transform(rows[k], int(kind[3:])), cuts, band))
+    return np.stack(out)
+
+
+def feature_ratio(got, ref, bnd):
+    """Elementwise |got - ref| / bnd (0 where both vanish; inf where bnd == 0 and got != ref)."""
+    err = np.abs(np.asarray(got).astype(HP) - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(bnd > 0, err / np.where(bnd > 0, bnd, 1), np.where(err > 0, np.inf, 0.0))
+    return r.astype(np.float64)
+
+
+def check_features(got, ref, bnd, what, family=None):
+    """``check_bound`` for features: asserts elementwise ``|got - ref| <= bnd`` with (ref, bnd) of
+    ``feature_reference``; where the bound is 0 (an empty segment, the leading zeros of a row) the
+    values must be equal.  Records the largest ``err / bound`` under ``family``; returns it."""
+    got = np.asarray(got)
+    assert got.shape == ref.shape == bnd.shape, (what, got.shape, ref.shape, bnd.shape)
+    assert np.isfinite(got).all(), what
+    zero = bnd == 0
+    assert np.array_equal(got[zero], ref[zero].astype(np.float64)), (what, "bound == 0 but got != ref")
+    r = feature_ratio(got, ref, bnd)
+    worst = float(r.max()) if r.size else 0.0
+    if family is not None:
+        RATIOS[family] = max(RATIOS.get(family, 0.0), worst)
+    if not worst <= 1.0:
+        at = np.unravel_index(int(np.argmax(r)), r.shape)
+        raise AssertionError(
+            f"{what}: |got - ref| exceeds the derived bound by a factor {worst:.3g} at "
+            f"(k, n, column) = {tuple(int(i) for i in at)}: got {got[at]!r}, ref {float(ref[at])!r}, "
+            f"bound {float(bnd[at])!r}; {int((r > 1).sum())} of {r.size} entries outside")
+    return worst
 
 
 def positive_precondition(hp, A):

@@ -105,6 +105,70 @@ def test_coswiss_oracle_within_bound(exponent, T):
                 assert ib.violates(ref * (1 + 1e-9), hp, A, n), what
 
 
+def test_probe_positions():
+    """Sorted, inside [0, T), the ends of the series and every boundary below T among them."""
+    for T in (1, 2, 63, 300, 1025, 3000):
+        p = ib.probe_positions(T)
+        assert p == sorted(set(p)) and p[0] == 0 and p[-1] == T - 1 and all(0 <= v < T for v in p)
+        want = {0, T - 1, T // 2, T // 3} | {v for v in (63, 64, 127, 128, 129, 255, 256, 257, 383, 384,
+                                                          511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049)
+                                             if v < T}
+        assert (want | ({T - 2} if T >= 2 else set())) <= set(p)
+    assert ib.probe_positions(1) == [0] and ib.probe_positions(2) == [0, 1]
+    assert ib.segments(300, [100, -1]) == [(0, 100), (100, 300)]
+    assert ib.segments(2, [0, -1]) == [(0, 0), (0, 2)]
+
+
+FEATURE_WEIGHTINGS = ("none", "indices", "indices_total")
+
+
+@pytest.mark.parametrize("T", [1, 2, 63, 300, 1025])
+@pytest.mark.parametrize("weighting", FEATURE_WEIGHTINGS)
+def test_feature_bounds_hold_the_oracle(weighting, T):
+    """The feature bounds of ``ib.feature_reference`` - END at the probe cuts; MAX, MIN, MPI(inc=0)
+    and MPI(inc=1) over [0, T//3) and [T//3, T) with open bands -: the float64 numpy oracle's
+    features lie inside them against the long-double ones, and on the positive input (A == hp:
+    ``positive_precondition`` holds of the oracle alone) the features of the rows times (1 + 1e-9)
+    lie outside.  The one case without a sensitivity half is MPI(inc=1) at T = 1: its only
+    feature is the padded increment, the constant 0, bound 0."""
+    spec = ib.WEIGHTINGS[weighting]
+    probes = [p + 1 for p in ib.probe_positions(T)]
+    for dist in ("normal", "uniform"):
+        X = ib.reals_input(dist, N_HOST, 3, T)
+        lookup, total = orc._weight_lookup(spec, X, X)
+        hp, A, n = ib.reals_reference(X, ib.WORDS, "EXTENDED", None, lookup, total)
+        rows = orc.iss_transform(X, ib.WORDS, "EXTENDED", None, lookup, total)
+        band = ib.open_band(A)
+        assert band[0] < -float(np.abs(rows).max()) * 1.5 and float(np.abs(rows).max()) * 1.5 < band[1]
+        if dist == "uniform":
+            assert ib.positive_precondition(hp, A) <= 1.0
+        for kind in ib.FEATURE_KINDS:
+            cut = probes if kind == "END" else [T // 3, -1]
+            what = f"{kind} T={T} {weighting} {dist}"
+            ref, bnd = ib.feature_reference(kind, hp, A, n, cut)
+            assert ref.shape == (hp.shape[0], N_HOST, len(cut)) and (bnd >= 0).all(), what
+            ib.check_features(ib.oracle_features(kind, rows, cut, band), ref, bnd, what)
+            if dist == "uniform" and not (kind == "MPI1" and T == 1):
+                off = ib.oracle_features(kind, rows * (1 + 1e-9), cut, band)
+                assert (ib.feature_ratio(off, ref, bnd) > 1.0).any(), what
+                with pytest.raises(AssertionError):
+                    ib.check_features(off, ref, bnd, what)
+
+
+def test_check_features_wants_equality_where_the_bound_is_zero():
+    """An empty segment ([0, T//3) at T = 2) and the leading zeros of a row: bound 0, values equal."""
+    X = ib.reals_input("uniform", 2, 3, 2)
+    hp, A, n = ib.reals_reference(X, ib.WORDS)
+    for kind in ib.FEATURE_KINDS[1:]:
+        ref, bnd = ib.feature_reference(kind, hp, A, n, [0, -1])
+        assert (ref[..., 0] == 0).all() and (bnd[..., 0] == 0).all()
+        got = ref.astype(np.float64)
+        ib.check_features(got, ref, bnd, kind)
+        got[0, 0, 0] = 1e-300
+        with pytest.raises(AssertionError):
+            ib.check_features(got, ref, bnd, kind)
+
+
 def test_check_bound_sees_what_the_old_bars_passed():
     """The faults the row-wise 1e-6 bar let through: an exp table rounded through float, a wrong
     early element of a row that grows by 1e4, a carry dropped at a chunk boundary."""
