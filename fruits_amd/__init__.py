@@ -18,6 +18,14 @@ from .iss.iss import ISS, ISSMode
 __version__ = "0.1.0"
 
 
+def __getattr__(name: str):
+    # ``fruits_amd.nn`` (the differentiable ISS) imports torch and torch.nn: loaded on first use
+    if name == "nn":
+        import importlib
+        return importlib.import_module(".nn", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def release_scratch() -> None:
     """Frees the device and page-locked scratch a device-side ``Fruit.fit`` keeps for the next
     one (fr_release_scratch); not in the reference."""

@@ -48,6 +48,7 @@ EXPORTS = [
     "fr_prep_mask", "fr_prep_pointwise",
     "fr_letter_rows", "fr_rows_unshift",
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
+    "fr_iss_backward",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -1169,3 +1170,32 @@ def rows_unshift(Ad, shifts, out=None, shifts_d=None):
     check(lib().fr_rows_unshift(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(sh_d),
                                 _i32p(sh), dptr(out), stream_ptr()), "fr_rows_unshift")
     return out
+
+
+# ----------------------------------------------------------------------- backward pass
+def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None):
+    """fr_iss_backward: the gradient ``(N, D, T)`` of unweighted Reals iterated sums with respect
+    to ``Xd``.  ``prefix_plan``: the plan of the distinct prefixes, each with depth 1; ``Sd``
+    ``(V, N, T)`` its output on ``Xd``; ``G`` the upstream gradient as an ``(N, K, T)`` device
+    tensor of any strides; ``row_prefix`` ``(K)`` int32 host array, the row of ``Sd`` that output
+    row k is; ``work``: a ``(V, N, T)`` scratch if the caller keeps one."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
+    K = int(rp.shape[0])
+    V = prefix_plan.rows
+    if G.dtype != t.float64 or tuple(G.shape) != (N, K, T) or G.device != Xd.device:
+        raise TypeError("the upstream gradient must be a float64 (N, K, T) tensor on the input's device")
+    if Sd.dtype != t.float64 or tuple(Sd.shape) != (V, N, T) or not Sd.is_contiguous():
+        raise TypeError("the prefix sums must be a contiguous float64 (V, N, T) device tensor")
+    if work is None:
+        work = t.empty((V, N, T), dtype=t.float64, device=Xd.device)
+    elif work.dtype != t.float64 or work.numel() < V * N * T or not work.is_contiguous():
+        raise TypeError("the scratch must be a contiguous float64 device tensor of V * N * T elements")
+    dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
+    sn, sk, st = (int(s) for s in G.stride())
+    check(lib().fr_iss_backward(prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
+                                dptr(Sd), dptr(G), C.c_int64(K), C.c_int64(sn), C.c_int64(sk),
+                                C.c_int64(st), _i32p(rp), dptr(work), dptr(dX), stream_ptr()),
+          "fr_iss_backward")
+    return dX

@@ -23,7 +23,8 @@ HEADERS = ["kernels.h", "plan.h", "jit.h", "walk.h", "walk_device.h", "walk_fuse
 
 
 # headers that only some units include: {header: unit names}
-CAPI = ("capi_core", "capi_plan", "capi_walk", "capi_pipeline", "capi_select", "capi_kernels")
+CAPI = ("capi_core", "capi_plan", "capi_walk", "capi_pipeline", "capi_select", "capi_kernels",
+        "capi_grad")
 LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep"),
                  "select_partition.h": ("kernels_select",),
                  "capi_common.h": CAPI,
@@ -42,6 +43,8 @@ def units():
            ("kernels_filter", "kernels_filter.hip", ["-ffp-contract=off"]),
            # the virtual rows of generic words: moves and fabs, compared bit for bit
            ("kernels_letters", "kernels_letters.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
+           # the backward pass: every product rounded, as the derived bound of its tests counts them
+           ("kernels_grad", "kernels_grad.hip", ["-ffp-contract=off"]),
            ("jit", "jit.cpp", []),
            # (the registry also holds the mixed kernels of the one-group programs and their
            # tail programs: no contraction, like the programs' own units below)

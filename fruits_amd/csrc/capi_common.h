@@ -52,5 +52,7 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 bool stream_is_capturing(hipStream_t st);
 int current_device_id();
 int claim_device(fr::Plan &p, const char *who);
+// frees the backward tables a plan holds (capi_grad.cpp; fr_plan_destroy)
+void release_grad_tables(fr::Plan &p);
 
 }  // namespace fr::capi

@@ -1,0 +1,250 @@
+// fr_iss_backward: the gradient of unweighted Reals iterated sums with respect to their input.
+// The trie - parents, children, letters - is read off the plan the plan compiler built
+// (plan.cpp); the kernels are those of kernels_grad.hip.
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "capi_common.h"
+#include "kernels.h"
+
+using namespace fr::capi;
+
+namespace {
+
+// The backward tables of a prefix plan: host copies, one device blob.  The trie part is a
+// function of the plan; the rows of G a node gathers are the caller's (`row_prefix`), kept to
+// see whether a later call brings the same.
+struct GradTables {
+  std::vector<int32_t> row_prefix;
+  std::vector<int32_t> parent_srow, child_begin, child, fac_begin, fac, g_begin, g_row,
+      level_nodes, level_begin, dim_begin, dim_item;
+  int64_t dims = 0;        // dimensions dim_begin covers (the D of the call it was built for)
+  void *d_blob = nullptr;
+  const int32_t *d_parent_srow = nullptr, *d_child_begin = nullptr, *d_child = nullptr,
+                *d_fac_begin = nullptr, *d_fac = nullptr, *d_g_begin = nullptr, *d_g_row = nullptr,
+                *d_level_nodes = nullptr, *d_dim_begin = nullptr, *d_dim_item = nullptr;
+};
+
+// Builds the host tables; "" or what is wrong with the plan / the row map.
+std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K, int64_t D,
+                         GradTables &g) {
+  const int V = (int)p.nodes.size();
+  if (p.cos || p.weighting != 0 || p.semiring != fr::kSemiReals)
+    return "the plan is not an unweighted Reals trie plan";
+  if (p.K != V) return "not a prefix plan: every node has to emit exactly one row";
+  // the trie behind the DFS order: an only child continues its parent's frame (F_CHAIN), the
+  // other nodes hang below the last node of the level above (as in plan.cpp, pieced)
+  std::vector<int> parent(V, -1), depth(V, 1), srow(V, -1);
+  for (int u = 0; u < p.units(); ++u) {
+    int last_at[fr::kMaxLevels + 1];
+    for (int &x : last_at) x = -1;
+    for (int i = p.unit_begin[u]; i < p.unit_begin[u + 1]; ++i) {
+      const fr::NodeDesc &nd = p.nodes[i];
+      if (nd.level < 0 || nd.level >= fr::kMaxLevels) return "a node beyond the frame limit";
+      parent[i] = (nd.flags & fr::F_CHAIN) ? last_at[nd.level] : (nd.level > 0 ? last_at[nd.level - 1] : -1);
+      last_at[nd.level] = i;
+      if (parent[i] >= 0) depth[i] = depth[parent[i]] + 1;
+      if (nd.emit_count != 1) return "not a prefix plan: every node has to emit exactly one row";
+      srow[i] = p.emit_rows[nd.emit_begin];
+      if (srow[i] < 0 || srow[i] >= V) return "an output row outside the plan";
+    }
+  }
+  std::vector<int> node_of_row(V, -1);
+  for (int i = 0; i < V; ++i) {
+    if (node_of_row[srow[i]] >= 0) return "not a prefix plan: two nodes emit one row";
+    node_of_row[srow[i]] = i;
+  }
+  g.parent_srow.assign(V, -1);
+  std::vector<std::vector<int32_t>> kids(V), grows(V);
+  for (int i = 0; i < V; ++i)
+    if (parent[i] >= 0) {
+      g.parent_srow[i] = srow[parent[i]];
+      kids[parent[i]].push_back(i);
+    }
+  for (int64_t k = 0; k < K; ++k) {
+    if (row_prefix[k] < 0 || row_prefix[k] >= V)
+      return "row " + std::to_string(k) + " of the gradient names prefix " +
+             std::to_string(row_prefix[k]) + " of " + std::to_string(V);
+    grows[node_of_row[row_prefix[k]]].push_back((int32_t)k);
+  }
+  g.row_prefix.assign(row_prefix, row_prefix + K);
+  g.child_begin.assign(1, 0);
+  g.g_begin.assign(1, 0);
+  g.fac_begin.assign(1, 0);
+  g.child.clear();
+  g.g_row.clear();
+  g.fac.clear();
+  std::vector<std::vector<int32_t>> items((size_t)D);
+  for (int i = 0; i < V; ++i) {
+    g.child.insert(g.child.end(), kids[i].begin(), kids[i].end());
+    g.child_begin.push_back((int32_t)g.child.size());
+    g.g_row.insert(g.g_row.end(), grows[i].begin(), grows[i].end());
+    g.g_begin.push_back((int32_t)g.g_row.size());
+    // the letter: one factor code per occurrence (row | FAC_DIV), the occurrences of a
+    // dimension adjacent -> {dimension, exponent}
+    const fr::NodeDesc &nd = p.nodes[i];
+    for (int j = 0; j < nd.fac_count; ++j) {
+      const int32_t code = p.factors[nd.fac_begin + j];
+      const int row = code & fr::FAC_ROW_MASK;
+      if (row >= (int)p.row_src.size() || p.row_src[row] < 0) return "a factor that is no input dimension";
+      const int32_t dim = p.row_src[row];
+      if (dim >= D) return "a factor beyond the input's dimensions";
+      const int32_t sign = (code & fr::FAC_DIV) ? -1 : 1;
+      const size_t begin = (size_t)g.fac_begin.back() * 2;
+      if (g.fac.size() > begin && g.fac[g.fac.size() - 2] == dim) {
+        g.fac.back() += sign;
+      } else {
+        g.fac.push_back(dim);
+        g.fac.push_back(sign);
+      }
+    }
+    for (size_t f = (size_t)g.fac_begin.back(); f < g.fac.size() / 2; ++f) {
+      if (g.fac[2 * f + 1] == 0) return "a letter with cancelling occurrences of one dimension";
+      items[(size_t)g.fac[2 * f]].push_back(i);
+      items[(size_t)g.fac[2 * f]].push_back((int32_t)f);
+    }
+    g.fac_begin.push_back((int32_t)(g.fac.size() / 2));
+  }
+  g.dim_begin.assign(1, 0);
+  g.dim_item.clear();
+  for (int64_t d = 0; d < D; ++d) {
+    g.dim_item.insert(g.dim_item.end(), items[(size_t)d].begin(), items[(size_t)d].end());
+    g.dim_begin.push_back((int32_t)(g.dim_item.size() / 2));
+  }
+  g.dims = D;
+  // the nodes by falling depth (stable: DFS order within a depth)
+  int deepest = 0;
+  for (int i = 0; i < V; ++i) deepest = std::max(deepest, depth[i]);
+  g.level_nodes.clear();
+  g.level_begin.assign(1, 0);
+  for (int dep = deepest; dep >= 1; --dep) {
+    for (int i = 0; i < V; ++i)
+      if (depth[i] == dep) g.level_nodes.push_back(i);
+    g.level_begin.push_back((int32_t)g.level_nodes.size());
+  }
+  return "";
+}
+
+int upload_tables(GradTables &g) {
+  const std::vector<int32_t> *parts[] = {&g.parent_srow, &g.child_begin, &g.child, &g.fac_begin, &g.fac,
+                                         &g.g_begin, &g.g_row, &g.level_nodes, &g.dim_begin, &g.dim_item};
+  const int32_t **dst[] = {&g.d_parent_srow, &g.d_child_begin, &g.d_child, &g.d_fac_begin, &g.d_fac,
+                           &g.d_g_begin, &g.d_g_row, &g.d_level_nodes, &g.d_dim_begin, &g.d_dim_item};
+  size_t off = 0, at[10];
+  for (int i = 0; i < 10; ++i) {
+    at[i] = off;
+    off = align_up(off + parts[i]->size() * 4 + 4, 64);   // (+ 4: an empty table still has an address)
+  }
+  std::vector<char> host(off, 0);
+  for (int i = 0; i < 10; ++i)
+    if (!parts[i]->empty()) std::memcpy(host.data() + at[i], parts[i]->data(), parts[i]->size() * 4);
+  void *d = nullptr;
+  HIP_TRY(hipMalloc(&d, host.size()));
+  hipError_t e = hipMemcpy(d, host.data(), host.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return hip_fail(e, "hipMemcpy(backward tables)");
+  }
+  g.d_blob = d;
+  for (int i = 0; i < 10; ++i) *dst[i] = reinterpret_cast<const int32_t *>(static_cast<char *>(d) + at[i]);
+  return FR_OK;
+}
+
+}  // namespace
+
+namespace fr::capi {
+void release_grad_tables(fr::Plan &p) {
+  GradTables *g = static_cast<GradTables *>(p.grad);
+  if (!g) return;
+  if (g->d_blob) (void)hipFree(g->d_blob);
+  delete g;
+  p.grad = nullptr;
+}
+}  // namespace fr::capi
+
+extern "C" {
+
+int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                    const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
+                    int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
+                    double *d_A, double *d_dX, void *stream) {
+  if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, "fr_iss_backward: null plan");
+  if (N < 0 || D < 1 || T < 0 || K < 0 || g_n_stride < 0 || g_k_stride < 0 || g_t_stride < 0)
+    return fail(FR_E_ARG, "fr_iss_backward: bad shape");
+  if (K > 0 && !h_row_prefix) return fail(FR_E_ARG, "fr_iss_backward: null host table");
+  fr::Plan &p = *prefix_plan->p;
+  if (p.max_dim > D)
+    return fail(FR_E_DIM, "fr_iss_backward: a word references dimension " + std::to_string(p.max_dim) +
+                              " but the input has only " + std::to_string(D));
+  const int64_t V = (int64_t)p.nodes.size();
+  if (N > 0 && T > 0) {
+    if (!d_X || !d_dX || (K > 0 && !d_G) || (V > 0 && (!d_S || !d_A)))
+      return fail(FR_E_ARG, "fr_iss_backward: null device pointer");
+    if (d_X == d_dX) return fail(FR_E_ARG, "fr_iss_backward: the gradient must not alias the input");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(p.mu);
+  GradTables *g = static_cast<GradTables *>(p.grad);
+  const bool same = g && g->dims == D && (int64_t)g->row_prefix.size() == K &&
+                    (K == 0 || std::memcmp(g->row_prefix.data(), h_row_prefix, (size_t)K * 4) == 0);
+  if (!same) {
+    // (the tables are checked on the host before anything is uploaded or launched)
+    GradTables fresh;
+    const std::string why = build_tables(p, h_row_prefix, K, D, fresh);
+    if (!why.empty()) return fail(FR_E_ARG, "fr_iss_backward: " + why);
+    if (N == 0 || T == 0) return FR_OK;
+    if (stream_is_capturing(st))
+      return fail(FR_E_ARG, "fr_iss_backward: the stream is being captured and the backward tables "
+                            "are not on the device yet - run one backward pass before the capture");
+    int rc = claim_device(p, "fr_iss_backward");
+    if (rc != FR_OK) return rc;
+    if (g) {
+      // (kernels of an earlier call may still read the old tables)
+      HIP_TRY(hipDeviceSynchronize());
+      release_grad_tables(p);
+    }
+    g = new GradTables(std::move(fresh));
+    rc = upload_tables(*g);
+    if (rc != FR_OK) {
+      delete g;
+      return rc;
+    }
+    p.grad = g;
+  }
+  if (N == 0 || T == 0) return FR_OK;
+  int rc = claim_device(p, "fr_iss_backward");
+  if (rc != FR_OK) return rc;
+  fr::GradArgs a{};
+  a.X = d_X;
+  a.S = d_S;
+  a.G = d_G;
+  a.A = d_A;
+  a.dX = d_dX;
+  a.N = N;
+  a.D = D;
+  a.T = T;
+  a.g_n = g_n_stride;
+  a.g_k = g_k_stride;
+  a.g_t = g_t_stride;
+  a.parent_srow = g->d_parent_srow;
+  a.child_begin = g->d_child_begin;
+  a.child = g->d_child;
+  a.fac_begin = g->d_fac_begin;
+  a.fac = g->d_fac;
+  a.g_begin = g->d_g_begin;
+  a.g_row = g->d_g_row;
+  a.level_nodes = g->d_level_nodes;
+  a.dim_begin = g->d_dim_begin;
+  a.dim_item = g->d_dim_item;
+  const char *limit = "fr_iss_backward: grid too large (N, N * D or T)";
+  for (size_t l = 0; l + 1 < g->level_begin.size(); ++l) {
+    const int first = g->level_begin[l], count = g->level_begin[l + 1] - first;
+    rc = launched(fr::launch_grad_suffix(a, first, count, st), "backward suffix launch", limit);
+    if (rc != FR_OK) return rc;
+  }
+  return launched(fr::launch_grad_input(a, st), "backward input launch", limit);
+}
+
+}  // extern "C"

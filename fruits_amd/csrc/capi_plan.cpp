@@ -293,6 +293,7 @@ void fr_plan_destroy(fr_plan_t *plan) {
       for (auto &kv : js->progs) fr::jit_unload(kv.second);
       delete js;
     }
+    release_grad_tables(*plan->p);
     delete plan->p;
   }
   delete plan;

@@ -132,5 +132,26 @@ hipError_t launch_letter_rows(const double *X, int64_t N, int64_t D, int64_t T, 
                               hipStream_t st);
 hipError_t launch_rows_unshift(const double *A, int64_t K, int64_t N, int64_t T,
                                const int32_t *shift, double *out, hipStream_t st);
+// the backward pass of the Reals walk (kernels_grad.hip): the tables of the prefix trie, all on
+// the device.  Node v is the plan's node v (DFS preorder); CSR tables have V + 1 (D + 1) offsets.
+struct GradArgs {
+  const double *X;      // (N, D, T)
+  const double *S;      // (V, N, T): row r = the iterated sum of the prefix with output row r
+  const double *G;      // upstream gradient, element (n, k, t) at n * g_n + k * g_k + t * g_t
+  double *A;            // (V, N, T) scratch: the suffix sums, by node
+  double *dX;           // (N, D, T), every element written
+  int64_t N, D, T;
+  int64_t g_n, g_k, g_t;
+  const int32_t *parent_srow;             // row of S of the node's parent, -1 at depth 1
+  const int32_t *child_begin, *child;     // the node's children
+  const int32_t *fac_begin, *fac;         // the node's letter: pairs {dimension, exponent != 0}
+  const int32_t *g_begin, *g_row;         // rows k of G that the node emitted in the forward pass
+  const int32_t *level_nodes;             // the nodes by falling depth
+  const int32_t *dim_begin, *dim_item;    // per input dimension: pairs {node, index into fac}
+};
+constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)
+// A of `count` nodes of one depth, level_nodes[first ...]: their children's A must be complete
+hipError_t launch_grad_suffix(const GradArgs &a, int first, int count, hipStream_t st);
+hipError_t launch_grad_input(const GradArgs &a, hipStream_t st);
 
 }  // namespace fr

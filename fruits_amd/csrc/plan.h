@@ -182,6 +182,7 @@ struct Plan {
   int64_t last_tail_series = 0;   // FR_INFO_STATIC_TAIL: the most recent materialising launch (under mu)
   LastLaunch last_launch;         // FR_INFO_LAST_LAUNCH: the most recent run_walk, fused ones too (under mu)
   void *jit = nullptr;   // run-time compiled static programs (capi_plan.h: JitState), or nullptr
+  void *grad = nullptr;  // tables of the backward pass (capi_grad.cpp: GradTables), or nullptr (under mu)
   int device = -1;     // HIP device the uploaded tables live on (-1: nothing uploaded yet)
   std::mutex mu;       // guards `programs`, `cos->d_blob` and `device` (uploads at run time)
 

@@ -1,0 +1,181 @@
+"""Differentiable iterated sums: device tensor in, device tensor out (not in the reference).
+
+``iss(X, words, mode)`` and ``ISSLayer(words, mode)`` compute the Reals iterated sums of
+``SimpleWord``s, unweighted, of a ``torch.float64`` batch ``(N, D, T)`` that lives on the GPU,
+and carry a gradient back to ``X``.  The forward pass is ``ISS(words, mode).transform_device``
+itself - the same plan, the same launch - and returns its ``(K, N, T)`` buffer as an
+``(N, K, T)`` view.  Only ``X`` is kept for the backward pass, which recomputes the iterated
+sums of every prefix with one more walk and runs the adjoint recursion of DESIGN.md 4.14
+(``fr_iss_backward``, csrc/kernels_grad.hip).  Nothing goes through the host.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _native as nat
+from .iss.cos import CosWISS
+from .iss.iss import ISS, ISSMode
+from .iss.semiring import Reals
+from .iss.words.word import SimpleWord
+
+__all__ = ["iss", "ISSLayer", "backward_calls"]
+
+_calls = {"backward": 0}
+_OPS: dict = {}      # the functional form's ISS objects by (word strings, mode, device), oldest first
+_OPS_KEPT = 8
+
+
+def backward_calls() -> int:
+    """Backward passes launched by this process so far (one ``fr_iss_backward`` each)."""
+    return _calls["backward"]
+
+
+def _check_config(op: ISS) -> None:
+    """The refusals that depend on the configuration alone: raised before any launch."""
+    if isinstance(op, CosWISS):
+        raise NotImplementedError("CosWISS has no backward pass: only the unweighted Reals ISS has")
+    if op.weighting is not None:
+        raise NotImplementedError(
+            f"a weighting ({type(op.weighting).__name__}) has no backward pass yet: only the "
+            "unweighted ISS has")
+    if not isinstance(op.semiring, Reals):
+        raise NotImplementedError(
+            f"the semiring {type(op.semiring).__name__} has no backward pass: only Reals has")
+    op._check_supported()
+    if op._has_generic:
+        raise NotImplementedError(
+            "generic words have no backward pass: only words of SimpleWord letters have")
+
+
+def _check_input(op: ISS, X) -> None:
+    """The refusals that depend on the input: raised before any launch, the device last."""
+    if not isinstance(X, torch.Tensor):
+        raise TypeError(f"X has to be a torch.Tensor, not {type(X).__name__}")
+    if X.dim() != 3:
+        raise TypeError(f"X has to have the shape (N, D, T), not {X.dim()} dimensions")
+    if X.dtype != torch.float64:
+        raise TypeError(f"X has to be torch.float64, not {X.dtype}")
+    if len(op.words) > 0:
+        plan = op._plan(0, len(op.words))
+        if plan.max_dim > X.shape[1]:
+            raise IndexError(f"a word references dimension {plan.max_dim} but the input has "
+                             f"only {X.shape[1]}")
+    if not X.is_cuda:
+        raise TypeError(f"X has to live on the GPU, not on {X.device}: nothing here goes "
+                        "through the host")
+
+
+def _prefix_program(op: ISS):
+    """(plan, row_prefix): the plan whose words are the distinct prefixes of the words, each with
+    depth 1 (row j = the iterated sum of prefix j; the construction CosWISS._program uses for
+    its terms), and per output row of ``op`` the prefix it is the iterated sum of.  Kept with
+    the ISS's other device programs."""
+    key = ("grad", op.mode)
+    prog = op._plans.get(key)
+    if prog is not None:
+        return prog
+    index, tables, row_prefix = {}, [], []
+    for i, word in enumerate(op.words):
+        depth = op._depth(i)
+        if depth == 0:
+            continue          # (every prefix was output by an earlier word: no rows, no work)
+        tab = np.asarray(word.table(), dtype=np.int32)
+        L = tab.shape[0]
+        ident = ()
+        for k in range(L):
+            # (a prefix is its letters; a letter its exponents without trailing zeros, as the
+            # plan compiler compares them)
+            ident += (tuple(np.trim_zeros(tab[k], "b").tolist()),)
+            if ident not in index:
+                index[ident] = len(tables)
+                tables.append(tab[:k + 1])
+            if L - k <= depth:
+                row_prefix.append(index[ident])
+    plan = nat.Plan(tables, [1] * len(tables), None, nat.FR_W_NONE)
+    if plan.nodes != len(tables):
+        raise NotImplementedError("the prefix trie of these words is too deep for the walk's "
+                                  "register frames: no backward pass")
+    prog = op._plans[key] = (plan, np.asarray(row_prefix, dtype=np.int32))
+    return prog
+
+
+class _ISSFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, op):
+        Xc = X.contiguous()
+        Y = op.transform_device(Xc)          # (K, N, T)
+        ctx.op = op
+        ctx.save_for_backward(Xc)
+        return Y.permute(1, 0, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        Xc, = ctx.saved_tensors
+        plan, row_prefix = _prefix_program(ctx.op)
+        with torch.cuda.device(Xc.device):
+            S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
+            _calls["backward"] += 1
+            return nat.iss_backward(plan, Xc, S, G, row_prefix), None
+
+
+def _apply(op: ISS, X):
+    _check_input(op, X)
+    if len(op.words) > 0 and not _prefix_program(op)[0].fits(int(X.shape[2])):
+        raise NotImplementedError("the words name more input dimensions than a workgroup stages")
+    with torch.cuda.device(X.device):
+        return _ISSFunction.apply(X, op)
+
+
+def iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, weighting=None):
+    """Iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the row order of
+    ``ISS(words, mode).transform(X)`` and with its bits; differentiable with respect to ``X``.
+    ``words`` may also be an ``ISS`` that carries the configuration."""
+    if isinstance(words, ISS):
+        op = words
+    else:
+        words = list(words)
+        # the plain case keeps its device programs between calls (a training loop calls this every
+        # step): the last few word lists, found by their strings
+        key = None
+        if semiring is None and weighting is None and all(isinstance(w, SimpleWord) for w in words):
+            # (a plan's tables live on one device)
+            key = (tuple(str(w) for w in words), mode, str(getattr(X, "device", None)))
+        op = _OPS.get(key) if key is not None else None
+        if op is None:
+            op = ISS(words, mode=mode, semiring=semiring, weighting=weighting)
+            if key is not None:
+                if len(_OPS) >= _OPS_KEPT:
+                    _OPS.pop(next(iter(_OPS)))
+                _OPS[key] = op
+    _check_config(op)
+    return _apply(op, X)
+
+
+class ISSLayer(torch.nn.Module):
+    """``iss`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, semiring=None,
+                 weighting=None) -> None:
+        super().__init__()
+        self.op = words if isinstance(words, ISS) else ISS(list(words), mode=mode,
+                                                          semiring=semiring, weighting=weighting)
+        _check_config(self.op)
+
+    @property
+    def words(self):
+        return self.op.words
+
+    @property
+    def mode(self) -> ISSMode:
+        return self.op.mode
+
+    def forward(self, X):
+        return _apply(self.op, X)
+
+    def extra_repr(self) -> str:
+        return f"{len(self.op.words)} words, {self.op.mode.name}"

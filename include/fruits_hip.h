@@ -675,6 +675,34 @@ int fr_letter_rows(const double *d_X, int64_t N, int64_t D, int64_t T, const dou
 int fr_rows_unshift(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_shift,
                     const int32_t *h_shift, double *d_out, void *stream);
 
+/* ------------------------------------------------------------------ backward pass
+ * The gradient of unweighted Reals iterated sums with respect to their input: the adjoint of
+ * the recursion of fruits/iss/semiring.py:98-125 (per letter: tmp = tmp * prod_d Z[d]^el,
+ * cumsum, then the shift by one step in front of the next letter).  Not in the reference.
+ *
+ * `prefix_plan`: an unweighted FR_W_NONE Reals plan whose words are the DISTINCT prefixes of
+ *   the differentiated words, each with depth 1 - every node of its trie then emits exactly one
+ *   row (FR_E_ARG otherwise); the trie, its parents, children and letters are read off it.
+ * d_S (V, N, T), V = its rows: the output of fr_iss_run of that plan on d_X (layout K, N, T).
+ * d_G: the upstream gradient of the K differentiated rows, element (n, k, t) at
+ *   n * g_n_stride + k * g_k_stride + t * g_t_stride doubles (any strides >= 0, 0 included).
+ * h_row_prefix (K, host): the row of `prefix_plan` that output row k is the iterated sum of;
+ *   several k may name one prefix, a prefix may have none.
+ * d_A (V, N, T): scratch.  d_dX (N, D, T): the gradient, every element written (dimensions no
+ *   word names get zeros); must not alias d_X.
+ * With B_v = G_v + sum over children c of (m_c A_c)[t+1], A_v = suffix sum of B_v:
+ *   dX_d[t] = sum over nodes v of A_v[t] S_parent(v)[t-1] d m_v / d x_d [t]
+ * (S_parent = 1 at depth 1).  x^(e-1) is formed by multiplication, so an input of 0 under a
+ * positive exponent has a finite gradient.  The sums have one association whatever the grid:
+ * the result is bit-identical from run to run.  The first call for a plan (or for another
+ * h_row_prefix / D) uploads tables - it allocates and synchronises, so it cannot be captured
+ * into a hipGraph; later calls only enqueue one launch per trie depth and one more.
+ * FR_E_DIM: a word names a dimension beyond D.  FR_E_LIMIT: N, N * D or T beyond the grid. */
+int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                    const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
+                    int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
+                    double *d_A, double *d_dX, void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest
