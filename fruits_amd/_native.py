@@ -48,7 +48,7 @@ EXPORTS = [
     "fr_prep_mask", "fr_prep_pointwise",
     "fr_letter_rows", "fr_rows_unshift",
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
-    "fr_iss_backward",
+    "fr_iss_backward", "fr_iss_backward_max",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -1173,12 +1173,13 @@ def rows_unshift(Ad, shifts, out=None, shifts_d=None):
 
 
 # ----------------------------------------------------------------------- backward pass
-def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None):
+def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, entry="fr_iss_backward"):
     """fr_iss_backward: the gradient ``(N, D, T)`` of unweighted Reals iterated sums with respect
     to ``Xd``.  ``prefix_plan``: the plan of the distinct prefixes, each with depth 1; ``Sd``
     ``(V, N, T)`` its output on ``Xd``; ``G`` the upstream gradient as an ``(N, K, T)`` device
     tensor of any strides; ``row_prefix`` ``(K)`` int32 host array, the row of ``Sd`` that output
-    row k is; ``work``: a ``(V, N, T)`` scratch if the caller keeps one."""
+    row k is; ``work``: a ``(V, N, T)`` scratch if the caller keeps one.  ``entry``: the ABI
+    entry that takes these arguments (``iss_backward_max``)."""
     t = torch()
     N, D, T = _rows3(Xd)
     rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
@@ -1194,8 +1195,15 @@ def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None):
         raise TypeError("the scratch must be a contiguous float64 device tensor of V * N * T elements")
     dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
     sn, sk, st = (int(s) for s in G.stride())
-    check(lib().fr_iss_backward(prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
+    check(getattr(lib(), entry)(prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
                                 dptr(Sd), dptr(G), C.c_int64(K), C.c_int64(sn), C.c_int64(sk),
                                 C.c_int64(st), _i32p(rp), dptr(work), dptr(dX), stream_ptr()),
-          "fr_iss_backward")
+          entry)
     return dX
+
+
+def iss_backward_max(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None):
+    """fr_iss_backward_max: the gradient ``(N, D, T)`` of unweighted Arctic or Bayesian iterated
+    sums with respect to ``Xd``; the arguments of ``iss_backward``, ``prefix_plan`` created with
+    ``arctic=True`` or ``bayesian=True``."""
+    return iss_backward(prefix_plan, Xd, Sd, G, row_prefix, work, entry="fr_iss_backward_max")

@@ -1,6 +1,7 @@
-// fr_iss_backward: the gradient of unweighted Reals iterated sums with respect to their input.
-// The trie - parents, children, letters - is read off the plan the plan compiler built
-// (plan.cpp); the kernels are those of kernels_grad.hip.
+// fr_iss_backward: the gradient of unweighted Reals iterated sums with respect to their input;
+// fr_iss_backward_max: the same for the max semirings Arctic and Bayesian.  The trie - parents,
+// children, letters - is read off the plan the plan compiler built (plan.cpp); the kernels are
+// those of kernels_grad.hip.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -19,20 +20,20 @@ namespace {
 struct GradTables {
   std::vector<int32_t> row_prefix;
   std::vector<int32_t> parent_srow, child_begin, child, fac_begin, fac, g_begin, g_row,
-      level_nodes, level_begin, dim_begin, dim_item;
+      level_nodes, level_begin, dim_begin, dim_item, self_srow;
   int64_t dims = 0;        // dimensions dim_begin covers (the D of the call it was built for)
   void *d_blob = nullptr;
   const int32_t *d_parent_srow = nullptr, *d_child_begin = nullptr, *d_child = nullptr,
                 *d_fac_begin = nullptr, *d_fac = nullptr, *d_g_begin = nullptr, *d_g_row = nullptr,
-                *d_level_nodes = nullptr, *d_dim_begin = nullptr, *d_dim_item = nullptr;
+                *d_level_nodes = nullptr, *d_dim_begin = nullptr, *d_dim_item = nullptr,
+                *d_self_srow = nullptr;
 };
 
-// Builds the host tables; "" or what is wrong with the plan / the row map.
+// Builds the host tables of an unweighted trie plan of any semiring (the caller has checked
+// which); "" or what is wrong with the plan / the row map.
 std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K, int64_t D,
                          GradTables &g) {
   const int V = (int)p.nodes.size();
-  if (p.cos || p.weighting != 0 || p.semiring != fr::kSemiReals)
-    return "the plan is not an unweighted Reals trie plan";
   if (p.K != V) return "not a prefix plan: every node has to emit exactly one row";
   // the trie behind the DFS order: an only child continues its parent's frame (F_CHAIN), the
   // other nodes hang below the last node of the level above (as in plan.cpp, pieced)
@@ -57,6 +58,7 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
     node_of_row[srow[i]] = i;
   }
   g.parent_srow.assign(V, -1);
+  g.self_srow.assign(srow.begin(), srow.end());
   std::vector<std::vector<int32_t>> kids(V), grows(V);
   for (int i = 0; i < V; ++i)
     if (parent[i] >= 0) {
@@ -83,7 +85,8 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
     g.g_row.insert(g.g_row.end(), grows[i].begin(), grows[i].end());
     g.g_begin.push_back((int32_t)g.g_row.size());
     // the letter: one factor code per occurrence (row | FAC_DIV), the occurrences of a
-    // dimension adjacent -> {dimension, exponent}
+    // dimension adjacent -> {dimension, exponent}.  Arctic: one code per dimension,
+    // fac_arctic(row, coefficient) with the coefficient in bits 8-15 -> {dimension, coefficient}
     const fr::NodeDesc &nd = p.nodes[i];
     for (int j = 0; j < nd.fac_count; ++j) {
       const int32_t code = p.factors[nd.fac_begin + j];
@@ -91,6 +94,11 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
       if (row >= (int)p.row_src.size() || p.row_src[row] < 0) return "a factor that is no input dimension";
       const int32_t dim = p.row_src[row];
       if (dim >= D) return "a factor beyond the input's dimensions";
+      if (p.semiring == fr::kSemiArctic) {
+        g.fac.push_back(dim);
+        g.fac.push_back((int32_t)(int8_t)((code >> 8) & 0xff));
+        continue;
+      }
       const int32_t sign = (code & fr::FAC_DIV) ? -1 : 1;
       const size_t begin = (size_t)g.fac_begin.back() * 2;
       if (g.fac.size() > begin && g.fac[g.fac.size() - 2] == dim) {
@@ -129,16 +137,19 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
 
 int upload_tables(GradTables &g) {
   const std::vector<int32_t> *parts[] = {&g.parent_srow, &g.child_begin, &g.child, &g.fac_begin, &g.fac,
-                                         &g.g_begin, &g.g_row, &g.level_nodes, &g.dim_begin, &g.dim_item};
+                                         &g.g_begin, &g.g_row, &g.level_nodes, &g.dim_begin, &g.dim_item,
+                                         &g.self_srow};
   const int32_t **dst[] = {&g.d_parent_srow, &g.d_child_begin, &g.d_child, &g.d_fac_begin, &g.d_fac,
-                           &g.d_g_begin, &g.d_g_row, &g.d_level_nodes, &g.d_dim_begin, &g.d_dim_item};
-  size_t off = 0, at[10];
-  for (int i = 0; i < 10; ++i) {
+                           &g.d_g_begin, &g.d_g_row, &g.d_level_nodes, &g.d_dim_begin, &g.d_dim_item,
+                           &g.d_self_srow};
+  constexpr int kParts = 11;
+  size_t off = 0, at[kParts];
+  for (int i = 0; i < kParts; ++i) {
     at[i] = off;
     off = align_up(off + parts[i]->size() * 4 + 4, 64);   // (+ 4: an empty table still has an address)
   }
   std::vector<char> host(off, 0);
-  for (int i = 0; i < 10; ++i)
+  for (int i = 0; i < kParts; ++i)
     if (!parts[i]->empty()) std::memcpy(host.data() + at[i], parts[i]->data(), parts[i]->size() * 4);
   void *d = nullptr;
   HIP_TRY(hipMalloc(&d, host.size()));
@@ -148,7 +159,7 @@ int upload_tables(GradTables &g) {
     return hip_fail(e, "hipMemcpy(backward tables)");
   }
   g.d_blob = d;
-  for (int i = 0; i < 10; ++i) *dst[i] = reinterpret_cast<const int32_t *>(static_cast<char *>(d) + at[i]);
+  for (int i = 0; i < kParts; ++i) *dst[i] = reinterpret_cast<const int32_t *>(static_cast<char *>(d) + at[i]);
   return FR_OK;
 }
 
@@ -164,26 +175,43 @@ void release_grad_tables(fr::Plan &p) {
 }
 }  // namespace fr::capi
 
-extern "C" {
+namespace {
 
-int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
-                    const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
-                    int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
-                    double *d_A, double *d_dX, void *stream) {
-  if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, "fr_iss_backward: null plan");
+// The body of both entries.  `max_plus`: fr_iss_backward_max - the plan has to be an Arctic or
+// a Bayesian one, and the kernels are the segmented ones.
+int run_backward(const std::string &who, bool max_plus, fr_plan_t *prefix_plan, const double *d_X,
+                 int64_t N, int64_t D, int64_t T, const double *d_S, const double *d_G, int64_t K,
+                 int64_t g_n_stride, int64_t g_k_stride, int64_t g_t_stride,
+                 const int32_t *h_row_prefix, double *d_A, double *d_dX, void *stream) {
+  if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, who + ": null plan");
   if (N < 0 || D < 1 || T < 0 || K < 0 || g_n_stride < 0 || g_k_stride < 0 || g_t_stride < 0)
-    return fail(FR_E_ARG, "fr_iss_backward: bad shape");
-  if (K > 0 && !h_row_prefix) return fail(FR_E_ARG, "fr_iss_backward: null host table");
+    return fail(FR_E_ARG, who + ": bad shape");
+  if (K > 0 && !h_row_prefix) return fail(FR_E_ARG, who + ": null host table");
   fr::Plan &p = *prefix_plan->p;
   if (p.max_dim > D)
-    return fail(FR_E_DIM, "fr_iss_backward: a word references dimension " + std::to_string(p.max_dim) +
+    return fail(FR_E_DIM, who + ": a word references dimension " + std::to_string(p.max_dim) +
                               " but the input has only " + std::to_string(D));
   const int64_t V = (int64_t)p.nodes.size();
   if (N > 0 && T > 0) {
     if (!d_X || !d_dX || (K > 0 && !d_G) || (V > 0 && (!d_S || !d_A)))
-      return fail(FR_E_ARG, "fr_iss_backward: null device pointer");
-    if (d_X == d_dX) return fail(FR_E_ARG, "fr_iss_backward: the gradient must not alias the input");
+      return fail(FR_E_ARG, who + ": null device pointer");
+    if (d_X == d_dX) return fail(FR_E_ARG, who + ": the gradient must not alias the input");
   }
+  // which plans an entry takes (what a plan is never changes after its creation)
+  const char *kind = nullptr;
+  if (!max_plus) {
+    if (p.cos || p.weighting != 0 || p.semiring != fr::kSemiReals)
+      kind = "the plan is not an unweighted Reals trie plan";
+  } else if (p.cos) {
+    kind = "a CosWISS plan has no backward pass";
+  } else if (p.semiring != fr::kSemiArctic && p.semiring != fr::kSemiBayesian) {
+    kind = "the plan is a Reals plan - its backward pass is fr_iss_backward";
+  } else if (p.weighting != 0) {
+    kind = "a weighted plan has no backward pass";
+  } else if (p.letter_sum) {
+    kind = "a letter-sum plan (Arctic argmax) has no backward pass";
+  }
+  if (kind) return fail(FR_E_ARG, who + ": " + kind);
   hipStream_t st = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(p.mu);
   GradTables *g = static_cast<GradTables *>(p.grad);
@@ -193,12 +221,12 @@ int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_
     // (the tables are checked on the host before anything is uploaded or launched)
     GradTables fresh;
     const std::string why = build_tables(p, h_row_prefix, K, D, fresh);
-    if (!why.empty()) return fail(FR_E_ARG, "fr_iss_backward: " + why);
+    if (!why.empty()) return fail(FR_E_ARG, who + ": " + why);
     if (N == 0 || T == 0) return FR_OK;
     if (stream_is_capturing(st))
-      return fail(FR_E_ARG, "fr_iss_backward: the stream is being captured and the backward tables "
+      return fail(FR_E_ARG, who + ": the stream is being captured and the backward tables "
                             "are not on the device yet - run one backward pass before the capture");
-    int rc = claim_device(p, "fr_iss_backward");
+    int rc = claim_device(p, who.c_str());
     if (rc != FR_OK) return rc;
     if (g) {
       // (kernels of an earlier call may still read the old tables)
@@ -214,7 +242,7 @@ int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_
     p.grad = g;
   }
   if (N == 0 || T == 0) return FR_OK;
-  int rc = claim_device(p, "fr_iss_backward");
+  int rc = claim_device(p, who.c_str());
   if (rc != FR_OK) return rc;
   fr::GradArgs a{};
   a.X = d_X;
@@ -238,13 +266,38 @@ int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_
   a.level_nodes = g->d_level_nodes;
   a.dim_begin = g->d_dim_begin;
   a.dim_item = g->d_dim_item;
-  const char *limit = "fr_iss_backward: grid too large (N, N * D or T)";
+  a.self_srow = g->d_self_srow;
+  const std::string limit_text = who + ": grid too large (N, N * D or T)";
+  const char *limit = limit_text.c_str();
   for (size_t l = 0; l + 1 < g->level_begin.size(); ++l) {
     const int first = g->level_begin[l], count = g->level_begin[l + 1] - first;
-    rc = launched(fr::launch_grad_suffix(a, first, count, st), "backward suffix launch", limit);
+    rc = launched(max_plus ? fr::launch_grad_max_suffix(a, p.semiring, first, count, st)
+                           : fr::launch_grad_suffix(a, first, count, st),
+                  "backward suffix launch", limit);
     if (rc != FR_OK) return rc;
   }
-  return launched(fr::launch_grad_input(a, st), "backward input launch", limit);
+  return launched(max_plus ? fr::launch_grad_max_input(a, p.semiring, st) : fr::launch_grad_input(a, st),
+                  "backward input launch", limit);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                    const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
+                    int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
+                    double *d_A, double *d_dX, void *stream) {
+  return run_backward("fr_iss_backward", false, prefix_plan, d_X, N, D, T, d_S, d_G, K, g_n_stride,
+                      g_k_stride, g_t_stride, h_row_prefix, d_A, d_dX, stream);
+}
+
+int fr_iss_backward_max(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                        const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
+                        int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
+                        double *d_A, double *d_dX, void *stream) {
+  return run_backward("fr_iss_backward_max", true, prefix_plan, d_X, N, D, T, d_S, d_G, K,
+                      g_n_stride, g_k_stride, g_t_stride, h_row_prefix, d_A, d_dX, stream);
 }
 
 }  // extern "C"

@@ -148,10 +148,16 @@ struct GradArgs {
   const int32_t *g_begin, *g_row;         // rows k of G that the node emitted in the forward pass
   const int32_t *level_nodes;             // the nodes by falling depth
   const int32_t *dim_begin, *dim_item;    // per input dimension: pairs {node, index into fac}
+  const int32_t *self_srow;               // row of S of the node itself (the max semirings' heads)
 };
 constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)
 // A of `count` nodes of one depth, level_nodes[first ...]: their children's A must be complete
 hipError_t launch_grad_suffix(const GradArgs &a, int first, int count, hipStream_t st);
 hipError_t launch_grad_input(const GradArgs &a, hipStream_t st);
+// the same for the max semirings (`semiring`: kSemiArctic or kSemiBayesian of walk_types.h;
+// hipErrorInvalidValue for another): the SEGMENTED suffix sums between the heads of S_v, and the
+// gather without a shift.  Arctic: the exponent of a `fac` pair is the letter's coefficient.
+hipError_t launch_grad_max_suffix(const GradArgs &a, int semiring, int first, int count, hipStream_t st);
+hipError_t launch_grad_max_input(const GradArgs &a, int semiring, hipStream_t st);
 
 }  // namespace fr

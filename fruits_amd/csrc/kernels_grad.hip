@@ -18,6 +18,9 @@
 //
 // Plain loads and stores only; all offsets are 64-bit; every access is guarded by t < T.  The
 // tables are wave-uniform and read through the constant address space (scalar loads).
+//
+// Below them, the same pair for the max semirings Arctic and Bayesian (grad_max_suffix_kernel,
+// grad_max_input_kernel): the suffix sums become SEGMENTED sums between the heads of S_v.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -153,6 +156,202 @@ hipError_t launch_grad_input(const GradArgs &a, hipStream_t st) {
   const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
   if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
   hipLaunchKernelGGL(grad_input_kernel, dim3((unsigned)(a.N * a.D), (unsigned)tiles), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the max semirings
+// Arctic (max, +) and Bayesian (max, x), fruits/iss/semiring.py:282-309 and :461-493: per node
+//     z_v = m_v (x) S_p (no shift; m_v alone at depth 1),   S_v = running maximum of z_v
+// with m_v[t] = sum_d e_vd x_d[t] (Arctic) or prod_d x_d[t]^e_vd (Bayesian).  A HEAD of v is a
+// time s with s == 0 or S_v[s] > S_v[s-1] - strictly, the first of equal maxima wins - and opens
+// the segment [s, next head): S_v[t] = z_v[s] for every t of it.  The adjoint, leaves to root:
+//     B_v[t] = G_v[t] + sum over children c of w_c[t] A_c[t]      (w_c = 1 Arctic, m_c[t] Bayesian)
+//     A_v[s] = sum of B_v over the segment of s at a head s, 0.0 elsewhere
+//     Arctic: dX_d[s] = sum_v e_vd A_v[s];   Bayesian: dX_d[s] = sum_v A_v[s] S_p[s] dm_v/dx_d[s]
+//
+// grad_max_suffix_kernel has the launch shape, the chunks and the reversed lane-to-time map of
+// grad_suffix_kernel; its scan is SEGMENTED.  Walking time downwards, what crosses from t + 1 to
+// t is the open sum carry(t + 1) = head(t + 1) ? 0 : R[t + 1] with R[t] = B[t] + carry(t + 1),
+// and A[t] = head(t) ? R[t] : 0.  A run of time steps [lo, hi] acts on the carry that enters it
+// from the right as  c -> f ? o : o + c  with f = "a head in the run" and o = the sum of B from
+// lo up to the run's first head (the whole run without one); a run `a` to the right of a run `b`
+// compose as  (o_a, f_a) o (o_b, f_b) = (f_b ? o_b : o_a + o_b, f_a | f_b).  So a segment's sum is
+// only ever formed from that segment's B - never as a difference of two suffix sums - and every
+// partial sum joins disjoint runs of one segment.  The flags of the 64 lanes are one ballot: a
+// lane decides each step of the wave scan with a bit test, only the sums travel by DPP.  Across
+// waves and chunks the carry is the value c alone (a pair applied to it gives a value).
+
+// One step of the wave scan: the open sum of the lanes to the right (0.0 where the lane has no
+// source) joins unless the lanes this one covers so far hold a head.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double seg_step(double v, bool blocked) {
+  const double src = dpp_fetch<CTRL, ROW_MASK, 0>(v);
+  return blocked ? v : v + src;
+}
+
+// Inclusive segmented scan over the lanes, lane 0 first (the latest time steps): `o` the lane's
+// open sum, `heads` the ballot of the lanes that hold a head.  The steps are those of
+// wave_inclusive_scan; before each, a lane covers the lanes [lo, lane] named beside it.
+__device__ __forceinline__ double wave_segmented_scan(double o, unsigned long long heads, int lane) {
+  const unsigned long long le = heads & ((2ull << lane) - 1ull);   // heads of the lanes [0, lane]
+  const int row = lane & 48;
+  const auto from = [&](int back) { return lane - back > row ? lane - back : row; };
+  o = seg_step<0x111, 0xf>(o, (le >> lane) != 0);      // row_shr:1   [lane, lane]
+  o = seg_step<0x112, 0xf>(o, (le >> from(1)) != 0);   // row_shr:2   [lane - 1, lane] within the row
+  o = seg_step<0x114, 0xf>(o, (le >> from(3)) != 0);   // row_shr:4   [lane - 3, lane]
+  o = seg_step<0x118, 0xf>(o, (le >> from(7)) != 0);   // row_shr:8   [lane - 7, lane]
+  o = seg_step<0x142, 0xa>(o, (le >> row) != 0);       // row_bcast:15 -> rows 1,3   [row, lane]
+  o = seg_step<0x143, 0xc>(o, (le >> 32) != 0);        // row_bcast:31 -> rows 2,3   [32, lane]
+  return o;
+}
+
+template <int SEMI>
+__global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int first) {
+  __shared__ double wave_total[2][4];
+  __shared__ int wave_head[2][4];
+  const int64_t n = blockIdx.x;
+  const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
+  const int64_t N = a.N, T = a.T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double *__restrict__ xn = a.X + n * a.D * T;
+  const double *__restrict__ gn = a.G + n * a.g_n;
+  const double *__restrict__ sv = a.S + ((int64_t)as_const(a.self_srow)[v] * N + n) * T;
+  double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
+  const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
+  const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
+
+  double carry = 0.0;   // the open sum that enters the chunk from the right
+  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
+  for (int64_t c = chunks - 1; c >= 0; --c) {
+    const int64_t t0 = c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
+    // the heads, read off the recomputed S_v alone (steps past T hold none)
+    double s[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) s[j] = (t0 + j >= 1 && t0 + j - 1 < T) ? sv[t0 + j - 1] : 0.0;
+    bool h[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) h[j] = t0 + j < T && (t0 + j == 0 || s[j + 1] > s[j]);
+    double b[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int g = gb; g < ge; ++g) {
+      const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (t0 + j < T) b[j] += gk[(t0 + j) * a.g_t];
+    }
+    for (int ci = cb; ci < ce; ++ci) {
+      const int ch = as_const(a.child)[ci];
+      const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
+      if constexpr (SEMI == kSemiArctic) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (t0 + j < T) b[j] += ac[t0 + j];
+      } else {
+        const int fb = as_const(a.fac_begin)[ch], fe = as_const(a.fac_begin)[ch + 1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (t0 + j < T) b[j] += letter_value(a, xn, fb, fe, t0 + j, -1) * ac[t0 + j];
+      }
+    }
+    // the lane's own run, from its last step to its first
+    double o = 0.0;
+    bool f = false;
+#pragma unroll
+    for (int j = 3; j >= 0; --j) {
+      o = h[j] ? 0.0 : b[j] + o;
+      f = f || h[j];
+    }
+    const unsigned long long heads = __ballot(f);
+    const double incl = wave_segmented_scan(o, heads, lane);
+    const double excl = wave_shift_right1<0>(incl);
+    if (lane == 63) {
+      wave_total[c & 1][wave] = incl;
+      wave_head[c & 1][wave] = heads != 0;
+    }
+    // (two buffers, as in grad_suffix_kernel)
+    __syncthreads();
+    double run = carry, off = carry;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      if (w == wave) off = run;
+      run = wave_head[c & 1][w] ? wave_total[c & 1][w] : wave_total[c & 1][w] + run;
+    }
+    carry = run;
+    // what enters this lane from the right, then its four steps
+    double in = (heads & ((1ull << lane) - 1ull)) != 0 ? excl : excl + off;
+#pragma unroll
+    for (int j = 3; j >= 0; --j) {
+      const double r = b[j] + in;
+      if (t0 + j < T) av[t0 + j] = h[j] ? r : 0.0;
+      in = h[j] ? 0.0 : r;
+    }
+  }
+}
+
+hipError_t launch_grad_max_suffix(const GradArgs &a, int semiring, int first, int count, hipStream_t st) {
+  if (semiring != kSemiArctic && semiring != kSemiBayesian) return hipErrorInvalidValue;
+  if (a.N <= 0 || a.T <= 0 || count <= 0) return hipSuccess;
+  if (a.N > 0x7fffffffLL) return hipErrorInvalidValue;
+  for (int done = 0; done < count; done += 65535) {
+    const int part = count - done < 65535 ? count - done : 65535;
+    const dim3 grid((unsigned)a.N, (unsigned)part);
+    if (semiring == kSemiArctic)
+      hipLaunchKernelGGL(grad_max_suffix_kernel<kSemiArctic>, grid, dim3(256), 0, st, a, first + done);
+    else
+      hipLaunchKernelGGL(grad_max_suffix_kernel<kSemiBayesian>, grid, dim3(256), 0, st, a, first + done);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <int SEMI>
+__global__ __launch_bounds__(256) void grad_max_input_kernel(GradArgs a) {
+  const int64_t row = blockIdx.x;   // (series, dimension)
+  const int64_t N = a.N, D = a.D, T = a.T;
+  const int64_t n = row / D, d = row - n * D;
+  const double *__restrict__ xn = a.X + n * D * T;
+  const int ib = as_const(a.dim_begin)[d], ie = as_const(a.dim_begin)[d + 1];
+#pragma unroll
+  for (int e = 0; e < kGradTile / 256; ++e) {
+    const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
+    if (t >= T) continue;
+    double acc = 0.0;
+    if constexpr (SEMI == kSemiArctic) {
+      // the letter is linear: its coefficient times A_v
+      for (int i = ib; i < ie; ++i) {
+        const int v = as_const(a.dim_item)[2 * i];
+        const int f = as_const(a.dim_item)[2 * i + 1];
+        acc += (double)as_const(a.fac)[2 * f + 1] * a.A[((int64_t)v * N + n) * T + t];
+      }
+    } else {
+      const double x = xn[d * T + t];
+      for (int i = ib; i < ie; ++i) {
+        const int v = as_const(a.dim_item)[2 * i];
+        const int f = as_const(a.dim_item)[2 * i + 1];
+        const int ps = as_const(a.parent_srow)[v];
+        // dm_v = A_v * S_p at the SAME step (no shift between the letters of a max semiring)
+        double dm = a.A[((int64_t)v * N + n) * T + t];
+        if (ps >= 0) dm *= a.S[((int64_t)ps * N + n) * T + t];
+        const int ex = as_const(a.fac)[2 * f + 1];
+        const double dpow = ex > 0 ? (double)ex * ipow(x, ex - 1) : (double)ex * (1.0 / ipow(x, 1 - ex));
+        const double others = letter_value(a, xn, as_const(a.fac_begin)[v], as_const(a.fac_begin)[v + 1], t, f);
+        acc += dm * (dpow * others);
+      }
+    }
+    a.dX[row * T + t] = acc;
+  }
+}
+
+hipError_t launch_grad_max_input(const GradArgs &a, int semiring, hipStream_t st) {
+  if (semiring != kSemiArctic && semiring != kSemiBayesian) return hipErrorInvalidValue;
+  if (a.N <= 0 || a.D <= 0 || a.T <= 0) return hipSuccess;
+  const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
+  if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(a.N * a.D), (unsigned)tiles);
+  if (semiring == kSemiArctic)
+    hipLaunchKernelGGL(grad_max_input_kernel<kSemiArctic>, grid, dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(grad_max_input_kernel<kSemiBayesian>, grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

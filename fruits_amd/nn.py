@@ -7,6 +7,12 @@ itself - the same plan, the same launch - and returns its ``(K, N, T)`` buffer a
 ``(N, K, T)`` view.  Only ``X`` is kept for the backward pass, which recomputes the iterated
 sums of every prefix with one more walk and runs the adjoint recursion of DESIGN.md 4.14
 (``fr_iss_backward``, csrc/kernels_grad.hip).  Nothing goes through the host.
+
+``max_iss(X, words, mode, semiring=...)`` and ``MaxISSLayer(words, mode, semiring=...)`` are the
+same for the two max semirings, ``Arctic()`` (max, +) and ``Bayesian()`` (max, x), unweighted:
+the gradient flows through the arg-max of every running maximum, of equal maxima through the
+FIRST (the tie rule of ``Arctic(argmax=True)``), and is a segmented suffix sum between the
+positions where a running maximum rises (``fr_iss_backward_max``).
 """
 from __future__ import annotations
 
@@ -19,10 +25,10 @@ from torch.autograd.function import once_differentiable
 from . import _native as nat
 from .iss.cos import CosWISS
 from .iss.iss import ISS, ISSMode
-from .iss.semiring import Reals
+from .iss.semiring import Arctic, Bayesian, Reals
 from .iss.words.word import SimpleWord
 
-__all__ = ["iss", "ISSLayer", "backward_calls"]
+__all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "backward_calls"]
 
 _calls = {"backward": 0}
 _OPS: dict = {}      # the functional form's ISS objects by (word strings, mode, device), oldest first
@@ -30,7 +36,8 @@ _OPS_KEPT = 8
 
 
 def backward_calls() -> int:
-    """Backward passes launched by this process so far (one ``fr_iss_backward`` each)."""
+    """Backward passes launched by this process so far (one ``fr_iss_backward`` or
+    ``fr_iss_backward_max`` each)."""
     return _calls["backward"]
 
 
@@ -95,7 +102,8 @@ def _prefix_program(op: ISS):
                 tables.append(tab[:k + 1])
             if L - k <= depth:
                 row_prefix.append(index[ident])
-    plan = nat.Plan(tables, [1] * len(tables), None, nat.FR_W_NONE)
+    plan = nat.Plan(tables, [1] * len(tables), None, nat.FR_W_NONE,
+                    arctic=isinstance(op.semiring, Arctic), bayesian=isinstance(op.semiring, Bayesian))
     if plan.nodes != len(tables):
         raise NotImplementedError("the prefix trie of these words is too deep for the walk's "
                                   "register frames: no backward pass")
@@ -120,7 +128,9 @@ class _ISSFunction(torch.autograd.Function):
         with torch.cuda.device(Xc.device):
             S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
             _calls["backward"] += 1
-            return nat.iss_backward(plan, Xc, S, G, row_prefix), None
+            # (a max semiring: the rises of the recomputed running maxima are the segments' heads)
+            entry = nat.iss_backward if isinstance(ctx.op.semiring, Reals) else nat.iss_backward_max
+            return entry(plan, Xc, S, G, row_prefix), None
 
 
 def _apply(op: ISS, X):
@@ -179,3 +189,100 @@ class ISSLayer(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"{len(self.op.words)} words, {self.op.mode.name}"
+
+
+# ----------------------------------------------------------------------- the max semirings
+def _check_max_config(op: ISS) -> None:
+    """``_check_config`` for ``max_iss``: raised before any launch."""
+    if isinstance(op, CosWISS):
+        raise NotImplementedError("CosWISS has no backward pass: only the unweighted ISS has")
+    if isinstance(op.semiring, Reals):
+        raise NotImplementedError(
+            "max_iss differentiates the max semirings Arctic and Bayesian: the Reals iterated "
+            "sums are nn.iss / nn.ISSLayer")
+    if not isinstance(op.semiring, (Arctic, Bayesian)):
+        raise NotImplementedError(
+            f"the semiring {type(op.semiring).__name__} has no backward pass: only Reals, Arctic "
+            "and Bayesian have")
+    if op._argmax:
+        raise NotImplementedError(
+            "Arctic(argmax=True) has no backward pass: its position rows are piecewise constant "
+            "- differentiate Arctic() instead")
+    if op.weighting is not None:
+        raise NotImplementedError(
+            f"a weighting ({type(op.weighting).__name__}) has no backward pass yet: only the "
+            "unweighted ISS has")
+    op._check_supported()
+    if op._has_generic:
+        raise NotImplementedError(
+            "generic words have no backward pass: only words of SimpleWord letters have")
+
+
+def _max_op(words, mode, semiring) -> ISS:
+    if isinstance(words, ISS):
+        if semiring is not None and type(semiring) is not type(words.semiring):
+            raise TypeError(f"the ISS carries {type(words.semiring).__name__}, not "
+                            f"{type(semiring).__name__}")
+        return words
+    if semiring is None:
+        raise TypeError("max_iss needs semiring=Arctic() or semiring=Bayesian()")
+    return ISS(list(words), mode=mode, semiring=semiring)
+
+
+def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
+    """Arctic (max, +) or Bayesian (max, x) iterated sums ``(N, K, T)`` of the device tensor ``X``
+    ``(N, D, T)``, in the row order of ``ISS(words, mode, semiring=semiring).transform(X)`` and
+    with its bits; differentiable with respect to ``X``.  ``semiring``: an ``Arctic()`` or a
+    ``Bayesian()``; or ``words`` is an ``ISS`` that carries one.
+
+    Row ``w`` at time ``t`` is ``max over i_1 <= ... <= i_p <= t of m_1[i_1] (x) ... (x) m_p[i_p]``
+    with ``m_k`` the value of letter k; the gradient is that of the term at the maximiser.  Of
+    equal maxima the first wins at every letter - the maximiser whose reversed index tuple
+    ``(i_p, ..., i_1)`` is lexicographically smallest, the rule of ``Arctic(argmax=True)`` - which
+    is a valid subgradient at a tie.  For Bayesian this holds on positive inputs; where ``X`` has
+    negative values the reference's recursion (a running maximum per letter) is not the maximum
+    over index tuples, and the gradient is that of the recursion as the reference defines it."""
+    op = key = None
+    if not isinstance(words, ISS):
+        words = list(words)
+        # (kept between calls like nn.iss keeps its plain case; an argmax Arctic is refused below)
+        plain = type(semiring) is Bayesian or (type(semiring) is Arctic and not semiring._argmax)
+        if plain and all(isinstance(w, SimpleWord) for w in words):
+            key = ("max", type(semiring).__name__, tuple(str(w) for w in words), mode,
+                   str(getattr(X, "device", None)))
+            op = _OPS.get(key)
+    if op is None:
+        op = _max_op(words, mode, semiring)
+        if key is not None:
+            if len(_OPS) >= _OPS_KEPT:
+                _OPS.pop(next(iter(_OPS)))
+            _OPS[key] = op
+    _check_max_config(op)
+    return _apply(op, X)
+
+
+class MaxISSLayer(torch.nn.Module):
+    """``max_iss`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, semiring=None) -> None:
+        super().__init__()
+        self.op = _max_op(words, mode, semiring)
+        _check_max_config(self.op)
+
+    @property
+    def words(self):
+        return self.op.words
+
+    @property
+    def mode(self) -> ISSMode:
+        return self.op.mode
+
+    @property
+    def semiring(self):
+        return self.op.semiring
+
+    def forward(self, X):
+        return _apply(self.op, X)
+
+    def extra_repr(self) -> str:
+        return f"{len(self.op.words)} words, {self.op.mode.name}, {type(self.op.semiring).__name__}"

@@ -703,6 +703,36 @@ int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_
                     int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
                     double *d_A, double *d_dX, void *stream);
 
+/* The same for the two max semirings: the gradient of unweighted Arctic (max, +) or Bayesian
+ * (max, x) iterated sums with respect to their input - the adjoint of the recursions of
+ * fruits/iss/semiring.py:282-309 (Arctic: tmp = tmp + el * Z[d] per dimension, running maximum,
+ * NO shift between letters) and fruits/iss/semiring.py:461-493 (Bayesian: the letters of Reals,
+ * running maximum, no shift).  Not in the reference.
+ *
+ * The arguments are those of fr_iss_backward; `prefix_plan` is the plan of the distinct
+ * prefixes (depth 1 each) created with FR_PLAN_ARCTIC or FR_PLAN_BAYESIAN, unweighted, and d_S
+ * its output on d_X.  FR_E_ARG, on the host and before any launch, for a Reals plan, a
+ * weighted plan, an FR_PLAN_ARCTIC_LETTER_SUM plan, a CosWISS plan, a plan that is no prefix
+ * plan, a bad row map, a null pointer or d_dX == d_X.
+ *
+ * With z_v = m_v (x) S_parent(v) (m_v alone at depth 1) and S_v the running maximum of z_v, a
+ * HEAD of node v is a time s with s == 0 or S_v[s] > S_v[s-1] - strictly: of equal maxima the
+ * FIRST wins, the rule of Arctic(argmax=True), fruits/iss/semiring.py:239-284 - read off d_S
+ * alone; a head opens the segment [s, next head).  Deepest nodes first:
+ *   B_v[t] = G_v[t] + sum over children c of w_c[t] A_c[t]     (w = 1 Arctic, m_c[t] Bayesian)
+ *   A_v[s] = sum of B_v over the segment of s at a head s, 0.0 elsewhere
+ *   Arctic:   dX_d[s] = sum over nodes v of e_vd A_v[s]
+ *   Bayesian: dX_d[s] = sum over nodes v of A_v[s] S_parent(v)[s] d m_v / d x_d [s]
+ * A segment's sum is formed from that segment's B alone.  For Arctic this is a subgradient of
+ * max over i_1 <= ... <= i_p <= t of sum_k m_k[i_k] (at ties: the maximiser with the smallest
+ * reversed index tuple); for Bayesian the same on positive inputs, and the gradient of the
+ * reference's recursion as it stands elsewhere.  Bit-identical from run to run and whatever the
+ * batch split; the tables are kept with the plan as fr_iss_backward keeps them. */
+int fr_iss_backward_max(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                        const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
+                        int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
+                        double *d_A, double *d_dX, void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest

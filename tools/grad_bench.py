@@ -1,11 +1,12 @@
-"""`python tools/grad_bench.py [reps] [launches]` from the root of the tree: what the backward
-pass of the differentiable ISS costs (fruits_amd.nn).  `of_weight(2, 3)` EXTENDED on a
-standard normal (2048, 3, 1024) batch that lives on the device: the forward pass alone
-(`nn.iss` under `torch.no_grad()`) and forward plus backward (`nn.iss(X).backward(G)` with a
-dense upstream gradient), `launches` (default 10) calls back to back between one pair of HIP
-events so that the host side of a call hides behind the work in front of it, the two interleaved
-over `reps` rounds (default 15) after one warm-up round; the medians per call and their ratio
-as one JSON line."""
+"""`python tools/grad_bench.py [reps] [launches] [--semiring=reals|arctic|bayesian]` from the root
+of the tree: what the backward pass of the differentiable ISS costs (fruits_amd.nn, DESIGN.md
+4.14).  `of_weight(2, 3)` EXTENDED on a (2048, 3, 1024) batch that lives on the device - standard
+normal, uniform in [0.25, 1] for Bayesian -: the forward pass alone (under `torch.no_grad()`) and
+forward plus backward (`layer(X).backward(G)` with a dense upstream gradient), `launches`
+(default 10) calls back to back between one pair of HIP events so that the host side of a call
+hides behind the work in front of it, interleaved over `reps` rounds (default 15) after one
+warm-up round; the medians per call and their ratio as one JSON line.  With a max semiring the
+Reals pair (`nn.ISSLayer`) runs interleaved in the same rounds, for comparison."""
 import json
 import statistics
 import sys
@@ -14,26 +15,44 @@ import fruits_amd as fr
 from fruits_amd import _native as nat
 from fruits_amd import nn
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 15
-launches = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
+semiring = "reals"
+for a in sys.argv[1:]:
+    if a.startswith("--semiring="):
+        semiring = a.split("=", 1)[1].lower()
+if semiring not in ("reals", "arctic", "bayesian"):
+    sys.exit("--semiring: reals, arctic or bayesian")
+reps = int(args[0]) if len(args) > 0 else 15
+launches = int(args[1]) if len(args) > 1 else 10
 t = nat.torch()
 nat.require_device()
 N, D, T = 2048, 3, 1024
 words = fr.words.of_weight(2, dim=3)
-layer = nn.ISSLayer(words, fr.ISSMode.EXTENDED)
-X = t.randn((N, D, T), dtype=t.float64, device="cuda").requires_grad_(True)
 K = fr.ISS(words, mode=fr.ISSMode.EXTENDED).n_iterated_sums()
 G = t.randn((N, K, T), dtype=t.float64, device="cuda")
 
 
-def forward():
-    with t.no_grad():
-        layer(X)
+def pair(layer, X):
+    def forward():
+        with t.no_grad():
+            layer(X)
+
+    def both():
+        X.grad = None
+        layer(X).backward(G)
+
+    return forward, both
 
 
-def both():
-    X.grad = None
-    layer(X).backward(G)
+X = t.randn((N, D, T), dtype=t.float64, device="cuda").requires_grad_(True)
+fns = {"": pair(nn.ISSLayer(words, fr.ISSMode.EXTENDED), X)}
+if semiring != "reals":
+    sr = fr.semiring.Arctic() if semiring == "arctic" else fr.semiring.Bayesian()
+    Xm = X.detach().clone()
+    if semiring == "bayesian":
+        Xm = 0.25 + 0.75 * t.rand((N, D, T), dtype=t.float64, device="cuda")
+    fns = {"": pair(nn.MaxISSLayer(words, fr.ISSMode.EXTENDED, semiring=sr), Xm.requires_grad_(True)),
+           "reals_": fns[""]}
 
 
 def timed(fn):
@@ -46,14 +65,17 @@ def timed(fn):
     return a.elapsed_time(b) / launches
 
 
-tf, tb = [], []
+times = {(k, i): [] for k in fns for i in (0, 1)}
 for r in range(reps + 1):
-    f, b = timed(forward), timed(both)
-    if r:                      # (round 0 uploads the tables and warms both up)
-        tf.append(f)
-        tb.append(b)
-f, b = statistics.median(tf), statistics.median(tb)
-print(json.dumps({"shape": [N, D, T], "words": "of_weight(2, 3) EXTENDED", "rows": K, "reps": reps,
-                  "launches": launches,
-                  "forward_ms": round(f, 4), "forward_backward_ms": round(b, 4),
-                  "ratio": round(b / f, 3)}))
+    for k, fs in fns.items():
+        for i in (0, 1):
+            ms = timed(fs[i])
+            if r:                      # (round 0 uploads the tables and warms everything up)
+                times[k, i].append(ms)
+out = {"shape": [N, D, T], "words": "of_weight(2, 3) EXTENDED", "rows": K, "reps": reps,
+       "launches": launches, "semiring": semiring}
+for k in fns:
+    f, b = statistics.median(times[k, 0]), statistics.median(times[k, 1])
+    out.update({k + "forward_ms": round(f, 4), k + "forward_backward_ms": round(b, 4),
+                k + "ratio": round(b / f, 3)})
+print(json.dumps(out))
