@@ -48,7 +48,7 @@ EXPORTS = [
     "fr_prep_mask", "fr_prep_pointwise",
     "fr_letter_rows", "fr_rows_unshift",
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
-    "fr_iss_backward", "fr_iss_backward_max",
+    "fr_iss_backward", "fr_iss_backward_max", "fr_iss_backward_weighted",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -1207,3 +1207,40 @@ def iss_backward_max(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None):
     sums with respect to ``Xd``; the arguments of ``iss_backward``, ``prefix_plan`` created with
     ``arctic=True`` or ``bayesian=True``."""
     return iss_backward(prefix_plan, Xd, Sd, G, row_prefix, work, entry="fr_iss_backward_max")
+
+
+def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=None):
+    """fr_iss_backward_weighted: the gradient ``(N, D, T)`` of weighted Reals iterated sums with
+    respect to ``Xd``, the lookup being a constant.  ``prefix_plan``: the weighted plan of the
+    distinct (letters, alphas) prefixes, each with depth 1; ``lookup_d`` ``(1 | N, T)`` the
+    weighting's device lookup; ``G`` and ``row_prefix`` as in ``iss_backward``.  The entry forms
+    the carried sums itself: it takes no output of the plan.  ``work``: a scratch of
+    ``2 V N T + 2 alphas rows T`` doubles if the caller keeps one."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
+    K = int(rp.shape[0])
+    V = prefix_plan.rows
+    if G.dtype != t.float64 or tuple(G.shape) != (N, K, T) or G.device != Xd.device:
+        raise TypeError("the upstream gradient must be a float64 (N, K, T) tensor on the input's device")
+    if (lookup_d is None or lookup_d.dtype != t.float64 or lookup_d.dim() != 2
+            or int(lookup_d.shape[1]) != T or int(lookup_d.shape[0]) not in (1, N)
+            or not lookup_d.is_contiguous() or lookup_d.device != Xd.device):
+        raise TypeError("the lookup must be a contiguous float64 (1 | N, T) tensor on the input's device")
+    rows = int(lookup_d.shape[0])
+    cells, aux = V * N * T, 2 * prefix_plan.info(FR_INFO_ALPHAS) * rows * T
+    if work is None:
+        work = t.empty((2 * cells + aux,), dtype=t.float64, device=Xd.device)
+    elif work.dtype != t.float64 or work.numel() < 2 * cells + aux or not work.is_contiguous():
+        raise TypeError("the scratch must be a contiguous float64 device tensor of "
+                        "2 V N T + 2 alphas rows T elements")
+    work = work.view(-1)
+    dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
+    sn, sk, st = (int(s) for s in G.stride())
+    # (the scratch in three parts; an empty part still gets a distinct address)
+    parts = [C.c_void_p(work.data_ptr() + 8 * o) for o in (0, cells, 2 * cells)]
+    check(lib().fr_iss_backward_weighted(
+        prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
+        C.c_int64(rows), dptr(G), C.c_int64(K), C.c_int64(sn), C.c_int64(sk), C.c_int64(st),
+        _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
+    return dX

@@ -1,7 +1,8 @@
 // fr_iss_backward: the gradient of unweighted Reals iterated sums with respect to their input;
-// fr_iss_backward_max: the same for the max semirings Arctic and Bayesian.  The trie - parents,
-// children, letters - is read off the plan the plan compiler built (plan.cpp); the kernels are
-// those of kernels_grad.hip.
+// fr_iss_backward_max: the same for the max semirings Arctic and Bayesian;
+// fr_iss_backward_weighted: the same for weighted Reals plans, total or not.  The trie - parents,
+// children, letters, exp tables - is read off the plan the plan compiler built (plan.cpp); the
+// kernels are those of kernels_grad.hip.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -21,16 +22,20 @@ struct GradTables {
   std::vector<int32_t> row_prefix;
   std::vector<int32_t> parent_srow, child_begin, child, fac_begin, fac, g_begin, g_row,
       level_nodes, level_begin, dim_begin, dim_item, self_srow;
+  // a weighted plan's: per node the exp tables {own E+, own E-, parent's E-} (-1: unused), the
+  // nodes that have children by rising depth, and the bits of the plan's distinct alphas
+  std::vector<int32_t> tab, inner_nodes, inner_begin, alpha_bits;
   int64_t dims = 0;        // dimensions dim_begin covers (the D of the call it was built for)
   void *d_blob = nullptr;
   const int32_t *d_parent_srow = nullptr, *d_child_begin = nullptr, *d_child = nullptr,
                 *d_fac_begin = nullptr, *d_fac = nullptr, *d_g_begin = nullptr, *d_g_row = nullptr,
                 *d_level_nodes = nullptr, *d_dim_begin = nullptr, *d_dim_item = nullptr,
-                *d_self_srow = nullptr;
+                *d_self_srow = nullptr, *d_tab = nullptr, *d_inner_nodes = nullptr,
+                *d_alpha_bits = nullptr;
 };
 
-// Builds the host tables of an unweighted trie plan of any semiring (the caller has checked
-// which); "" or what is wrong with the plan / the row map.
+// Builds the host tables of a trie plan of any semiring, unweighted or - Reals - weighted (the
+// caller has checked which); "" or what is wrong with the plan / the row map.
 std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K, int64_t D,
                          GradTables &g) {
   const int V = (int)p.nodes.size();
@@ -79,6 +84,9 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
   g.g_row.clear();
   g.fac.clear();
   std::vector<std::vector<int32_t>> items((size_t)D);
+  const bool weighted = p.weighting != 0;
+  g.tab.assign(weighted ? (size_t)3 * V : 0, -1);
+  const std::string not_weighted = "the exp factors of a node are not those of a weighted prefix plan";
   for (int i = 0; i < V; ++i) {
     g.child.insert(g.child.end(), kids[i].begin(), kids[i].end());
     g.child_begin.push_back((int32_t)g.child.size());
@@ -91,6 +99,14 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
     for (int j = 0; j < nd.fac_count; ++j) {
       const int32_t code = p.factors[nd.fac_begin + j];
       const int row = code & fr::FAC_ROW_MASK;
+      if (weighted && p.multiplicative() && row >= p.dims_used && row < (int)p.row_src.size()) {
+        // an exp table, not an input dimension (plan.cpp, emit_node): an even table is the
+        // node's own exp(+g alpha), an odd one its parent's exp(-g alpha)
+        const int table = row - p.dims_used;
+        if ((code & fr::FAC_DIV) || g.tab[3 * i + ((table & 1) ? 2 : 0)] >= 0) return not_weighted;
+        g.tab[3 * i + ((table & 1) ? 2 : 0)] = table;
+        continue;
+      }
       if (row >= (int)p.row_src.size() || p.row_src[row] < 0) return "a factor that is no input dimension";
       const int32_t dim = p.row_src[row];
       if (dim >= D) return "a factor beyond the input's dimensions";
@@ -114,6 +130,28 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
       items[(size_t)g.fac[2 * f]].push_back((int32_t)f);
     }
     g.fac_begin.push_back((int32_t)(g.fac.size() / 2));
+    if (weighted) {
+      // the node's own tables: non-total - the weight of the child scan (inner nodes only, a
+      // leaf needs none); total - the factor above and the weight of the emitted row
+      int32_t *tb = &g.tab[3 * (size_t)i];
+      if (p.weighting == 1 && nd.z_mul >= 0) {
+        tb[0] = nd.z_mul - p.dims_used;
+        tb[1] = tb[0] + 1;
+      } else if (p.weighting == 2) {
+        tb[1] = nd.emit_mul - p.dims_used;
+      }
+      const int tables = p.aux_tables();
+      const bool inner = !kids[i].empty();
+      if (p.weighting == 2 || inner)
+        if (tb[0] < 0 || tb[0] + 1 >= tables || (tb[0] & 1) || tb[1] != tb[0] + 1) return not_weighted;
+      // (a parent comes before its children: its tables are checked by now)
+      if ((parent[i] >= 0) != (tb[2] >= 0) || (parent[i] >= 0 && tb[2] != g.tab[3 * (size_t)parent[i] + 1]))
+        return not_weighted;
+    }
+  }
+  if (weighted) {
+    g.alpha_bits.resize(p.alphas.size());
+    if (!p.alphas.empty()) std::memcpy(g.alpha_bits.data(), p.alphas.data(), p.alphas.size() * 4);
   }
   g.dim_begin.assign(1, 0);
   g.dim_item.clear();
@@ -132,17 +170,26 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
       if (depth[i] == dep) g.level_nodes.push_back(i);
     g.level_begin.push_back((int32_t)g.level_nodes.size());
   }
+  // a weighted plan's carried sums are formed root first: the nodes that have children, by
+  // rising depth (the others' are never read)
+  g.inner_nodes.clear();
+  g.inner_begin.assign(1, 0);
+  for (int dep = 1; weighted && dep <= deepest; ++dep) {
+    for (int i = 0; i < V; ++i)
+      if (depth[i] == dep && !kids[i].empty()) g.inner_nodes.push_back(i);
+    g.inner_begin.push_back((int32_t)g.inner_nodes.size());
+  }
   return "";
 }
 
 int upload_tables(GradTables &g) {
   const std::vector<int32_t> *parts[] = {&g.parent_srow, &g.child_begin, &g.child, &g.fac_begin, &g.fac,
                                          &g.g_begin, &g.g_row, &g.level_nodes, &g.dim_begin, &g.dim_item,
-                                         &g.self_srow};
+                                         &g.self_srow, &g.tab, &g.inner_nodes, &g.alpha_bits};
   const int32_t **dst[] = {&g.d_parent_srow, &g.d_child_begin, &g.d_child, &g.d_fac_begin, &g.d_fac,
                            &g.d_g_begin, &g.d_g_row, &g.d_level_nodes, &g.d_dim_begin, &g.d_dim_item,
-                           &g.d_self_srow};
-  constexpr int kParts = 11;
+                           &g.d_self_srow, &g.d_tab, &g.d_inner_nodes, &g.d_alpha_bits};
+  constexpr int kParts = 14;
   size_t off = 0, at[kParts];
   for (int i = 0; i < kParts; ++i) {
     at[i] = off;
@@ -176,6 +223,60 @@ void release_grad_tables(fr::Plan &p) {
 }  // namespace fr::capi
 
 namespace {
+
+// The plan's backward tables for this row map and D, on the device: those it holds, or fresh
+// ones - checked on the host before anything is uploaded or launched.  Caller holds p.mu.  With
+// nothing to launch (N == 0 or T == 0) the tables are only checked.
+int ensure_tables(fr::Plan &p, const std::string &who, const int32_t *h_row_prefix, int64_t K,
+                  int64_t D, bool nothing_to_do, hipStream_t st, GradTables *&g) {
+  g = static_cast<GradTables *>(p.grad);
+  const bool same = g && g->dims == D && (int64_t)g->row_prefix.size() == K &&
+                    (K == 0 || std::memcmp(g->row_prefix.data(), h_row_prefix, (size_t)K * 4) == 0);
+  if (same) return FR_OK;
+  GradTables fresh;
+  const std::string why = build_tables(p, h_row_prefix, K, D, fresh);
+  if (!why.empty()) return fail(FR_E_ARG, who + ": " + why);
+  if (nothing_to_do) return FR_OK;
+  if (stream_is_capturing(st))
+    return fail(FR_E_ARG, who + ": the stream is being captured and the backward tables "
+                          "are not on the device yet - run one backward pass before the capture");
+  int rc = claim_device(p, who.c_str());
+  if (rc != FR_OK) return rc;
+  if (g) {
+    // (kernels of an earlier call may still read the old tables)
+    HIP_TRY(hipDeviceSynchronize());
+    release_grad_tables(p);
+  }
+  g = new GradTables(std::move(fresh));
+  rc = upload_tables(*g);
+  if (rc != FR_OK) {
+    delete g;
+    g = nullptr;
+    return rc;
+  }
+  p.grad = g;
+  return FR_OK;
+}
+
+// The kernel arguments that are the tables' and the shape's.
+fr::GradArgs table_args(const GradTables &g, int64_t N, int64_t D, int64_t T) {
+  fr::GradArgs a{};
+  a.N = N;
+  a.D = D;
+  a.T = T;
+  a.parent_srow = g.d_parent_srow;
+  a.child_begin = g.d_child_begin;
+  a.child = g.d_child;
+  a.fac_begin = g.d_fac_begin;
+  a.fac = g.d_fac;
+  a.g_begin = g.d_g_begin;
+  a.g_row = g.d_g_row;
+  a.level_nodes = g.d_level_nodes;
+  a.dim_begin = g.d_dim_begin;
+  a.dim_item = g.d_dim_item;
+  a.self_srow = g.d_self_srow;
+  return a;
+}
 
 // The body of both entries.  `max_plus`: fr_iss_backward_max - the plan has to be an Arctic or
 // a Bayesian one, and the kernels are the segmented ones.
@@ -214,59 +315,20 @@ int run_backward(const std::string &who, bool max_plus, fr_plan_t *prefix_plan, 
   if (kind) return fail(FR_E_ARG, who + ": " + kind);
   hipStream_t st = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(p.mu);
-  GradTables *g = static_cast<GradTables *>(p.grad);
-  const bool same = g && g->dims == D && (int64_t)g->row_prefix.size() == K &&
-                    (K == 0 || std::memcmp(g->row_prefix.data(), h_row_prefix, (size_t)K * 4) == 0);
-  if (!same) {
-    // (the tables are checked on the host before anything is uploaded or launched)
-    GradTables fresh;
-    const std::string why = build_tables(p, h_row_prefix, K, D, fresh);
-    if (!why.empty()) return fail(FR_E_ARG, who + ": " + why);
-    if (N == 0 || T == 0) return FR_OK;
-    if (stream_is_capturing(st))
-      return fail(FR_E_ARG, who + ": the stream is being captured and the backward tables "
-                            "are not on the device yet - run one backward pass before the capture");
-    int rc = claim_device(p, who.c_str());
-    if (rc != FR_OK) return rc;
-    if (g) {
-      // (kernels of an earlier call may still read the old tables)
-      HIP_TRY(hipDeviceSynchronize());
-      release_grad_tables(p);
-    }
-    g = new GradTables(std::move(fresh));
-    rc = upload_tables(*g);
-    if (rc != FR_OK) {
-      delete g;
-      return rc;
-    }
-    p.grad = g;
-  }
-  if (N == 0 || T == 0) return FR_OK;
-  int rc = claim_device(p, who.c_str());
+  GradTables *g = nullptr;
+  int rc = ensure_tables(p, who, h_row_prefix, K, D, N == 0 || T == 0, st, g);
+  if (rc != FR_OK || N == 0 || T == 0) return rc;
+  rc = claim_device(p, who.c_str());
   if (rc != FR_OK) return rc;
-  fr::GradArgs a{};
+  fr::GradArgs a = table_args(*g, N, D, T);
   a.X = d_X;
   a.S = d_S;
   a.G = d_G;
   a.A = d_A;
   a.dX = d_dX;
-  a.N = N;
-  a.D = D;
-  a.T = T;
   a.g_n = g_n_stride;
   a.g_k = g_k_stride;
   a.g_t = g_t_stride;
-  a.parent_srow = g->d_parent_srow;
-  a.child_begin = g->d_child_begin;
-  a.child = g->d_child;
-  a.fac_begin = g->d_fac_begin;
-  a.fac = g->d_fac;
-  a.g_begin = g->d_g_begin;
-  a.g_row = g->d_g_row;
-  a.level_nodes = g->d_level_nodes;
-  a.dim_begin = g->d_dim_begin;
-  a.dim_item = g->d_dim_item;
-  a.self_srow = g->d_self_srow;
   const std::string limit_text = who + ": grid too large (N, N * D or T)";
   const char *limit = limit_text.c_str();
   for (size_t l = 0; l + 1 < g->level_begin.size(); ++l) {
@@ -280,9 +342,96 @@ int run_backward(const std::string &who, bool max_plus, fr_plan_t *prefix_plan, 
                   "backward input launch", limit);
 }
 
+// fr_iss_backward_weighted: the exp tables, the carried sums root first, the adjoint leaves first.
+int run_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                          const double *d_lookup, int64_t lookup_rows, const double *d_G, int64_t K,
+                          int64_t g_n_stride, int64_t g_k_stride, int64_t g_t_stride,
+                          const int32_t *h_row_prefix, double *d_C, double *d_A, double *d_aux,
+                          double *d_dX, void *stream) {
+  const std::string who = "fr_iss_backward_weighted";
+  if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, who + ": null plan");
+  if (N < 0 || D < 1 || T < 0 || K < 0 || g_n_stride < 0 || g_k_stride < 0 || g_t_stride < 0)
+    return fail(FR_E_ARG, who + ": bad shape");
+  if (lookup_rows != 1 && lookup_rows != N)
+    return fail(FR_E_ARG, who + ": the lookup has to have 1 or N rows, not " + std::to_string(lookup_rows));
+  if (K > 0 && !h_row_prefix) return fail(FR_E_ARG, who + ": null host table");
+  fr::Plan &p = *prefix_plan->p;
+  // which plans the entry takes (what a plan is never changes after its creation)
+  const char *kind = nullptr;
+  if (p.cos)
+    kind = "a CosWISS plan has no backward pass";
+  else if (p.semiring != fr::kSemiReals)
+    kind = "the plan is an Arctic or a Bayesian plan - fr_iss_backward_max differentiates the "
+           "unweighted ones, a weighted one has no backward pass";
+  else if (p.weighting == 0)
+    kind = "the plan is an unweighted Reals plan - its backward pass is fr_iss_backward";
+  if (kind) return fail(FR_E_ARG, who + ": " + kind);
+  if (p.max_dim > D)
+    return fail(FR_E_DIM, who + ": a word references dimension " + std::to_string(p.max_dim) +
+                              " but the input has only " + std::to_string(D));
+  const int64_t V = (int64_t)p.nodes.size();
+  if (N > 0 && T > 0) {
+    if (!d_X || !d_dX || !d_lookup || (K > 0 && !d_G) || (V > 0 && (!d_C || !d_A || !d_aux)))
+      return fail(FR_E_ARG, who + ": null device pointer");
+    if (d_X == d_dX) return fail(FR_E_ARG, who + ": the gradient must not alias the input");
+    if (V > 0 && (d_C == d_A || d_aux == d_A || d_aux == d_C))
+      return fail(FR_E_ARG, who + ": the scratches must be distinct buffers");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(p.mu);
+  GradTables *g = nullptr;
+  int rc = ensure_tables(p, who, h_row_prefix, K, D, N == 0 || T == 0, st, g);
+  if (rc != FR_OK || N == 0 || T == 0) return rc;
+  rc = claim_device(p, who.c_str());
+  if (rc != FR_OK) return rc;
+  const int64_t count = lookup_rows * T;
+  rc = launched(fr::launch_exp_tables(d_lookup, count, reinterpret_cast<const float *>(g->d_alpha_bits),
+                                      (int)p.alphas.size(), d_aux, false, st),
+                "exp_tables launch");
+  if (rc != FR_OK) return rc;
+  fr::GradWArgs w{};
+  w.g = table_args(*g, N, D, T);
+  w.g.X = d_X;
+  w.g.G = d_G;
+  w.g.A = d_A;
+  w.g.dX = d_dX;
+  w.g.g_n = g_n_stride;
+  w.g.g_k = g_k_stride;
+  w.g.g_t = g_t_stride;
+  w.C = d_C;
+  w.aux = d_aux;
+  w.aux_tab = count;
+  w.aux_n = lookup_rows == 1 ? 0 : T;
+  w.tab = g->d_tab;
+  w.inner_nodes = g->d_inner_nodes;
+  const bool total = p.weighting == FR_W_TOTAL;
+  const std::string limit_text = who + ": grid too large (N, N * D or T)";
+  const char *limit = limit_text.c_str();
+  for (size_t l = 0; l + 1 < g->inner_begin.size(); ++l) {
+    const int first = g->inner_begin[l], n_nodes = g->inner_begin[l + 1] - first;
+    rc = launched(fr::launch_grad_w_prefix(w, first, n_nodes, st), "backward prefix launch", limit);
+    if (rc != FR_OK) return rc;
+  }
+  for (size_t l = 0; l + 1 < g->level_begin.size(); ++l) {
+    const int first = g->level_begin[l], n_nodes = g->level_begin[l + 1] - first;
+    rc = launched(fr::launch_grad_w_suffix(w, total, first, n_nodes, st), "backward suffix launch", limit);
+    if (rc != FR_OK) return rc;
+  }
+  return launched(fr::launch_grad_w_input(w, total, st), "backward input launch", limit);
+}
+
 }  // namespace
 
 extern "C" {
+
+int fr_iss_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D,
+                             int64_t T, const double *d_lookup, int64_t lookup_rows,
+                             const double *d_G, int64_t K, int64_t g_n_stride, int64_t g_k_stride,
+                             int64_t g_t_stride, const int32_t *h_row_prefix, double *d_C,
+                             double *d_A, double *d_aux, double *d_dX, void *stream) {
+  return run_backward_weighted(prefix_plan, d_X, N, D, T, d_lookup, lookup_rows, d_G, K, g_n_stride,
+                               g_k_stride, g_t_stride, h_row_prefix, d_C, d_A, d_aux, d_dX, stream);
+}
 
 int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
                     const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,

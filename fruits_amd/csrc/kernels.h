@@ -159,5 +159,22 @@ hipError_t launch_grad_input(const GradArgs &a, hipStream_t st);
 // gather without a shift.  Arctic: the exponent of a `fac` pair is the letter's coefficient.
 hipError_t launch_grad_max_suffix(const GradArgs &a, int semiring, int first, int count, hipStream_t st);
 hipError_t launch_grad_max_input(const GradArgs &a, int semiring, hipStream_t st);
+// the backward pass of a WEIGHTED Reals plan: the tables of GradArgs - `g.S` is
+// unused - and what the exp weights add.  C holds the CARRIED sums C_v = cumsum(y_v), which the
+// kernels form themselves; rows of C are numbered like the rows of S (self_srow, parent_srow).
+struct GradWArgs {
+  GradArgs g;
+  double *C;            // (V, N, T) scratch: the carried sums of the nodes that have children
+  const double *aux;    // (2 n_alpha, rows, T): table 2a = exp(+g alpha_a), 2a + 1 = exp(-g alpha_a)
+  int64_t aux_tab;      // doubles from one table to the next (rows * T)
+  int64_t aux_n;        // doubles from one series' row to the next (T; 0: one row for all)
+  const int32_t *tab;   // three tables per node: its own E+, its own E-, its parent's E- (-1: unused)
+  const int32_t *inner_nodes;   // the nodes that have children, by rising depth
+};
+// C of `count` nodes of one depth, inner_nodes[first ...]: their parents' C must be complete
+hipError_t launch_grad_w_prefix(const GradWArgs &a, int first, int count, hipStream_t st);
+// A of `count` nodes of one depth, g.level_nodes[first ...], as launch_grad_suffix
+hipError_t launch_grad_w_suffix(const GradWArgs &a, bool total, int first, int count, hipStream_t st);
+hipError_t launch_grad_w_input(const GradWArgs &a, bool total, hipStream_t st);
 
 }  // namespace fr

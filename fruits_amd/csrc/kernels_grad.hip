@@ -20,7 +20,10 @@
 // tables are wave-uniform and read through the constant address space (scalar loads).
 //
 // Below them, the same pair for the max semirings Arctic and Bayesian (grad_max_suffix_kernel,
-// grad_max_input_kernel): the suffix sums become SEGMENTED sums between the heads of S_v.
+// grad_max_input_kernel): the suffix sums become SEGMENTED sums between the heads of S_v.  And at
+// the end the kernels of weighted Reals plans (grad_w_prefix_kernel, grad_w_suffix_kernel,
+// grad_w_input_kernel): the exp factors join the products, and a prefix scan forms the sums the
+// forward pass carries from letter to letter.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -352,6 +355,270 @@ hipError_t launch_grad_max_input(const GradArgs &a, int semiring, hipStream_t st
     hipLaunchKernelGGL(grad_max_input_kernel<kSemiArctic>, grid, dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL(grad_max_input_kernel<kSemiBayesian>, grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ weighted Reals plans
+// Both weighted bodies of fruits/iss/semiring.py:98-158 carry the same sums from letter to letter
+// (E+_v = exp(g alpha_v), E-_v = exp(-g alpha_v) of the node's last letter):
+//     y_v[t] = m_v[t] E-_p[t] E+_v[t] C_p[t-1]   (depth 1: m_v[t] E+_v[t]),   C_v = cumsum(y_v)
+// and differ in what a node emits: S_v = C_v E-_v (total) or S_v = cumsum(z_v), y_v = z_v E+_v
+// (non-total).  The adjoint, leaves to root, children c reading C_v[s] at time s + 1:
+//     total:      B_v[s] = G_v[s] E-_v[s] + sum_c m_c[s+1] E-_v[s+1] E+_c[s+1] A_c[s+1]
+//                 A_v = suffix(B_v);                          dm_v = A_v E-_p E+_v shift(C_p)
+//     non-total:  Q_v[s] = sum_c m_c[s+1] E-_v[s+1] A_c[s+1]
+//                 A_v = suffix(G_v) + E+_v suffix(Q_v);       dm_v = A_v E-_p shift(C_p)
+// Nothing is divided by an exp factor.  The forward walk of a non-total plan emits S, not C, so
+// grad_w_prefix_kernel forms C of the nodes that have children; the exp tables are read from
+// global memory (launch_exp_tables filled them on the same stream).
+
+// Table `tb` (-1: none, the factor 1.0) of the series whose tables start at `aux_n` at time t.
+__device__ __forceinline__ double exp_factor(const double *__restrict__ aux_n, int64_t aux_tab, int tb,
+                                             int64_t t) {
+  return tb < 0 ? 1.0 : aux_n[(int64_t)tb * aux_tab + t];
+}
+
+// (one kernel for both bodies: they carry the same sums)
+__global__ __launch_bounds__(256) void grad_w_prefix_kernel(GradWArgs w, int first) {
+  __shared__ double wave_total[2][4];
+  const GradArgs &a = w.g;
+  const int64_t n = blockIdx.x;
+  const int v = as_const(w.inner_nodes)[first + (int)blockIdx.y];
+  const int64_t N = a.N, T = a.T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double *__restrict__ xn = a.X + n * a.D * T;
+  const double *__restrict__ en = w.aux + n * w.aux_n;
+  const int fb = as_const(a.fac_begin)[v], fe = as_const(a.fac_begin)[v + 1];
+  const int ps = as_const(a.parent_srow)[v];
+  const int t_plus = as_const(w.tab)[3 * v], t_pminus = as_const(w.tab)[3 * v + 2];
+  const double *__restrict__ cp = ps >= 0 ? w.C + ((int64_t)ps * N + n) * T : nullptr;
+  double *__restrict__ cv = w.C + ((int64_t)as_const(a.self_srow)[v] * N + n) * T;
+
+  double carry = 0.0;   // sum of y_v over the chunks to the left
+  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
+  for (int64_t c = 0; c < chunks; ++c) {
+    const int64_t t0 = c * kGradChunk + 4 * (int64_t)threadIdx.x;
+    double y[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t t = t0 + j;
+      if (t >= T) continue;
+      double val = letter_value(a, xn, fb, fe, t, -1);
+      if (ps >= 0) val = t > 0 ? val * cp[t - 1] * exp_factor(en, w.aux_tab, t_pminus, t) : 0.0;
+      y[j] = val * exp_factor(en, w.aux_tab, t_plus, t);
+    }
+    // the lane's own prefix sums (steps past T hold exact zeros), then the lanes from the left
+    y[1] += y[0];
+    y[2] += y[1];
+    y[3] += y[2];
+    const double incl = wave_inclusive_scan<0>(y[3]);
+    const double excl = wave_shift_right1<0>(incl);
+    if (lane == 63) wave_total[c & 1][wave] = incl;
+    // (two buffers, as in grad_suffix_kernel)
+    __syncthreads();
+    double run = carry, off = carry;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k == wave) off = run;
+      run += wave_total[c & 1][k];
+    }
+    carry = run;
+    off += excl;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (t0 + j < T) cv[t0 + j] = off + y[j];
+  }
+}
+
+hipError_t launch_grad_w_prefix(const GradWArgs &w, int first, int count, hipStream_t st) {
+  if (w.g.N <= 0 || w.g.T <= 0 || count <= 0) return hipSuccess;
+  if (w.g.N > 0x7fffffffLL) return hipErrorInvalidValue;
+  for (int done = 0; done < count; done += 65535) {
+    const int part = count - done < 65535 ? count - done : 65535;
+    hipLaunchKernelGGL(grad_w_prefix_kernel, dim3((unsigned)w.g.N, (unsigned)part), dim3(256), 0, st, w,
+                       first + done);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The launch shape, the chunks and the reversed lane-to-time map of grad_suffix_kernel.  Total: one
+// scan over B_v.  Non-total: the suffix sums of G_v and of Q_v are two scans with two carries,
+// joined as suffix(G) + E+ suffix(Q); a scan whose operand is empty - a node that is no output
+// row, a node without children - is skipped (block-uniform branches).
+template <bool TOTAL>
+__global__ __launch_bounds__(256) void grad_w_suffix_kernel(GradWArgs w, int first) {
+  __shared__ double wave_total[2][2][4];
+  const GradArgs &a = w.g;
+  const int64_t n = blockIdx.x;
+  const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
+  const int64_t N = a.N, T = a.T;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double *__restrict__ xn = a.X + n * a.D * T;
+  const double *__restrict__ gn = a.G + n * a.g_n;
+  const double *__restrict__ en = w.aux + n * w.aux_n;
+  double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
+  const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
+  const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
+  const int t_plus = as_const(w.tab)[3 * v], t_minus = as_const(w.tab)[3 * v + 1];
+  const bool has_g = ge > gb, has_c = ce > cb;
+  // which sums are scanned: total - B alone (slot 0); non-total - G (slot 0) and Q (slot 1)
+  const bool scan0 = TOTAL ? (has_g || has_c) : has_g;
+  const bool scan1 = !TOTAL && has_c;
+
+  double carry0 = 0.0, carry1 = 0.0;   // the sums over the chunks to the right
+  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
+  for (int64_t c = chunks - 1; c >= 0; --c) {
+    const int64_t t0 = c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
+    double b[4] = {0.0, 0.0, 0.0, 0.0};   // total: B_v; non-total: G_v
+    double q[4] = {0.0, 0.0, 0.0, 0.0};   // non-total: Q_v
+    for (int g = gb; g < ge; ++g) {
+      const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (t0 + j < T) b[j] += gk[(t0 + j) * a.g_t];
+    }
+    if (TOTAL && has_g) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (t0 + j < T) b[j] *= exp_factor(en, w.aux_tab, t_minus, t0 + j);
+    }
+    for (int ci = cb; ci < ce; ++ci) {
+      const int ch = as_const(a.child)[ci];
+      const int fb = as_const(a.fac_begin)[ch], fe = as_const(a.fac_begin)[ch + 1];
+      const int c_plus = as_const(w.tab)[3 * ch];
+      const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t s = t0 + j + 1;
+        if (s >= T) continue;
+        double term = letter_value(a, xn, fb, fe, s, -1) * exp_factor(en, w.aux_tab, t_minus, s);
+        if constexpr (TOTAL) {
+          term *= exp_factor(en, w.aux_tab, c_plus, s);
+          b[j] += term * ac[s];
+        } else {
+          q[j] += term * ac[s];
+        }
+      }
+    }
+    // the lane's own suffix sums (steps past T hold exact zeros), then the lanes from the right
+    double excl0 = 0.0, excl1 = 0.0;
+    if (scan0) {
+      b[2] += b[3];
+      b[1] += b[2];
+      b[0] += b[1];
+      const double incl = wave_inclusive_scan<0>(b[0]);
+      excl0 = wave_shift_right1<0>(incl);
+      if (lane == 63) wave_total[c & 1][0][wave] = incl;
+    }
+    if (scan1) {
+      q[2] += q[3];
+      q[1] += q[2];
+      q[0] += q[1];
+      const double incl = wave_inclusive_scan<0>(q[0]);
+      excl1 = wave_shift_right1<0>(incl);
+      if (lane == 63) wave_total[c & 1][1][wave] = incl;
+    }
+    // (two buffers, as in grad_suffix_kernel; one barrier serves both scans)
+    __syncthreads();
+    double off0 = 0.0, off1 = 0.0;
+    if (scan0) {
+      double run = carry0;
+      off0 = carry0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k == wave) off0 = run;
+        run += wave_total[c & 1][0][k];
+      }
+      carry0 = run;
+      off0 += excl0;
+    }
+    if (scan1) {
+      double run = carry1;
+      off1 = carry1;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (k == wave) off1 = run;
+        run += wave_total[c & 1][1][k];
+      }
+      carry1 = run;
+      off1 += excl1;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (t0 + j >= T) continue;
+      double out = scan0 ? off0 + b[j] : 0.0;
+      if (scan1) {
+        const double sq = (off1 + q[j]) * exp_factor(en, w.aux_tab, t_plus, t0 + j);
+        out = scan0 ? out + sq : sq;
+      }
+      av[t0 + j] = out;
+    }
+  }
+}
+
+hipError_t launch_grad_w_suffix(const GradWArgs &w, bool total, int first, int count, hipStream_t st) {
+  if (w.g.N <= 0 || w.g.T <= 0 || count <= 0) return hipSuccess;
+  if (w.g.N > 0x7fffffffLL) return hipErrorInvalidValue;
+  for (int done = 0; done < count; done += 65535) {
+    const int part = count - done < 65535 ? count - done : 65535;
+    const dim3 grid((unsigned)w.g.N, (unsigned)part);
+    if (total)
+      hipLaunchKernelGGL(grad_w_suffix_kernel<true>, grid, dim3(256), 0, st, w, first + done);
+    else
+      hipLaunchKernelGGL(grad_w_suffix_kernel<false>, grid, dim3(256), 0, st, w, first + done);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+template <bool TOTAL>
+__global__ __launch_bounds__(256) void grad_w_input_kernel(GradWArgs w) {
+  const GradArgs &a = w.g;
+  const int64_t row = blockIdx.x;   // (series, dimension)
+  const int64_t N = a.N, D = a.D, T = a.T;
+  const int64_t n = row / D, d = row - n * D;
+  const double *__restrict__ xn = a.X + n * D * T;
+  const double *__restrict__ en = w.aux + n * w.aux_n;
+  const int ib = as_const(a.dim_begin)[d], ie = as_const(a.dim_begin)[d + 1];
+#pragma unroll
+  for (int e = 0; e < kGradTile / 256; ++e) {
+    const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
+    if (t >= T) continue;
+    const double x = xn[d * T + t];
+    double acc = 0.0;
+    for (int i = ib; i < ie; ++i) {
+      const int v = as_const(a.dim_item)[2 * i];
+      const int f = as_const(a.dim_item)[2 * i + 1];
+      const int ps = as_const(a.parent_srow)[v];
+      // total: dm_v = A_v E-_p E+_v shift(C_p); non-total: dm_v = A_v E-_p shift(C_p); shift(C)[0] = 0
+      double dm = a.A[((int64_t)v * N + n) * T + t];
+      if (ps >= 0)
+        dm = t > 0 ? dm * exp_factor(en, w.aux_tab, as_const(w.tab)[3 * v + 2], t) *
+                         w.C[((int64_t)ps * N + n) * T + t - 1]
+                   : 0.0;
+      if constexpr (TOTAL) dm *= exp_factor(en, w.aux_tab, as_const(w.tab)[3 * v], t);
+      const int ex = as_const(a.fac)[2 * f + 1];
+      const double dpow = ex > 0 ? (double)ex * ipow(x, ex - 1) : (double)ex * (1.0 / ipow(x, 1 - ex));
+      const double others = letter_value(a, xn, as_const(a.fac_begin)[v], as_const(a.fac_begin)[v + 1], t, f);
+      acc += dm * (dpow * others);
+    }
+    a.dX[row * T + t] = acc;
+  }
+}
+
+hipError_t launch_grad_w_input(const GradWArgs &w, bool total, hipStream_t st) {
+  const GradArgs &a = w.g;
+  if (a.N <= 0 || a.D <= 0 || a.T <= 0) return hipSuccess;
+  const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
+  if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(a.N * a.D), (unsigned)tiles);
+  if (total)
+    hipLaunchKernelGGL(grad_w_input_kernel<true>, grid, dim3(256), 0, st, w);
+  else
+    hipLaunchKernelGGL(grad_w_input_kernel<false>, grid, dim3(256), 0, st, w);
   return hipGetLastError();
 }
 

@@ -13,6 +13,13 @@ same for the two max semirings, ``Arctic()`` (max, +) and ``Bayesian()`` (max, x
 the gradient flows through the arg-max of every running maximum, of equal maxima through the
 FIRST (the tie rule of ``Arctic(argmax=True)``), and is a segmented suffix sum between the
 positions where a running maximum rises (``fr_iss_backward_max``).
+
+``weighted_iss(X, words, mode, weighting=...)`` and ``WeightedISSLayer(words, mode,
+weighting=...)`` are the Reals iterated sums with an exponential time penalty, total or not, for
+the weightings whose lookup does not depend on the input (``Indices``, ``Plateaus``).  Their
+backward pass forms the sums the forward pass carries from letter to letter itself, with a prefix
+scan per inner node of the trie, instead of a second walk (DESIGN.md 4.14.2,
+``fr_iss_backward_weighted``).
 """
 from __future__ import annotations
 
@@ -28,7 +35,8 @@ from .iss.iss import ISS, ISSMode
 from .iss.semiring import Arctic, Bayesian, Reals
 from .iss.words.word import SimpleWord
 
-__all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "backward_calls"]
+__all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "weighted_iss", "WeightedISSLayer",
+           "backward_calls"]
 
 _calls = {"backward": 0}
 _OPS: dict = {}      # the functional form's ISS objects by (word strings, mode, device), oldest first
@@ -36,8 +44,8 @@ _OPS_KEPT = 8
 
 
 def backward_calls() -> int:
-    """Backward passes launched by this process so far (one ``fr_iss_backward`` or
-    ``fr_iss_backward_max`` each)."""
+    """Backward passes launched by this process so far (one ``fr_iss_backward``,
+    ``fr_iss_backward_max`` or ``fr_iss_backward_weighted`` each)."""
     return _calls["backward"]
 
 
@@ -47,8 +55,8 @@ def _check_config(op: ISS) -> None:
         raise NotImplementedError("CosWISS has no backward pass: only the unweighted Reals ISS has")
     if op.weighting is not None:
         raise NotImplementedError(
-            f"a weighting ({type(op.weighting).__name__}) has no backward pass yet: only the "
-            "unweighted ISS has")
+            f"a weighting ({type(op.weighting).__name__}) has no backward pass here: the weighted "
+            "Reals iterated sums are nn.weighted_iss / nn.WeightedISSLayer")
     if not isinstance(op.semiring, Reals):
         raise NotImplementedError(
             f"the semiring {type(op.semiring).__name__} has no backward pass: only Reals has")
@@ -286,3 +294,158 @@ class MaxISSLayer(torch.nn.Module):
 
     def extra_repr(self) -> str:
         return f"{len(self.op.words)} words, {self.op.mode.name}, {type(self.op.semiring).__name__}"
+
+
+# ----------------------------------------------------------------------- weighted Reals
+def _check_weighted_config(op: ISS) -> None:
+    """``_check_config`` for ``weighted_iss``: raised before any launch."""
+    if isinstance(op, CosWISS):
+        raise NotImplementedError("CosWISS has no backward pass: only the trie walk's ISS has")
+    if op.weighting is None:
+        raise NotImplementedError(
+            "weighted_iss differentiates a weighted ISS: the unweighted iterated sums are "
+            "nn.iss / nn.ISSLayer")
+    if not op.weighting._supports_lengths():
+        raise NotImplementedError(
+            f"the lookup of the weighting {type(op.weighting).__name__} depends on the input, and "
+            "the gradient would have to flow through it too: only weightings whose lookup is a "
+            "function of the time step alone (Indices, Plateaus) have a backward pass")
+    if not isinstance(op.semiring, Reals):
+        raise NotImplementedError(
+            f"the semiring {type(op.semiring).__name__} has no weighted backward pass: only "
+            "Reals has")
+    op._check_supported()
+    if op._has_generic:
+        raise NotImplementedError(
+            "generic words have no backward pass: only words of SimpleWord letters have")
+
+
+def _weighted_prefix_program(op: ISS):
+    """``_prefix_program`` of a weighted ISS: the distinct (letters, alphas) prefixes as words of
+    depth 1, each with its slice of the alphas - two words with the same letters and other
+    alphas are other nodes, as in the plan compiler's trie - and per output row of ``op`` the
+    prefix, with the alphas of the word that emits the row."""
+    wmode = nat.FR_W_TOTAL if op.weighting.total else nat.FR_W_NONTOTAL
+    # (found by what the program is a function of besides the letters, as ISS._plan_indices does)
+    key = ("grad_weighted", op.mode, wmode,
+           tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in op.words))
+    prog = op._plans.get(key)
+    if prog is not None:
+        return prog
+    index, tables, alphas, row_prefix = {}, [], [], []
+    for i, word in enumerate(op.words):
+        depth = op._depth(i)
+        if depth == 0:
+            continue
+        tab = np.asarray(word.table(), dtype=np.int32)
+        alpha = np.asarray(word.alpha, dtype=np.float32)
+        L = tab.shape[0]
+        ident = ()
+        for k in range(L):
+            ident += ((tuple(np.trim_zeros(tab[k], "b").tolist()), alpha[k].tobytes()),)
+            if ident not in index:
+                index[ident] = len(tables)
+                tables.append(tab[:k + 1])
+                alphas.append(alpha[:k + 1])
+            if L - k <= depth:
+                row_prefix.append(index[ident])
+    plan = nat.Plan(tables, [1] * len(tables), alphas, wmode)
+    if plan.nodes != len(tables):
+        raise NotImplementedError("the prefix trie of these words is too deep for the walk's "
+                                  "register frames: no backward pass")
+    prog = op._plans[key] = (plan, np.asarray(row_prefix, dtype=np.int32))
+    return prog
+
+
+class _WeightedISSFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, op):
+        Xc = X.contiguous()
+        Y = op.transform_device(Xc)          # (K, N, T)
+        ctx.op = op
+        ctx.save_for_backward(Xc)
+        return Y.permute(1, 0, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        Xc, = ctx.saved_tensors
+        plan, row_prefix = _weighted_prefix_program(ctx.op)
+        with torch.cuda.device(Xc.device):
+            # (the lookup is a function of T alone: formed again, not kept; the prefix plan
+            # itself never runs - the entry forms the carried sums - so it need not fit the LDS)
+            lookup = ctx.op.lookup_device(Xc)
+            _calls["backward"] += 1
+            return nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix), None
+
+
+def _apply_weighted(op: ISS, X):
+    _check_input(op, X)
+    with torch.cuda.device(X.device):
+        return _WeightedISSFunction.apply(X, op)
+
+
+def _weighted_op(words, mode, weighting) -> ISS:
+    if isinstance(words, ISS):
+        if weighting is not None and weighting is not words.weighting:
+            raise TypeError("the ISS carries its own weighting")
+        return words
+    return ISS(list(words), mode=mode, weighting=weighting)
+
+
+def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
+    """Weighted Reals iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the
+    row order of ``ISS(words, mode, weighting=weighting).transform(X)`` and with its bits;
+    differentiable with respect to ``X``.  ``weighting``: an ``Indices`` or a ``Plateaus``, total or
+    not - the weightings whose lookup does not depend on ``X``; or ``words`` is an ``ISS`` that
+    carries one.  The letters' alphas are the words' (``word.alpha``).
+
+    The backward pass is ``fr_iss_backward_weighted``: it forms the sums the
+    forward pass carries from letter to letter with a prefix scan per inner trie node, then the
+    adjoint with suffix scans, the exp factors ``exp(+-g alpha)`` as constants."""
+    op = key = None
+    if not isinstance(words, ISS):
+        words = list(words)
+        # (kept between calls like nn.iss keeps its plain case; the ISS holds the weighting, so
+        # its id names it for as long as the entry lives)
+        if weighting is not None and all(isinstance(w, SimpleWord) for w in words):
+            key = ("weighted", id(weighting), tuple(str(w) for w in words),
+                   tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in words), mode,
+                   str(getattr(X, "device", None)))
+            op = _OPS.get(key)
+    if op is None:
+        op = _weighted_op(words, mode, weighting)
+        if key is not None:
+            if len(_OPS) >= _OPS_KEPT:
+                _OPS.pop(next(iter(_OPS)))
+            _OPS[key] = op
+    _check_weighted_config(op)
+    return _apply_weighted(op, X)
+
+
+class WeightedISSLayer(torch.nn.Module):
+    """``weighted_iss`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, weighting=None) -> None:
+        super().__init__()
+        self.op = _weighted_op(words, mode, weighting)
+        _check_weighted_config(self.op)
+
+    @property
+    def words(self):
+        return self.op.words
+
+    @property
+    def mode(self) -> ISSMode:
+        return self.op.mode
+
+    @property
+    def weighting(self):
+        return self.op.weighting
+
+    def forward(self, X):
+        return _apply_weighted(self.op, X)
+
+    def extra_repr(self) -> str:
+        return (f"{len(self.op.words)} words, {self.op.mode.name}, "
+                f"{type(self.op.weighting).__name__}{' total' if self.op.weighting.total else ''}")

@@ -733,6 +733,38 @@ int fr_iss_backward_max(fr_plan_t *prefix_plan, const double *d_X, int64_t N, in
                         int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
                         double *d_A, double *d_dX, void *stream);
 
+/* The same for WEIGHTED Reals iterated sums, total or not: the adjoint of both bodies of
+ * fruits/iss/semiring.py:98-158 (_reals_single with alpha, :98-125; _total_weighted_reals_single,
+ * :128-158) with respect to the input, the lookup g being a constant.  Not in the reference.
+ *
+ * `prefix_plan`: an FR_W_NONTOTAL or FR_W_TOTAL Reals plan whose words are the DISTINCT
+ *   (letters, alphas) prefixes of the differentiated words, each with its slice of the alphas and
+ *   depth 1.  FR_E_ARG, on the host and before any launch, for an unweighted plan (its entry is
+ *   fr_iss_backward), an Arctic or Bayesian plan (fr_iss_backward_max takes the unweighted ones),
+ *   a CosWISS plan, a plan that is no prefix plan, a bad row map, a null pointer, d_dX == d_X.
+ * d_lookup (lookup_rows, T), lookup_rows in {1, N}: g, as fr_iss_run takes it.
+ * d_G, K, the strides, h_row_prefix, d_dX: as in fr_iss_backward.
+ * d_C (V, N, T), d_A (V, N, T), d_aux (2 * alphas * lookup_rows * T; alphas = FR_INFO_ALPHAS of
+ *   the plan): scratch, distinct buffers.
+ * With E+_v = exp(g alpha_v), E-_v = exp(-g alpha_v) of the node's last letter, p its parent and
+ * the carried sums C_v = cumsum(y_v), y_v[t] = m_v[t] E-_p[t] E+_v[t] C_p[t-1] (depth 1:
+ * m_v E+_v), which this entry forms itself - it does not need the plan's output - deepest first:
+ *   total:      B_v[s] = G_v[s] E-_v[s] + sum_c m_c[s+1] E-_v[s+1] E+_c[s+1] A_c[s+1]
+ *               A_v = suffix sum of B_v;   dm_v = A_v E-_p E+_v shift(C_p)
+ *   non-total:  Q_v[s] = sum_c m_c[s+1] E-_v[s+1] A_c[s+1]
+ *               A_v = suffix(G_v) + E+_v suffix(Q_v);   dm_v = A_v E-_p shift(C_p)
+ *   dX_d[t] = sum over nodes v of dm_v[t] d m_v / d x_d [t]   (powers by multiplication)
+ * Nothing is divided by an exp factor.  One association per sum whatever the grid: bit-identical
+ * from run to run and whatever the batch split.  The plan need not fit a workgroup's LDS
+ * (fr_plan_fits): the exp tables are read from d_aux.  Tables are kept with the plan as
+ * fr_iss_backward keeps them; later calls enqueue the exp tables, two launches per trie depth
+ * at most and one more.  FR_E_DIM / FR_E_LIMIT as fr_iss_backward. */
+int fr_iss_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D,
+                             int64_t T, const double *d_lookup, int64_t lookup_rows,
+                             const double *d_G, int64_t K, int64_t g_n_stride, int64_t g_k_stride,
+                             int64_t g_t_stride, const int32_t *h_row_prefix, double *d_C,
+                             double *d_A, double *d_aux, double *d_dX, void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest
