@@ -1173,6 +1173,29 @@ def rows_unshift(Ad, shifts, out=None, shifts_d=None):
 
 
 # ----------------------------------------------------------------------- backward pass
+def _backward_args(prefix_plan: Plan, Xd, G, row_prefix):
+    """What the backward entries share: ``(N, D, T, K, V)``, the row map as a contiguous int32
+    host array and the strides of the checked upstream gradient."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
+    K = int(rp.shape[0])
+    if G.dtype != t.float64 or tuple(G.shape) != (N, K, T) or G.device != Xd.device:
+        raise TypeError("the upstream gradient must be a float64 (N, K, T) tensor on the input's device")
+    return (N, D, T, K, prefix_plan.rows), rp, [C.c_int64(int(s)) for s in G.stride()]
+
+
+def _backward_scratch(work, need: int, what: str, Xd):
+    """The caller's scratch if it holds ``need`` doubles (``what``: that number in words), or a
+    fresh one."""
+    t = torch()
+    if work is None:
+        return t.empty((need,), dtype=t.float64, device=Xd.device)
+    if work.dtype != t.float64 or work.numel() < need or not work.is_contiguous():
+        raise TypeError(f"the scratch must be a contiguous float64 device tensor of {what} elements")
+    return work
+
+
 def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, entry="fr_iss_backward"):
     """fr_iss_backward: the gradient ``(N, D, T)`` of unweighted Reals iterated sums with respect
     to ``Xd``.  ``prefix_plan``: the plan of the distinct prefixes, each with depth 1; ``Sd``
@@ -1181,23 +1204,14 @@ def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, entry="fr_
     row k is; ``work``: a ``(V, N, T)`` scratch if the caller keeps one.  ``entry``: the ABI
     entry that takes these arguments (``iss_backward_max``)."""
     t = torch()
-    N, D, T = _rows3(Xd)
-    rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
-    K = int(rp.shape[0])
-    V = prefix_plan.rows
-    if G.dtype != t.float64 or tuple(G.shape) != (N, K, T) or G.device != Xd.device:
-        raise TypeError("the upstream gradient must be a float64 (N, K, T) tensor on the input's device")
+    (N, D, T, K, V), rp, (sn, sk, st) = _backward_args(prefix_plan, Xd, G, row_prefix)
     if Sd.dtype != t.float64 or tuple(Sd.shape) != (V, N, T) or not Sd.is_contiguous():
         raise TypeError("the prefix sums must be a contiguous float64 (V, N, T) device tensor")
-    if work is None:
-        work = t.empty((V, N, T), dtype=t.float64, device=Xd.device)
-    elif work.dtype != t.float64 or work.numel() < V * N * T or not work.is_contiguous():
-        raise TypeError("the scratch must be a contiguous float64 device tensor of V * N * T elements")
+    work = _backward_scratch(work, V * N * T, "V * N * T", Xd)
     dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
-    sn, sk, st = (int(s) for s in G.stride())
     check(getattr(lib(), entry)(prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
-                                dptr(Sd), dptr(G), C.c_int64(K), C.c_int64(sn), C.c_int64(sk),
-                                C.c_int64(st), _i32p(rp), dptr(work), dptr(dX), stream_ptr()),
+                                dptr(Sd), dptr(G), C.c_int64(K), sn, sk, st, _i32p(rp), dptr(work),
+                                dptr(dX), stream_ptr()),
           entry)
     return dX
 
@@ -1217,30 +1231,19 @@ def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=N
     the carried sums itself: it takes no output of the plan.  ``work``: a scratch of
     ``2 V N T + 2 alphas rows T`` doubles if the caller keeps one."""
     t = torch()
-    N, D, T = _rows3(Xd)
-    rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
-    K = int(rp.shape[0])
-    V = prefix_plan.rows
-    if G.dtype != t.float64 or tuple(G.shape) != (N, K, T) or G.device != Xd.device:
-        raise TypeError("the upstream gradient must be a float64 (N, K, T) tensor on the input's device")
+    (N, D, T, K, V), rp, (sn, sk, st) = _backward_args(prefix_plan, Xd, G, row_prefix)
     if (lookup_d is None or lookup_d.dtype != t.float64 or lookup_d.dim() != 2
             or int(lookup_d.shape[1]) != T or int(lookup_d.shape[0]) not in (1, N)
             or not lookup_d.is_contiguous() or lookup_d.device != Xd.device):
         raise TypeError("the lookup must be a contiguous float64 (1 | N, T) tensor on the input's device")
     rows = int(lookup_d.shape[0])
     cells, aux = V * N * T, 2 * prefix_plan.info(FR_INFO_ALPHAS) * rows * T
-    if work is None:
-        work = t.empty((2 * cells + aux,), dtype=t.float64, device=Xd.device)
-    elif work.dtype != t.float64 or work.numel() < 2 * cells + aux or not work.is_contiguous():
-        raise TypeError("the scratch must be a contiguous float64 device tensor of "
-                        "2 V N T + 2 alphas rows T elements")
-    work = work.view(-1)
+    work = _backward_scratch(work, 2 * cells + aux, "2 V N T + 2 alphas rows T", Xd).view(-1)
     dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
-    sn, sk, st = (int(s) for s in G.stride())
     # (the scratch in three parts; an empty part still gets a distinct address)
     parts = [C.c_void_p(work.data_ptr() + 8 * o) for o in (0, cells, 2 * cells)]
     check(lib().fr_iss_backward_weighted(
         prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
-        C.c_int64(rows), dptr(G), C.c_int64(K), C.c_int64(sn), C.c_int64(sk), C.c_int64(st),
+        C.c_int64(rows), dptr(G), C.c_int64(K), sn, sk, st,
         _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
     return dX

@@ -132,11 +132,19 @@ hipError_t launch_letter_rows(const double *X, int64_t N, int64_t D, int64_t T, 
                               hipStream_t st);
 hipError_t launch_rows_unshift(const double *A, int64_t K, int64_t N, int64_t T,
                                const int32_t *shift, double *out, hipStream_t st);
-// the backward pass of the Reals walk (kernels_grad.hip): the tables of the prefix trie, all on
-// the device.  Node v is the plan's node v (DFS preorder); CSR tables have V + 1 (D + 1) offsets.
+// the backward pass of the trie walk (kernels_grad.hip): which adjoint, and the
+// tables of the prefix trie, all on the device.  Node v is the plan's node v (DFS preorder); CSR
+// tables have V + 1 (D + 1) offsets.
+enum GradKind : int {
+  kGradReals = 0,   // unweighted Reals
+  kGradTotal,       // weighted Reals, total
+  kGradNonTotal,    // weighted Reals, non-total
+  kGradArctic,      // (max, +): the exponent of a `fac` pair is the letter's coefficient
+  kGradBayesian,    // (max, x)
+};
 struct GradArgs {
   const double *X;      // (N, D, T)
-  const double *S;      // (V, N, T): row r = the iterated sum of the prefix with output row r
+  const double *S;      // (V, N, T): row r = the iterated sum of the prefix with output row r (unweighted kinds)
   const double *G;      // upstream gradient, element (n, k, t) at n * g_n + k * g_k + t * g_t
   double *A;            // (V, N, T) scratch: the suffix sums, by node
   double *dX;           // (N, D, T), every element written
@@ -149,21 +157,9 @@ struct GradArgs {
   const int32_t *level_nodes;             // the nodes by falling depth
   const int32_t *dim_begin, *dim_item;    // per input dimension: pairs {node, index into fac}
   const int32_t *self_srow;               // row of S of the node itself (the max semirings' heads)
-};
-constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)
-// A of `count` nodes of one depth, level_nodes[first ...]: their children's A must be complete
-hipError_t launch_grad_suffix(const GradArgs &a, int first, int count, hipStream_t st);
-hipError_t launch_grad_input(const GradArgs &a, hipStream_t st);
-// the same for the max semirings (`semiring`: kSemiArctic or kSemiBayesian of walk_types.h;
-// hipErrorInvalidValue for another): the SEGMENTED suffix sums between the heads of S_v, and the
-// gather without a shift.  Arctic: the exponent of a `fac` pair is the letter's coefficient.
-hipError_t launch_grad_max_suffix(const GradArgs &a, int semiring, int first, int count, hipStream_t st);
-hipError_t launch_grad_max_input(const GradArgs &a, int semiring, hipStream_t st);
-// the backward pass of a WEIGHTED Reals plan: the tables of GradArgs - `g.S` is
-// unused - and what the exp weights add.  C holds the CARRIED sums C_v = cumsum(y_v), which the
-// kernels form themselves; rows of C are numbered like the rows of S (self_srow, parent_srow).
-struct GradWArgs {
-  GradArgs g;
+  // what the exp weights add; null or 0 for the unweighted kinds.  C holds the
+  // CARRIED sums C_v = cumsum(y_v), which the kernels form themselves; rows of C are numbered
+  // like the rows of S (self_srow, parent_srow).
   double *C;            // (V, N, T) scratch: the carried sums of the nodes that have children
   const double *aux;    // (2 n_alpha, rows, T): table 2a = exp(+g alpha_a), 2a + 1 = exp(-g alpha_a)
   int64_t aux_tab;      // doubles from one table to the next (rows * T)
@@ -171,10 +167,17 @@ struct GradWArgs {
   const int32_t *tab;   // three tables per node: its own E+, its own E-, its parent's E- (-1: unused)
   const int32_t *inner_nodes;   // the nodes that have children, by rising depth
 };
+constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)
+// Every launcher: hipErrorInvalidValue for a kind that is not its own, or a grid limit.
+// A of `count` nodes of one depth, level_nodes[first ...]: their children's A must be complete.
+// Additive suffix sums (kGradReals, kGradTotal, kGradNonTotal) ...
+hipError_t launch_grad_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st);
+// ... and SEGMENTED ones between the heads of S_v, the gather without a shift (kGradArctic, kGradBayesian)
+hipError_t launch_grad_max_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st);
 // C of `count` nodes of one depth, inner_nodes[first ...]: their parents' C must be complete
-hipError_t launch_grad_w_prefix(const GradWArgs &a, int first, int count, hipStream_t st);
-// A of `count` nodes of one depth, g.level_nodes[first ...], as launch_grad_suffix
-hipError_t launch_grad_w_suffix(const GradWArgs &a, bool total, int first, int count, hipStream_t st);
-hipError_t launch_grad_w_input(const GradWArgs &a, bool total, hipStream_t st);
+// (kGradTotal, kGradNonTotal)
+hipError_t launch_grad_prefix(const GradArgs &a, int kind, int first, int count, hipStream_t st);
+// dX from the finished A (every kind)
+hipError_t launch_grad_input(const GradArgs &a, int kind, hipStream_t st);
 
 }  // namespace fr

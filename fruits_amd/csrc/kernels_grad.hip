@@ -1,29 +1,73 @@
-// The backward pass of the Reals trie walk: the gradient of unweighted iterated sums with respect
-// to their input.  The forward pass is, node by node of the prefix trie,
-//     S_v = cumsum(m_v * shift(S_p)),   m_v[t] = prod_d x_d[t]^e_vd
-// (fruits/iss/semiring.py:98-125); its adjoint walks the trie leaves-to-root with SUFFIX sums:
-//     B_v[t] = G_v[t] + sum over children c of m_c[t+1] A_c[t+1]        (nothing at t = T-1)
-//     A_v[t] = sum over s >= t of B_v[s]
-//     dX_d[t] = sum over v of A_v[t] shift(S_p)[t] dm_v/dx_d[t]
+// The backward pass of the trie walk: the gradient of iterated sums with respect to their input
+// (DESIGN.md 4.14), for five adjoints - GradKind of kernels.h: unweighted Reals, weighted Reals
+// total and non-total, Arctic, Bayesian.
 //
-// Two kernels.  grad_suffix_kernel: one workgroup of 256 lanes per (node, series), launched depth
-// by depth, the deepest nodes first, so a node GATHERS the finished A of its children (no atomics).
-// It walks the time axis in chunks of kGradChunk steps from the last chunk to the first with a
-// carry from the right.  Lane i owns the four time steps [c0 + 1020 - 4 i, c0 + 1023 - 4 i] of a
-// chunk: the lane-to-time map is REVERSED, so the suffix sum over time is an inclusive prefix scan
-// over the lanes - wave_inclusive_scan of walk_scan.h as it is - with the four wave totals through
-// LDS.  grad_input_kernel: one thread per element of dX, which adds the terms of the nodes whose
-// letter holds its dimension in the fixed order of the table.  Every sum has one association,
-// whatever the grid: the result is the same bits from run to run.
-//
+// THE SHARED FRAME.  Every adjoint walks the prefix trie leaves-to-root: per node v a row B_v of
+// what reaches it - the rows of the upstream gradient G it emitted plus a term of each child's
+// finished A_c - and A_v = a scan of B_v over time; then per element of dX a sum over the nodes
+// whose letter holds its dimension.
+//   * Scan kernels: one workgroup of 256 lanes per (node, series), launched depth by depth
+//     (launch_per_depth), the deepest nodes first, so a node GATHERS the finished A of its children
+//     (no atomics).  A workgroup walks the time axis in chunks of kGradChunk steps with a carry
+//     from chunk to chunk; a lane owns four adjacent steps of a chunk.  For the suffix kernels the
+//     chunks run from the last to the first and the lane-to-time map is REVERSED (reversed_t0:
+//     lane i owns [c0 + 1020 - 4 i, c0 + 1023 - 4 i]), so the suffix sum over time is an inclusive
+//     prefix scan over the lanes - wave_inclusive_scan of walk_scan.h as it is.  The block scan has
+//     two phases around the caller's ONE barrier: scan_publish (the wave scan; lane 63 leaves the
+//     wave's total in an LDS slot) and scan_offset (the four wave totals join the carry in wave
+//     order).  The slots are double-buffered by the chunk's parity: a wave that runs ahead writes
+//     the other buffer, and nobody reaches the chunk after that before every wave has passed this
+//     chunk's barrier.
+//   * gather_upstream adds the node's rows of G; the children's terms are the adjoint's own.
+//   * grad_input_kernel: one thread per element of dX, which adds the terms dm_v * d(letter)/dx of
+//     the nodes in the fixed order of the table (dim_item); the adjoints differ in dm_v alone.
+// Every sum has one association, whatever the grid: the result is the same bits from run to run.
 // Plain loads and stores only; all offsets are 64-bit; every access is guarded by t < T.  The
 // tables are wave-uniform and read through the constant address space (scalar loads).
 //
-// Below them, the same pair for the max semirings Arctic and Bayesian (grad_max_suffix_kernel,
-// grad_max_input_kernel): the suffix sums become SEGMENTED sums between the heads of S_v.  And at
-// the end the kernels of weighted Reals plans (grad_w_prefix_kernel, grad_w_suffix_kernel,
-// grad_w_input_kernel): the exp factors join the products, and a prefix scan forms the sums the
-// forward pass carries from letter to letter.
+// WHAT EACH ADJOINT ADDS.
+// Reals, unweighted (fruits/iss/semiring.py:98-125): S_v = cumsum(m_v * shift(S_p)),
+// m_v[t] = prod_d x_d[t]^e_vd.
+//     B_v[t] = G_v[t] + sum over children c of m_c[t+1] A_c[t+1]        (nothing at t = T-1)
+//     A_v[t] = sum over s >= t of B_v[s];      dm_v = A_v shift(S_p)
+// S is the caller's: one more forward walk of the prefix plan.
+//
+// Reals, weighted (semiring.py:98-158; E+_v = exp(g alpha_v), E-_v =
+// exp(-g alpha_v) of the node's last letter).  Both bodies carry the same sums from letter to
+// letter,
+//     y_v[t] = m_v[t] E-_p[t] E+_v[t] C_p[t-1]   (depth 1: m_v[t] E+_v[t]),   C_v = cumsum(y_v)
+// and differ in what a node emits: S_v = C_v E-_v (total) or S_v = cumsum(z_v), y_v = z_v E+_v
+// (non-total).  The adjoint, children c reading C_v[s] at time s + 1:
+//     total:      B_v[s] = G_v[s] E-_v[s] + sum_c m_c[s+1] E-_v[s+1] E+_c[s+1] A_c[s+1]
+//                 A_v = suffix(B_v);                          dm_v = A_v E-_p E+_v shift(C_p)
+//     non-total:  Q_v[s] = sum_c m_c[s+1] E-_v[s+1] A_c[s+1]
+//                 A_v = suffix(G_v) + E+_v suffix(Q_v);       dm_v = A_v E-_p shift(C_p)
+// Nothing is divided by an exp factor.  Non-total is two scans with two carries behind the one
+// barrier; a scan whose operand is empty - a node that is no output row, a node without children -
+// is skipped (block-uniform branches).  The forward walk of a non-total plan emits S, not C, so
+// grad_prefix_kernel forms C of the nodes that have children, root first, with the forward lane
+// map; the exp tables are read from global memory (launch_exp_tables filled them on the stream).
+//
+// Arctic (max, +) and Bayesian (max, x), semiring.py:282-309 and :461-493: per node
+//     z_v = m_v (x) S_p (no shift; m_v alone at depth 1),   S_v = running maximum of z_v
+// with m_v[t] = sum_d e_vd x_d[t] (Arctic) or prod_d x_d[t]^e_vd (Bayesian).  A HEAD of v is a
+// time s with s == 0 or S_v[s] > S_v[s-1] - strictly, the first of equal maxima wins - and opens
+// the segment [s, next head): S_v[t] = z_v[s] for every t of it.
+//     B_v[t] = G_v[t] + sum over children c of w_c[t] A_c[t]      (w_c = 1 Arctic, m_c[t] Bayesian)
+//     A_v[s] = sum of B_v over the segment of s at a head s, 0.0 elsewhere
+//     Arctic: dX_d[s] = sum_v e_vd A_v[s];   Bayesian: dm_v = A_v S_p at the same step
+// grad_max_suffix_kernel stands in the frame of grad_suffix_kernel - chunks, reversed map, slot
+// parity, one barrier -; its scan is SEGMENTED and keeps its own operator.  Walking time
+// downwards, what crosses from t + 1 to t is the open sum carry(t + 1) = head(t + 1) ? 0 : R[t + 1]
+// with R[t] = B[t] + carry(t + 1), and A[t] = head(t) ? R[t] : 0.  A run of time steps [lo, hi]
+// acts on the carry that enters it from the right as  c -> f ? o : o + c  with f = "a head in the
+// run" and o = the sum of B from lo up to the run's first head (the whole run without one); a run
+// `a` to the right of a run `b` compose as  (o_a, f_a) o (o_b, f_b) = (f_b ? o_b : o_a + o_b,
+// f_a | f_b).  So a segment's sum is only ever formed from that segment's B - never as a
+// difference of two suffix sums - and every partial sum joins disjoint runs of one segment.  The
+// flags of the 64 lanes are one ballot: a lane decides each step of the wave scan with a bit test,
+// only the sums travel by DPP.  Across waves and chunks the carry is the value c alone (a pair
+// applied to it gives a value).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -31,12 +75,20 @@
 
 namespace fr {
 
+constexpr bool grad_weighted(int kind) { return kind == kGradTotal || kind == kGradNonTotal; }
+
 // x^e for e >= 0 by multiplication (e - 1 roundings; x^0 = 1 for every x, a zero included)
 __device__ __forceinline__ double ipow(double x, int e) {
   if (e == 0) return 1.0;
   double p = x;
   for (int i = 1; i < e; ++i) p *= x;
   return p;
+}
+
+// d/dx x^e = e x^(e-1), the power by multiplication (never m / x: a zero input is an ordinary
+// one); e < 0: e / x^(|e|+1)
+__device__ __forceinline__ double dpow(double x, int e) {
+  return e > 0 ? (double)e * ipow(x, e - 1) : (double)e * (1.0 / ipow(x, 1 - e));
 }
 
 // The letter prod_d x_d[t]^e_d of the factors [fb, fe) at time t of the series whose rows start
@@ -54,136 +106,219 @@ __device__ __forceinline__ double letter_value(const GradArgs &a, const double *
   return m;
 }
 
-__global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first) {
-  __shared__ double wave_total[2][4];
-  const int64_t n = blockIdx.x;
-  const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
-  const int64_t N = a.N, T = a.T;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double *__restrict__ xn = a.X + n * a.D * T;
-  const double *__restrict__ gn = a.G + n * a.g_n;
-  double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
-  const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
-  const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
+// Table `tb` (-1: none, the factor 1.0) of the series whose tables start at `aux_n` at time t.
+__device__ __forceinline__ double exp_factor(const double *__restrict__ aux_n, int64_t aux_tab, int tb,
+                                             int64_t t) {
+  return tb < 0 ? 1.0 : aux_n[(int64_t)tb * aux_tab + t];
+}
 
-  double carry = 0.0;   // sum of B_v over the chunks to the right
-  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
-  for (int64_t c = chunks - 1; c >= 0; --c) {
-    const int64_t t0 = c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
-    double b[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int g = gb; g < ge; ++g) {
-      const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
+// ------------------------------------------------------------------ the shared frame
+// The chunks of a time axis and the first of the four steps of this lane in chunk c.
+__device__ __forceinline__ int64_t grad_chunks(int64_t T) { return (T + kGradChunk - 1) / kGradChunk; }
+__device__ __forceinline__ int64_t forward_t0(int64_t c) { return c * kGradChunk + 4 * (int64_t)threadIdx.x; }
+__device__ __forceinline__ int64_t reversed_t0(int64_t c) {
+  return c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
+}
+
+// The additive block scan over the lanes' totals, lane 0 first.  Publish: the wave scan; lane 63
+// leaves the wave's total in slot[wave]; returns the sum of the lanes in front within the wave.
+__device__ __forceinline__ double scan_publish(double total, double *slot) {
+  const double incl = wave_inclusive_scan<0>(total);
+  const double excl = wave_shift_right1<0>(incl);
+  if ((threadIdx.x & 63) == 63) slot[threadIdx.x >> 6] = incl;
+  return excl;
+}
+
+// Offset, after the barrier: the wave totals join `carry` in wave order; returns the sum of
+// everything in front of this lane - the chunks before, the waves before, `excl` - and leaves
+// the carry of the next chunk.
+__device__ __forceinline__ double scan_offset(const double *slot, double excl, double &carry) {
+  const int wave = threadIdx.x >> 6;
+  double run = carry, off = carry;
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (t0 + j < T) b[j] += gk[(t0 + j) * a.g_t];
-    }
-    for (int ci = cb; ci < ce; ++ci) {
-      const int ch = as_const(a.child)[ci];
-      const int fb = as_const(a.fac_begin)[ch], fe = as_const(a.fac_begin)[ch + 1];
-      const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (t0 + j + 1 < T) b[j] += letter_value(a, xn, fb, fe, t0 + j + 1, -1) * ac[t0 + j + 1];
-    }
-    // the lane's own suffix sums (steps past T hold exact zeros), then the lanes from the right
-    b[2] += b[3];
-    b[1] += b[2];
-    b[0] += b[1];
-    const double incl = wave_inclusive_scan<0>(b[0]);
-    const double excl = wave_shift_right1<0>(incl);
-    if (lane == 63) wave_total[c & 1][wave] = incl;
-    // (two buffers: a wave that runs ahead writes the other one, and nobody reaches the chunk
-    // after that before every wave has passed this barrier)
-    __syncthreads();
-    double run = carry, off = carry;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      if (w == wave) off = run;
-      run += wave_total[c & 1][w];
-    }
-    carry = run;
-    off += excl;
+  for (int w = 0; w < 4; ++w) {
+    if (w == wave) off = run;
+    run += slot[w];
+  }
+  carry = run;
+  return off + excl;
+}
+
+// The lane's own inclusive sums, towards its first step (the reversed map: suffix sums over time).
+__device__ __forceinline__ void lane_suffix(double (&b)[4]) {
+  b[2] += b[3];
+  b[1] += b[2];
+  b[0] += b[1];
+}
+
+// b[j] += the rows [gb, ge) of the upstream gradient of the series at `gn`, at the steps t0 + j.
+__device__ __forceinline__ void gather_upstream(const GradArgs &a, const double *__restrict__ gn, int gb,
+                                                int ge, int64_t t0, double (&b)[4]) {
+  for (int g = gb; g < ge; ++g) {
+    const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (t0 + j < T) av[t0 + j] = off + b[j];
+      if (t0 + j < a.T) b[j] += gk[(t0 + j) * a.g_t];
   }
 }
 
-hipError_t launch_grad_suffix(const GradArgs &a, int first, int count, hipStream_t st) {
+// `count` workgroups per series, blockIdx.y < 65535 each launch: nodes [first, first + count) of
+// a per-depth table.
+template <typename Args>
+hipError_t launch_per_depth(void (*kernel)(Args, int), const Args &a, int first, int count, hipStream_t st) {
   if (a.N <= 0 || a.T <= 0 || count <= 0) return hipSuccess;
   if (a.N > 0x7fffffffLL) return hipErrorInvalidValue;
   for (int done = 0; done < count; done += 65535) {
     const int part = count - done < 65535 ? count - done : 65535;
-    hipLaunchKernelGGL(grad_suffix_kernel, dim3((unsigned)a.N, (unsigned)part), dim3(256), 0, st, a,
-                       first + done);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)a.N, (unsigned)part), dim3(256), 0, st, a, first + done);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-constexpr int kGradTile = 1024;   // time steps of a workgroup of grad_input_kernel (4 per lane, strided)
+// ------------------------------------------------------------------ the additive suffix scans
+// KIND: kGradReals, kGradTotal or kGradNonTotal.  Slot 0 scans B_v (non-total: G_v), slot 1 - of
+// the non-total body alone - Q_v; the unweighted kernel has no exp factor and always scans.
+template <int KIND>
+__global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first) {
+  constexpr bool WEIGHTED = grad_weighted(KIND), TOTAL = KIND == kGradTotal;
+  __shared__ double wave_total[2][KIND == kGradNonTotal ? 2 : 1][4];
+  const int64_t n = blockIdx.x;
+  const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
+  const int64_t N = a.N, T = a.T;
+  const double *__restrict__ xn = a.X + n * a.D * T;
+  const double *__restrict__ gn = a.G + n * a.g_n;
+  const double *__restrict__ en = WEIGHTED ? a.aux + n * a.aux_n : nullptr;
+  double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
+  const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
+  const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
+  int t_plus = -1, t_minus = -1;
+  if constexpr (WEIGHTED) {
+    t_plus = as_const(a.tab)[3 * v];
+    t_minus = as_const(a.tab)[3 * v + 1];
+  }
+  const bool has_g = ge > gb, has_c = ce > cb;
+  const bool scan0 = !WEIGHTED || (TOTAL ? (has_g || has_c) : has_g);
+  const bool scan1 = KIND == kGradNonTotal && has_c;
 
-__global__ __launch_bounds__(256) void grad_input_kernel(GradArgs a) {
-  const int64_t row = blockIdx.x;   // (series, dimension)
-  const int64_t N = a.N, D = a.D, T = a.T;
-  const int64_t n = row / D, d = row - n * D;
-  const double *__restrict__ xn = a.X + n * D * T;
-  const int ib = as_const(a.dim_begin)[d], ie = as_const(a.dim_begin)[d + 1];
+  double carry0 = 0.0, carry1 = 0.0;   // the sums over the chunks to the right
+  for (int64_t c = grad_chunks(T) - 1; c >= 0; --c) {
+    const int64_t t0 = reversed_t0(c);
+    double b[4] = {0.0, 0.0, 0.0, 0.0};   // B_v; non-total: G_v
+    double q[4] = {0.0, 0.0, 0.0, 0.0};   // non-total: Q_v
+    gather_upstream(a, gn, gb, ge, t0, b);
+    if (TOTAL && has_g) {
 #pragma unroll
-  for (int e = 0; e < kGradTile / 256; ++e) {
-    const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
-    if (t >= T) continue;
-    const double x = xn[d * T + t];
-    double acc = 0.0;
-    for (int i = ib; i < ie; ++i) {
-      const int v = as_const(a.dim_item)[2 * i];
-      const int f = as_const(a.dim_item)[2 * i + 1];
-      const int ps = as_const(a.parent_srow)[v];
-      // dm_v = A_v * shift(S_p); shift(S)[0] = 0
-      double dm = a.A[((int64_t)v * N + n) * T + t];
-      if (ps >= 0) dm *= t > 0 ? a.S[((int64_t)ps * N + n) * T + t - 1] : 0.0;
-      // d/dx x^e = e x^(e-1), the power by multiplication (never m / x: a zero input is an
-      // ordinary one); e < 0: e / x^(|e|+1)
-      const int ex = as_const(a.fac)[2 * f + 1];
-      const double dpow = ex > 0 ? (double)ex * ipow(x, ex - 1) : (double)ex * (1.0 / ipow(x, 1 - ex));
-      const double others = letter_value(a, xn, as_const(a.fac_begin)[v], as_const(a.fac_begin)[v + 1], t, f);
-      acc += dm * (dpow * others);
+      for (int j = 0; j < 4; ++j)
+        if (t0 + j < T) b[j] *= exp_factor(en, a.aux_tab, t_minus, t0 + j);
     }
-    a.dX[row * T + t] = acc;
+    for (int ci = cb; ci < ce; ++ci) {
+      const int ch = as_const(a.child)[ci];
+      const int fb = as_const(a.fac_begin)[ch], fe = as_const(a.fac_begin)[ch + 1];
+      const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
+      int c_plus = -1;
+      if constexpr (TOTAL) c_plus = as_const(a.tab)[3 * ch];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t s = t0 + j + 1;
+        if (s >= T) continue;
+        double term = letter_value(a, xn, fb, fe, s, -1);
+        if constexpr (WEIGHTED) term *= exp_factor(en, a.aux_tab, t_minus, s);
+        if constexpr (TOTAL) term *= exp_factor(en, a.aux_tab, c_plus, s);
+        if constexpr (KIND == kGradNonTotal)
+          q[j] += term * ac[s];
+        else
+          b[j] += term * ac[s];
+      }
+    }
+    // the lane's own suffix sums (steps past T hold exact zeros), then the lanes from the right
+    double excl0 = 0.0, excl1 = 0.0;
+    if (scan0) {
+      lane_suffix(b);
+      excl0 = scan_publish(b[0], wave_total[c & 1][0]);
+    }
+    if constexpr (KIND == kGradNonTotal) {
+      if (scan1) {
+        lane_suffix(q);
+        excl1 = scan_publish(q[0], wave_total[c & 1][1]);
+      }
+    }
+    __syncthreads();   // (one barrier serves both scans)
+    double off0 = 0.0, off1 = 0.0;
+    if (scan0) off0 = scan_offset(wave_total[c & 1][0], excl0, carry0);
+    if constexpr (KIND == kGradNonTotal) {
+      if (scan1) off1 = scan_offset(wave_total[c & 1][1], excl1, carry1);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (t0 + j >= T) continue;
+      double out = scan0 ? off0 + b[j] : 0.0;
+      if (scan1) {
+        const double sq = (off1 + q[j]) * exp_factor(en, a.aux_tab, t_plus, t0 + j);
+        out = scan0 ? out + sq : sq;
+      }
+      av[t0 + j] = out;
+    }
   }
 }
 
-hipError_t launch_grad_input(const GradArgs &a, hipStream_t st) {
-  if (a.N <= 0 || a.D <= 0 || a.T <= 0) return hipSuccess;
-  const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
-  if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(grad_input_kernel, dim3((unsigned)(a.N * a.D), (unsigned)tiles), dim3(256), 0, st, a);
-  return hipGetLastError();
+hipError_t launch_grad_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st) {
+  switch (kind) {
+    case kGradReals: return launch_per_depth(grad_suffix_kernel<kGradReals>, a, first, count, st);
+    case kGradTotal: return launch_per_depth(grad_suffix_kernel<kGradTotal>, a, first, count, st);
+    case kGradNonTotal: return launch_per_depth(grad_suffix_kernel<kGradNonTotal>, a, first, count, st);
+    default: return hipErrorInvalidValue;
+  }
 }
 
-// ------------------------------------------------------------------ the max semirings
-// Arctic (max, +) and Bayesian (max, x), fruits/iss/semiring.py:282-309 and :461-493: per node
-//     z_v = m_v (x) S_p (no shift; m_v alone at depth 1),   S_v = running maximum of z_v
-// with m_v[t] = sum_d e_vd x_d[t] (Arctic) or prod_d x_d[t]^e_vd (Bayesian).  A HEAD of v is a
-// time s with s == 0 or S_v[s] > S_v[s-1] - strictly, the first of equal maxima wins - and opens
-// the segment [s, next head): S_v[t] = z_v[s] for every t of it.  The adjoint, leaves to root:
-//     B_v[t] = G_v[t] + sum over children c of w_c[t] A_c[t]      (w_c = 1 Arctic, m_c[t] Bayesian)
-//     A_v[s] = sum of B_v over the segment of s at a head s, 0.0 elsewhere
-//     Arctic: dX_d[s] = sum_v e_vd A_v[s];   Bayesian: dX_d[s] = sum_v A_v[s] S_p[s] dm_v/dx_d[s]
-//
-// grad_max_suffix_kernel has the launch shape, the chunks and the reversed lane-to-time map of
-// grad_suffix_kernel; its scan is SEGMENTED.  Walking time downwards, what crosses from t + 1 to
-// t is the open sum carry(t + 1) = head(t + 1) ? 0 : R[t + 1] with R[t] = B[t] + carry(t + 1),
-// and A[t] = head(t) ? R[t] : 0.  A run of time steps [lo, hi] acts on the carry that enters it
-// from the right as  c -> f ? o : o + c  with f = "a head in the run" and o = the sum of B from
-// lo up to the run's first head (the whole run without one); a run `a` to the right of a run `b`
-// compose as  (o_a, f_a) o (o_b, f_b) = (f_b ? o_b : o_a + o_b, f_a | f_b).  So a segment's sum is
-// only ever formed from that segment's B - never as a difference of two suffix sums - and every
-// partial sum joins disjoint runs of one segment.  The flags of the 64 lanes are one ballot: a
-// lane decides each step of the wave scan with a bit test, only the sums travel by DPP.  Across
-// waves and chunks the carry is the value c alone (a pair applied to it gives a value).
+// ------------------------------------------------------------------ the carried sums of a weighted plan
+// (one kernel for both bodies: they carry the same sums)
+__global__ __launch_bounds__(256) void grad_prefix_kernel(GradArgs a, int first) {
+  __shared__ double wave_total[2][4];
+  const int64_t n = blockIdx.x;
+  const int v = as_const(a.inner_nodes)[first + (int)blockIdx.y];
+  const int64_t N = a.N, T = a.T;
+  const double *__restrict__ xn = a.X + n * a.D * T;
+  const double *__restrict__ en = a.aux + n * a.aux_n;
+  const int fb = as_const(a.fac_begin)[v], fe = as_const(a.fac_begin)[v + 1];
+  const int ps = as_const(a.parent_srow)[v];
+  const int t_plus = as_const(a.tab)[3 * v], t_pminus = as_const(a.tab)[3 * v + 2];
+  const double *__restrict__ cp = ps >= 0 ? a.C + ((int64_t)ps * N + n) * T : nullptr;
+  double *__restrict__ cv = a.C + ((int64_t)as_const(a.self_srow)[v] * N + n) * T;
 
+  double carry = 0.0;   // sum of y_v over the chunks to the left
+  const int64_t chunks = grad_chunks(T);
+  for (int64_t c = 0; c < chunks; ++c) {
+    const int64_t t0 = forward_t0(c);
+    double y[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t t = t0 + j;
+      if (t >= T) continue;
+      double val = letter_value(a, xn, fb, fe, t, -1);
+      if (ps >= 0) val = t > 0 ? val * cp[t - 1] * exp_factor(en, a.aux_tab, t_pminus, t) : 0.0;
+      y[j] = val * exp_factor(en, a.aux_tab, t_plus, t);
+    }
+    // the lane's own prefix sums (steps past T hold exact zeros), then the lanes from the left
+    y[1] += y[0];
+    y[2] += y[1];
+    y[3] += y[2];
+    const double excl = scan_publish(y[3], wave_total[c & 1]);
+    __syncthreads();
+    const double off = scan_offset(wave_total[c & 1], excl, carry);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (t0 + j < T) cv[t0 + j] = off + y[j];
+  }
+}
+
+hipError_t launch_grad_prefix(const GradArgs &a, int kind, int first, int count, hipStream_t st) {
+  if (!grad_weighted(kind)) return hipErrorInvalidValue;
+  return launch_per_depth(grad_prefix_kernel, a, first, count, st);
+}
+
+// ------------------------------------------------------------------ the segmented suffix scans
 // One step of the wave scan: the open sum of the lanes to the right (0.0 where the lane has no
 // source) joins unless the lanes this one covers so far hold a head.
 template <int CTRL, int ROW_MASK>
@@ -208,7 +343,8 @@ __device__ __forceinline__ double wave_segmented_scan(double o, unsigned long lo
   return o;
 }
 
-template <int SEMI>
+// KIND: kGradArctic or kGradBayesian.
+template <int KIND>
 __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int first) {
   __shared__ double wave_total[2][4];
   __shared__ int wave_head[2][4];
@@ -224,9 +360,8 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
   const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
 
   double carry = 0.0;   // the open sum that enters the chunk from the right
-  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
-  for (int64_t c = chunks - 1; c >= 0; --c) {
-    const int64_t t0 = c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
+  for (int64_t c = grad_chunks(T) - 1; c >= 0; --c) {
+    const int64_t t0 = reversed_t0(c);
     // the heads, read off the recomputed S_v alone (steps past T hold none)
     double s[5];
 #pragma unroll
@@ -235,16 +370,11 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
 #pragma unroll
     for (int j = 0; j < 4; ++j) h[j] = t0 + j < T && (t0 + j == 0 || s[j + 1] > s[j]);
     double b[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int g = gb; g < ge; ++g) {
-      const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (t0 + j < T) b[j] += gk[(t0 + j) * a.g_t];
-    }
+    gather_upstream(a, gn, gb, ge, t0, b);
     for (int ci = cb; ci < ce; ++ci) {
       const int ch = as_const(a.child)[ci];
       const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
-      if constexpr (SEMI == kSemiArctic) {
+      if constexpr (KIND == kGradArctic) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (t0 + j < T) b[j] += ac[t0 + j];
@@ -270,7 +400,6 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
       wave_total[c & 1][wave] = incl;
       wave_head[c & 1][wave] = heads != 0;
     }
-    // (two buffers, as in grad_suffix_kernel)
     __syncthreads();
     double run = carry, off = carry;
 #pragma unroll
@@ -290,36 +419,55 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
   }
 }
 
-hipError_t launch_grad_max_suffix(const GradArgs &a, int semiring, int first, int count, hipStream_t st) {
-  if (semiring != kSemiArctic && semiring != kSemiBayesian) return hipErrorInvalidValue;
-  if (a.N <= 0 || a.T <= 0 || count <= 0) return hipSuccess;
-  if (a.N > 0x7fffffffLL) return hipErrorInvalidValue;
-  for (int done = 0; done < count; done += 65535) {
-    const int part = count - done < 65535 ? count - done : 65535;
-    const dim3 grid((unsigned)a.N, (unsigned)part);
-    if (semiring == kSemiArctic)
-      hipLaunchKernelGGL(grad_max_suffix_kernel<kSemiArctic>, grid, dim3(256), 0, st, a, first + done);
-    else
-      hipLaunchKernelGGL(grad_max_suffix_kernel<kSemiBayesian>, grid, dim3(256), 0, st, a, first + done);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+hipError_t launch_grad_max_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st) {
+  switch (kind) {
+    case kGradArctic: return launch_per_depth(grad_max_suffix_kernel<kGradArctic>, a, first, count, st);
+    case kGradBayesian: return launch_per_depth(grad_max_suffix_kernel<kGradBayesian>, a, first, count, st);
+    default: return hipErrorInvalidValue;
   }
-  return hipSuccess;
 }
 
-template <int SEMI>
-__global__ __launch_bounds__(256) void grad_max_input_kernel(GradArgs a) {
+// ------------------------------------------------------------------ the input kernel
+constexpr int kGradTile = 1024;   // time steps of a workgroup of grad_input_kernel (4 per lane, strided)
+
+// dm_v[t]: A_v times what the node's letter multiplies in the forward pass.
+template <int KIND>
+__device__ __forceinline__ double input_dm(const GradArgs &a, const double *__restrict__ en, int v,
+                                           int64_t n, int64_t t) {
+  const int64_t N = a.N, T = a.T;
+  const int ps = as_const(a.parent_srow)[v];
+  double dm = a.A[((int64_t)v * N + n) * T + t];
+  if constexpr (KIND == kGradReals) {
+    // A_v * shift(S_p); shift(S)[0] = 0
+    if (ps >= 0) dm *= t > 0 ? a.S[((int64_t)ps * N + n) * T + t - 1] : 0.0;
+  } else if constexpr (KIND == kGradBayesian) {
+    // A_v * S_p at the SAME step (no shift between the letters of a max semiring)
+    if (ps >= 0) dm *= a.S[((int64_t)ps * N + n) * T + t];
+  } else {
+    // total: A_v E-_p E+_v shift(C_p); non-total: A_v E-_p shift(C_p); shift(C)[0] = 0
+    if (ps >= 0)
+      dm = t > 0 ? dm * exp_factor(en, a.aux_tab, as_const(a.tab)[3 * v + 2], t) *
+                       a.C[((int64_t)ps * N + n) * T + t - 1]
+                 : 0.0;
+    if constexpr (KIND == kGradTotal) dm *= exp_factor(en, a.aux_tab, as_const(a.tab)[3 * v], t);
+  }
+  return dm;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void grad_input_kernel(GradArgs a) {
   const int64_t row = blockIdx.x;   // (series, dimension)
   const int64_t N = a.N, D = a.D, T = a.T;
   const int64_t n = row / D, d = row - n * D;
   const double *__restrict__ xn = a.X + n * D * T;
+  const double *__restrict__ en = grad_weighted(KIND) ? a.aux + n * a.aux_n : nullptr;
   const int ib = as_const(a.dim_begin)[d], ie = as_const(a.dim_begin)[d + 1];
 #pragma unroll
   for (int e = 0; e < kGradTile / 256; ++e) {
     const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
     if (t >= T) continue;
     double acc = 0.0;
-    if constexpr (SEMI == kSemiArctic) {
+    if constexpr (KIND == kGradArctic) {
       // the letter is linear: its coefficient times A_v
       for (int i = ib; i < ie; ++i) {
         const int v = as_const(a.dim_item)[2 * i];
@@ -331,294 +479,29 @@ __global__ __launch_bounds__(256) void grad_max_input_kernel(GradArgs a) {
       for (int i = ib; i < ie; ++i) {
         const int v = as_const(a.dim_item)[2 * i];
         const int f = as_const(a.dim_item)[2 * i + 1];
-        const int ps = as_const(a.parent_srow)[v];
-        // dm_v = A_v * S_p at the SAME step (no shift between the letters of a max semiring)
-        double dm = a.A[((int64_t)v * N + n) * T + t];
-        if (ps >= 0) dm *= a.S[((int64_t)ps * N + n) * T + t];
-        const int ex = as_const(a.fac)[2 * f + 1];
-        const double dpow = ex > 0 ? (double)ex * ipow(x, ex - 1) : (double)ex * (1.0 / ipow(x, 1 - ex));
+        const double dm = input_dm<KIND>(a, en, v, n, t);
         const double others = letter_value(a, xn, as_const(a.fac_begin)[v], as_const(a.fac_begin)[v + 1], t, f);
-        acc += dm * (dpow * others);
+        acc += dm * (dpow(x, as_const(a.fac)[2 * f + 1]) * others);
       }
     }
     a.dX[row * T + t] = acc;
   }
 }
 
-hipError_t launch_grad_max_input(const GradArgs &a, int semiring, hipStream_t st) {
-  if (semiring != kSemiArctic && semiring != kSemiBayesian) return hipErrorInvalidValue;
+hipError_t launch_grad_input(const GradArgs &a, int kind, hipStream_t st) {
+  void (*kernel)(GradArgs) = nullptr;
+  switch (kind) {
+    case kGradReals: kernel = grad_input_kernel<kGradReals>; break;
+    case kGradTotal: kernel = grad_input_kernel<kGradTotal>; break;
+    case kGradNonTotal: kernel = grad_input_kernel<kGradNonTotal>; break;
+    case kGradArctic: kernel = grad_input_kernel<kGradArctic>; break;
+    case kGradBayesian: kernel = grad_input_kernel<kGradBayesian>; break;
+    default: return hipErrorInvalidValue;
+  }
   if (a.N <= 0 || a.D <= 0 || a.T <= 0) return hipSuccess;
   const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
   if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(a.N * a.D), (unsigned)tiles);
-  if (semiring == kSemiArctic)
-    hipLaunchKernelGGL(grad_max_input_kernel<kSemiArctic>, grid, dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(grad_max_input_kernel<kSemiBayesian>, grid, dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------------ weighted Reals plans
-// Both weighted bodies of fruits/iss/semiring.py:98-158 carry the same sums from letter to letter
-// (E+_v = exp(g alpha_v), E-_v = exp(-g alpha_v) of the node's last letter):
-//     y_v[t] = m_v[t] E-_p[t] E+_v[t] C_p[t-1]   (depth 1: m_v[t] E+_v[t]),   C_v = cumsum(y_v)
-// and differ in what a node emits: S_v = C_v E-_v (total) or S_v = cumsum(z_v), y_v = z_v E+_v
-// (non-total).  The adjoint, leaves to root, children c reading C_v[s] at time s + 1:
-//     total:      B_v[s] = G_v[s] E-_v[s] + sum_c m_c[s+1] E-_v[s+1] E+_c[s+1] A_c[s+1]
-//                 A_v = suffix(B_v);                          dm_v = A_v E-_p E+_v shift(C_p)
-//     non-total:  Q_v[s] = sum_c m_c[s+1] E-_v[s+1] A_c[s+1]
-//                 A_v = suffix(G_v) + E+_v suffix(Q_v);       dm_v = A_v E-_p shift(C_p)
-// Nothing is divided by an exp factor.  The forward walk of a non-total plan emits S, not C, so
-// grad_w_prefix_kernel forms C of the nodes that have children; the exp tables are read from
-// global memory (launch_exp_tables filled them on the same stream).
-
-// Table `tb` (-1: none, the factor 1.0) of the series whose tables start at `aux_n` at time t.
-__device__ __forceinline__ double exp_factor(const double *__restrict__ aux_n, int64_t aux_tab, int tb,
-                                             int64_t t) {
-  return tb < 0 ? 1.0 : aux_n[(int64_t)tb * aux_tab + t];
-}
-
-// (one kernel for both bodies: they carry the same sums)
-__global__ __launch_bounds__(256) void grad_w_prefix_kernel(GradWArgs w, int first) {
-  __shared__ double wave_total[2][4];
-  const GradArgs &a = w.g;
-  const int64_t n = blockIdx.x;
-  const int v = as_const(w.inner_nodes)[first + (int)blockIdx.y];
-  const int64_t N = a.N, T = a.T;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double *__restrict__ xn = a.X + n * a.D * T;
-  const double *__restrict__ en = w.aux + n * w.aux_n;
-  const int fb = as_const(a.fac_begin)[v], fe = as_const(a.fac_begin)[v + 1];
-  const int ps = as_const(a.parent_srow)[v];
-  const int t_plus = as_const(w.tab)[3 * v], t_pminus = as_const(w.tab)[3 * v + 2];
-  const double *__restrict__ cp = ps >= 0 ? w.C + ((int64_t)ps * N + n) * T : nullptr;
-  double *__restrict__ cv = w.C + ((int64_t)as_const(a.self_srow)[v] * N + n) * T;
-
-  double carry = 0.0;   // sum of y_v over the chunks to the left
-  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
-  for (int64_t c = 0; c < chunks; ++c) {
-    const int64_t t0 = c * kGradChunk + 4 * (int64_t)threadIdx.x;
-    double y[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int64_t t = t0 + j;
-      if (t >= T) continue;
-      double val = letter_value(a, xn, fb, fe, t, -1);
-      if (ps >= 0) val = t > 0 ? val * cp[t - 1] * exp_factor(en, w.aux_tab, t_pminus, t) : 0.0;
-      y[j] = val * exp_factor(en, w.aux_tab, t_plus, t);
-    }
-    // the lane's own prefix sums (steps past T hold exact zeros), then the lanes from the left
-    y[1] += y[0];
-    y[2] += y[1];
-    y[3] += y[2];
-    const double incl = wave_inclusive_scan<0>(y[3]);
-    const double excl = wave_shift_right1<0>(incl);
-    if (lane == 63) wave_total[c & 1][wave] = incl;
-    // (two buffers, as in grad_suffix_kernel)
-    __syncthreads();
-    double run = carry, off = carry;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k == wave) off = run;
-      run += wave_total[c & 1][k];
-    }
-    carry = run;
-    off += excl;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (t0 + j < T) cv[t0 + j] = off + y[j];
-  }
-}
-
-hipError_t launch_grad_w_prefix(const GradWArgs &w, int first, int count, hipStream_t st) {
-  if (w.g.N <= 0 || w.g.T <= 0 || count <= 0) return hipSuccess;
-  if (w.g.N > 0x7fffffffLL) return hipErrorInvalidValue;
-  for (int done = 0; done < count; done += 65535) {
-    const int part = count - done < 65535 ? count - done : 65535;
-    hipLaunchKernelGGL(grad_w_prefix_kernel, dim3((unsigned)w.g.N, (unsigned)part), dim3(256), 0, st, w,
-                       first + done);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// The launch shape, the chunks and the reversed lane-to-time map of grad_suffix_kernel.  Total: one
-// scan over B_v.  Non-total: the suffix sums of G_v and of Q_v are two scans with two carries,
-// joined as suffix(G) + E+ suffix(Q); a scan whose operand is empty - a node that is no output
-// row, a node without children - is skipped (block-uniform branches).
-template <bool TOTAL>
-__global__ __launch_bounds__(256) void grad_w_suffix_kernel(GradWArgs w, int first) {
-  __shared__ double wave_total[2][2][4];
-  const GradArgs &a = w.g;
-  const int64_t n = blockIdx.x;
-  const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
-  const int64_t N = a.N, T = a.T;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double *__restrict__ xn = a.X + n * a.D * T;
-  const double *__restrict__ gn = a.G + n * a.g_n;
-  const double *__restrict__ en = w.aux + n * w.aux_n;
-  double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
-  const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
-  const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
-  const int t_plus = as_const(w.tab)[3 * v], t_minus = as_const(w.tab)[3 * v + 1];
-  const bool has_g = ge > gb, has_c = ce > cb;
-  // which sums are scanned: total - B alone (slot 0); non-total - G (slot 0) and Q (slot 1)
-  const bool scan0 = TOTAL ? (has_g || has_c) : has_g;
-  const bool scan1 = !TOTAL && has_c;
-
-  double carry0 = 0.0, carry1 = 0.0;   // the sums over the chunks to the right
-  const int64_t chunks = (T + kGradChunk - 1) / kGradChunk;
-  for (int64_t c = chunks - 1; c >= 0; --c) {
-    const int64_t t0 = c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
-    double b[4] = {0.0, 0.0, 0.0, 0.0};   // total: B_v; non-total: G_v
-    double q[4] = {0.0, 0.0, 0.0, 0.0};   // non-total: Q_v
-    for (int g = gb; g < ge; ++g) {
-      const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (t0 + j < T) b[j] += gk[(t0 + j) * a.g_t];
-    }
-    if (TOTAL && has_g) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (t0 + j < T) b[j] *= exp_factor(en, w.aux_tab, t_minus, t0 + j);
-    }
-    for (int ci = cb; ci < ce; ++ci) {
-      const int ch = as_const(a.child)[ci];
-      const int fb = as_const(a.fac_begin)[ch], fe = as_const(a.fac_begin)[ch + 1];
-      const int c_plus = as_const(w.tab)[3 * ch];
-      const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t s = t0 + j + 1;
-        if (s >= T) continue;
-        double term = letter_value(a, xn, fb, fe, s, -1) * exp_factor(en, w.aux_tab, t_minus, s);
-        if constexpr (TOTAL) {
-          term *= exp_factor(en, w.aux_tab, c_plus, s);
-          b[j] += term * ac[s];
-        } else {
-          q[j] += term * ac[s];
-        }
-      }
-    }
-    // the lane's own suffix sums (steps past T hold exact zeros), then the lanes from the right
-    double excl0 = 0.0, excl1 = 0.0;
-    if (scan0) {
-      b[2] += b[3];
-      b[1] += b[2];
-      b[0] += b[1];
-      const double incl = wave_inclusive_scan<0>(b[0]);
-      excl0 = wave_shift_right1<0>(incl);
-      if (lane == 63) wave_total[c & 1][0][wave] = incl;
-    }
-    if (scan1) {
-      q[2] += q[3];
-      q[1] += q[2];
-      q[0] += q[1];
-      const double incl = wave_inclusive_scan<0>(q[0]);
-      excl1 = wave_shift_right1<0>(incl);
-      if (lane == 63) wave_total[c & 1][1][wave] = incl;
-    }
-    // (two buffers, as in grad_suffix_kernel; one barrier serves both scans)
-    __syncthreads();
-    double off0 = 0.0, off1 = 0.0;
-    if (scan0) {
-      double run = carry0;
-      off0 = carry0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (k == wave) off0 = run;
-        run += wave_total[c & 1][0][k];
-      }
-      carry0 = run;
-      off0 += excl0;
-    }
-    if (scan1) {
-      double run = carry1;
-      off1 = carry1;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        if (k == wave) off1 = run;
-        run += wave_total[c & 1][1][k];
-      }
-      carry1 = run;
-      off1 += excl1;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (t0 + j >= T) continue;
-      double out = scan0 ? off0 + b[j] : 0.0;
-      if (scan1) {
-        const double sq = (off1 + q[j]) * exp_factor(en, w.aux_tab, t_plus, t0 + j);
-        out = scan0 ? out + sq : sq;
-      }
-      av[t0 + j] = out;
-    }
-  }
-}
-
-hipError_t launch_grad_w_suffix(const GradWArgs &w, bool total, int first, int count, hipStream_t st) {
-  if (w.g.N <= 0 || w.g.T <= 0 || count <= 0) return hipSuccess;
-  if (w.g.N > 0x7fffffffLL) return hipErrorInvalidValue;
-  for (int done = 0; done < count; done += 65535) {
-    const int part = count - done < 65535 ? count - done : 65535;
-    const dim3 grid((unsigned)w.g.N, (unsigned)part);
-    if (total)
-      hipLaunchKernelGGL(grad_w_suffix_kernel<true>, grid, dim3(256), 0, st, w, first + done);
-    else
-      hipLaunchKernelGGL(grad_w_suffix_kernel<false>, grid, dim3(256), 0, st, w, first + done);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <bool TOTAL>
-__global__ __launch_bounds__(256) void grad_w_input_kernel(GradWArgs w) {
-  const GradArgs &a = w.g;
-  const int64_t row = blockIdx.x;   // (series, dimension)
-  const int64_t N = a.N, D = a.D, T = a.T;
-  const int64_t n = row / D, d = row - n * D;
-  const double *__restrict__ xn = a.X + n * D * T;
-  const double *__restrict__ en = w.aux + n * w.aux_n;
-  const int ib = as_const(a.dim_begin)[d], ie = as_const(a.dim_begin)[d + 1];
-#pragma unroll
-  for (int e = 0; e < kGradTile / 256; ++e) {
-    const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
-    if (t >= T) continue;
-    const double x = xn[d * T + t];
-    double acc = 0.0;
-    for (int i = ib; i < ie; ++i) {
-      const int v = as_const(a.dim_item)[2 * i];
-      const int f = as_const(a.dim_item)[2 * i + 1];
-      const int ps = as_const(a.parent_srow)[v];
-      // total: dm_v = A_v E-_p E+_v shift(C_p); non-total: dm_v = A_v E-_p shift(C_p); shift(C)[0] = 0
-      double dm = a.A[((int64_t)v * N + n) * T + t];
-      if (ps >= 0)
-        dm = t > 0 ? dm * exp_factor(en, w.aux_tab, as_const(w.tab)[3 * v + 2], t) *
-                         w.C[((int64_t)ps * N + n) * T + t - 1]
-                   : 0.0;
-      if constexpr (TOTAL) dm *= exp_factor(en, w.aux_tab, as_const(w.tab)[3 * v], t);
-      const int ex = as_const(a.fac)[2 * f + 1];
-      const double dpow = ex > 0 ? (double)ex * ipow(x, ex - 1) : (double)ex * (1.0 / ipow(x, 1 - ex));
-      const double others = letter_value(a, xn, as_const(a.fac_begin)[v], as_const(a.fac_begin)[v + 1], t, f);
-      acc += dm * (dpow * others);
-    }
-    a.dX[row * T + t] = acc;
-  }
-}
-
-hipError_t launch_grad_w_input(const GradWArgs &w, bool total, hipStream_t st) {
-  const GradArgs &a = w.g;
-  if (a.N <= 0 || a.D <= 0 || a.T <= 0) return hipSuccess;
-  const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
-  if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
-  const dim3 grid((unsigned)(a.N * a.D), (unsigned)tiles);
-  if (total)
-    hipLaunchKernelGGL(grad_w_input_kernel<true>, grid, dim3(256), 0, st, w);
-  else
-    hipLaunchKernelGGL(grad_w_input_kernel<false>, grid, dim3(256), 0, st, w);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(a.N * a.D), (unsigned)tiles), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

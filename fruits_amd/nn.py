@@ -49,6 +49,14 @@ def backward_calls() -> int:
     return _calls["backward"]
 
 
+def _check_words(op: ISS) -> None:
+    """The tail every configuration check shares."""
+    op._check_supported()
+    if op._has_generic:
+        raise NotImplementedError(
+            "generic words have no backward pass: only words of SimpleWord letters have")
+
+
 def _check_config(op: ISS) -> None:
     """The refusals that depend on the configuration alone: raised before any launch."""
     if isinstance(op, CosWISS):
@@ -60,10 +68,50 @@ def _check_config(op: ISS) -> None:
     if not isinstance(op.semiring, Reals):
         raise NotImplementedError(
             f"the semiring {type(op.semiring).__name__} has no backward pass: only Reals has")
-    op._check_supported()
-    if op._has_generic:
+    _check_words(op)
+
+
+def _check_max_config(op: ISS) -> None:
+    """``_check_config`` for ``max_iss``: raised before any launch."""
+    if isinstance(op, CosWISS):
+        raise NotImplementedError("CosWISS has no backward pass: only the unweighted ISS has")
+    if isinstance(op.semiring, Reals):
         raise NotImplementedError(
-            "generic words have no backward pass: only words of SimpleWord letters have")
+            "max_iss differentiates the max semirings Arctic and Bayesian: the Reals iterated "
+            "sums are nn.iss / nn.ISSLayer")
+    if not isinstance(op.semiring, (Arctic, Bayesian)):
+        raise NotImplementedError(
+            f"the semiring {type(op.semiring).__name__} has no backward pass: only Reals, Arctic "
+            "and Bayesian have")
+    if op._argmax:
+        raise NotImplementedError(
+            "Arctic(argmax=True) has no backward pass: its position rows are piecewise constant "
+            "- differentiate Arctic() instead")
+    if op.weighting is not None:
+        raise NotImplementedError(
+            f"a weighting ({type(op.weighting).__name__}) has no backward pass yet: only the "
+            "unweighted ISS has")
+    _check_words(op)
+
+
+def _check_weighted_config(op: ISS) -> None:
+    """``_check_config`` for ``weighted_iss``: raised before any launch."""
+    if isinstance(op, CosWISS):
+        raise NotImplementedError("CosWISS has no backward pass: only the trie walk's ISS has")
+    if op.weighting is None:
+        raise NotImplementedError(
+            "weighted_iss differentiates a weighted ISS: the unweighted iterated sums are "
+            "nn.iss / nn.ISSLayer")
+    if not op.weighting._supports_lengths():
+        raise NotImplementedError(
+            f"the lookup of the weighting {type(op.weighting).__name__} depends on the input, and "
+            "the gradient would have to flow through it too: only weightings whose lookup is a "
+            "function of the time step alone (Indices, Plateaus) have a backward pass")
+    if not isinstance(op.semiring, Reals):
+        raise NotImplementedError(
+            f"the semiring {type(op.semiring).__name__} has no weighted backward pass: only "
+            "Reals has")
+    _check_words(op)
 
 
 def _check_input(op: ISS, X) -> None:
@@ -88,35 +136,56 @@ def _prefix_program(op: ISS):
     """(plan, row_prefix): the plan whose words are the distinct prefixes of the words, each with
     depth 1 (row j = the iterated sum of prefix j; the construction CosWISS._program uses for
     its terms), and per output row of ``op`` the prefix it is the iterated sum of.  Kept with
-    the ISS's other device programs."""
-    key = ("grad", op.mode)
+    the ISS's other device programs.
+
+    A weighted ISS: the distinct (letters, alphas) prefixes, each with its slice of the alphas -
+    two words with the same letters and other alphas are other nodes, as in the plan compiler's
+    trie - and per output row the prefix with the alphas of the word that emits the row."""
+    weighted = op.weighting is not None
+    if weighted:
+        wmode = nat.FR_W_TOTAL if op.weighting.total else nat.FR_W_NONTOTAL
+        # (found by what the program is a function of besides the letters, as ISS._plan_indices does)
+        key = ("grad_weighted", op.mode, wmode,
+               tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in op.words))
+    else:
+        key = ("grad", op.mode)
     prog = op._plans.get(key)
     if prog is not None:
         return prog
-    index, tables, row_prefix = {}, [], []
+    index, tables, alphas, row_prefix = {}, [], [], []
     for i, word in enumerate(op.words):
         depth = op._depth(i)
         if depth == 0:
             continue          # (every prefix was output by an earlier word: no rows, no work)
         tab = np.asarray(word.table(), dtype=np.int32)
+        alpha = np.asarray(word.alpha, dtype=np.float32) if weighted else None
         L = tab.shape[0]
         ident = ()
         for k in range(L):
-            # (a prefix is its letters; a letter its exponents without trailing zeros, as the
-            # plan compiler compares them)
-            ident += (tuple(np.trim_zeros(tab[k], "b").tolist()),)
+            # (a prefix is its letters - a letter its exponents without trailing zeros, as the
+            # plan compiler compares them - and, weighted, the bits of their alphas)
+            letter = tuple(np.trim_zeros(tab[k], "b").tolist())
+            ident += ((letter, alpha[k].tobytes()) if weighted else letter,)
             if ident not in index:
                 index[ident] = len(tables)
                 tables.append(tab[:k + 1])
+                if weighted:
+                    alphas.append(alpha[:k + 1])
             if L - k <= depth:
                 row_prefix.append(index[ident])
-    plan = nat.Plan(tables, [1] * len(tables), None, nat.FR_W_NONE,
-                    arctic=isinstance(op.semiring, Arctic), bayesian=isinstance(op.semiring, Bayesian))
+    if weighted:
+        plan = nat.Plan(tables, [1] * len(tables), alphas, wmode)
+    else:
+        plan = nat.Plan(tables, [1] * len(tables), None, nat.FR_W_NONE,
+                        arctic=isinstance(op.semiring, Arctic), bayesian=isinstance(op.semiring, Bayesian))
     if plan.nodes != len(tables):
         raise NotImplementedError("the prefix trie of these words is too deep for the walk's "
                                   "register frames: no backward pass")
     prog = op._plans[key] = (plan, np.asarray(row_prefix, dtype=np.int32))
     return prog
+
+
+_weighted_prefix_program = _prefix_program      # (the name the weighted sums' callers know it by)
 
 
 class _ISSFunction(torch.autograd.Function):
@@ -132,57 +201,52 @@ class _ISSFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, G):
         Xc, = ctx.saved_tensors
-        plan, row_prefix = _prefix_program(ctx.op)
+        op = ctx.op
+        plan, row_prefix = _prefix_program(op)
         with torch.cuda.device(Xc.device):
+            if op.weighting is not None:
+                # (the lookup is a function of T alone: formed again, not kept; the prefix plan
+                # itself never runs - the entry forms the carried sums - so it need not fit the LDS)
+                lookup = op.lookup_device(Xc)
+                _calls["backward"] += 1
+                return nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix), None
             S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
             _calls["backward"] += 1
             # (a max semiring: the rises of the recomputed running maxima are the segments' heads)
-            entry = nat.iss_backward if isinstance(ctx.op.semiring, Reals) else nat.iss_backward_max
+            entry = nat.iss_backward if isinstance(op.semiring, Reals) else nat.iss_backward_max
             return entry(plan, Xc, S, G, row_prefix), None
 
 
 def _apply(op: ISS, X):
     _check_input(op, X)
-    if len(op.words) > 0 and not _prefix_program(op)[0].fits(int(X.shape[2])):
+    # (an unweighted backward pass runs the prefix plan: it has to fit a workgroup's LDS)
+    if op.weighting is None and len(op.words) > 0 and not _prefix_program(op)[0].fits(int(X.shape[2])):
         raise NotImplementedError("the words name more input dimensions than a workgroup stages")
     with torch.cuda.device(X.device):
         return _ISSFunction.apply(X, op)
 
 
-def iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, weighting=None):
-    """Iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the row order of
-    ``ISS(words, mode).transform(X)`` and with its bits; differentiable with respect to ``X``.
-    ``words`` may also be an ``ISS`` that carries the configuration."""
-    if isinstance(words, ISS):
-        op = words
-    else:
-        words = list(words)
-        # the plain case keeps its device programs between calls (a training loop calls this every
-        # step): the last few word lists, found by their strings
-        key = None
-        if semiring is None and weighting is None and all(isinstance(w, SimpleWord) for w in words):
-            # (a plan's tables live on one device)
-            key = (tuple(str(w) for w in words), mode, str(getattr(X, "device", None)))
-        op = _OPS.get(key) if key is not None else None
-        if op is None:
-            op = ISS(words, mode=mode, semiring=semiring, weighting=weighting)
-            if key is not None:
-                if len(_OPS) >= _OPS_KEPT:
-                    _OPS.pop(next(iter(_OPS)))
-                _OPS[key] = op
-    _check_config(op)
-    return _apply(op, X)
+def _cached_op(key, make) -> ISS:
+    """The functional forms keep their device programs between calls (a training loop calls them
+    every step): the ISS of the last few plain configurations, found by ``key`` (None: not kept)."""
+    op = _OPS.get(key) if key is not None else None
+    if op is None:
+        op = make()
+        if key is not None:
+            if len(_OPS) >= _OPS_KEPT:
+                _OPS.pop(next(iter(_OPS)))
+            _OPS[key] = op
+    return op
 
 
-class ISSLayer(torch.nn.Module):
-    """``iss`` as a module without parameters; keeps its device programs between calls."""
+class _Layer(torch.nn.Module):
+    """What the three layers share: a module without parameters around one ISS (``check``: its
+    configuration check), which keeps its device programs between calls."""
 
-    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, semiring=None,
-                 weighting=None) -> None:
+    def __init__(self, op: ISS, check) -> None:
         super().__init__()
-        self.op = words if isinstance(words, ISS) else ISS(list(words), mode=mode,
-                                                          semiring=semiring, weighting=weighting)
-        _check_config(self.op)
+        self.op = op
+        check(op)
 
     @property
     def words(self):
@@ -199,33 +263,34 @@ class ISSLayer(torch.nn.Module):
         return f"{len(self.op.words)} words, {self.op.mode.name}"
 
 
+# ----------------------------------------------------------------------- Reals, unweighted
+def iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, weighting=None):
+    """Iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the row order of
+    ``ISS(words, mode).transform(X)`` and with its bits; differentiable with respect to ``X``.
+    ``words`` may also be an ``ISS`` that carries the configuration."""
+    if isinstance(words, ISS):
+        op = words
+    else:
+        words = list(words)
+        key = None
+        if semiring is None and weighting is None and all(isinstance(w, SimpleWord) for w in words):
+            # (found by the words' strings; a plan's tables live on one device)
+            key = (tuple(str(w) for w in words), mode, str(getattr(X, "device", None)))
+        op = _cached_op(key, lambda: ISS(words, mode=mode, semiring=semiring, weighting=weighting))
+    _check_config(op)
+    return _apply(op, X)
+
+
+class ISSLayer(_Layer):
+    """``iss`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, semiring=None,
+                 weighting=None) -> None:
+        super().__init__(words if isinstance(words, ISS) else
+                         ISS(list(words), mode=mode, semiring=semiring, weighting=weighting), _check_config)
+
+
 # ----------------------------------------------------------------------- the max semirings
-def _check_max_config(op: ISS) -> None:
-    """``_check_config`` for ``max_iss``: raised before any launch."""
-    if isinstance(op, CosWISS):
-        raise NotImplementedError("CosWISS has no backward pass: only the unweighted ISS has")
-    if isinstance(op.semiring, Reals):
-        raise NotImplementedError(
-            "max_iss differentiates the max semirings Arctic and Bayesian: the Reals iterated "
-            "sums are nn.iss / nn.ISSLayer")
-    if not isinstance(op.semiring, (Arctic, Bayesian)):
-        raise NotImplementedError(
-            f"the semiring {type(op.semiring).__name__} has no backward pass: only Reals, Arctic "
-            "and Bayesian have")
-    if op._argmax:
-        raise NotImplementedError(
-            "Arctic(argmax=True) has no backward pass: its position rows are piecewise constant "
-            "- differentiate Arctic() instead")
-    if op.weighting is not None:
-        raise NotImplementedError(
-            f"a weighting ({type(op.weighting).__name__}) has no backward pass yet: only the "
-            "unweighted ISS has")
-    op._check_supported()
-    if op._has_generic:
-        raise NotImplementedError(
-            "generic words have no backward pass: only words of SimpleWord letters have")
-
-
 def _max_op(words, mode, semiring) -> ISS:
     if isinstance(words, ISS):
         if semiring is not None and type(semiring) is not type(words.semiring):
@@ -250,7 +315,7 @@ def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
     is a valid subgradient at a tie.  For Bayesian this holds on positive inputs; where ``X`` has
     negative values the reference's recursion (a running maximum per letter) is not the maximum
     over index tuples, and the gradient is that of the recursion as the reference defines it."""
-    op = key = None
+    key = None
     if not isinstance(words, ISS):
         words = list(words)
         # (kept between calls like nn.iss keeps its plain case; an argmax Arctic is refused below)
@@ -258,133 +323,26 @@ def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
         if plain and all(isinstance(w, SimpleWord) for w in words):
             key = ("max", type(semiring).__name__, tuple(str(w) for w in words), mode,
                    str(getattr(X, "device", None)))
-            op = _OPS.get(key)
-    if op is None:
-        op = _max_op(words, mode, semiring)
-        if key is not None:
-            if len(_OPS) >= _OPS_KEPT:
-                _OPS.pop(next(iter(_OPS)))
-            _OPS[key] = op
+    op = _cached_op(key, lambda: _max_op(words, mode, semiring))
     _check_max_config(op)
     return _apply(op, X)
 
 
-class MaxISSLayer(torch.nn.Module):
+class MaxISSLayer(_Layer):
     """``max_iss`` as a module without parameters; keeps its device programs between calls."""
 
     def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, semiring=None) -> None:
-        super().__init__()
-        self.op = _max_op(words, mode, semiring)
-        _check_max_config(self.op)
-
-    @property
-    def words(self):
-        return self.op.words
-
-    @property
-    def mode(self) -> ISSMode:
-        return self.op.mode
+        super().__init__(_max_op(words, mode, semiring), _check_max_config)
 
     @property
     def semiring(self):
         return self.op.semiring
 
-    def forward(self, X):
-        return _apply(self.op, X)
-
     def extra_repr(self) -> str:
-        return f"{len(self.op.words)} words, {self.op.mode.name}, {type(self.op.semiring).__name__}"
+        return f"{super().extra_repr()}, {type(self.op.semiring).__name__}"
 
 
 # ----------------------------------------------------------------------- weighted Reals
-def _check_weighted_config(op: ISS) -> None:
-    """``_check_config`` for ``weighted_iss``: raised before any launch."""
-    if isinstance(op, CosWISS):
-        raise NotImplementedError("CosWISS has no backward pass: only the trie walk's ISS has")
-    if op.weighting is None:
-        raise NotImplementedError(
-            "weighted_iss differentiates a weighted ISS: the unweighted iterated sums are "
-            "nn.iss / nn.ISSLayer")
-    if not op.weighting._supports_lengths():
-        raise NotImplementedError(
-            f"the lookup of the weighting {type(op.weighting).__name__} depends on the input, and "
-            "the gradient would have to flow through it too: only weightings whose lookup is a "
-            "function of the time step alone (Indices, Plateaus) have a backward pass")
-    if not isinstance(op.semiring, Reals):
-        raise NotImplementedError(
-            f"the semiring {type(op.semiring).__name__} has no weighted backward pass: only "
-            "Reals has")
-    op._check_supported()
-    if op._has_generic:
-        raise NotImplementedError(
-            "generic words have no backward pass: only words of SimpleWord letters have")
-
-
-def _weighted_prefix_program(op: ISS):
-    """``_prefix_program`` of a weighted ISS: the distinct (letters, alphas) prefixes as words of
-    depth 1, each with its slice of the alphas - two words with the same letters and other
-    alphas are other nodes, as in the plan compiler's trie - and per output row of ``op`` the
-    prefix, with the alphas of the word that emits the row."""
-    wmode = nat.FR_W_TOTAL if op.weighting.total else nat.FR_W_NONTOTAL
-    # (found by what the program is a function of besides the letters, as ISS._plan_indices does)
-    key = ("grad_weighted", op.mode, wmode,
-           tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in op.words))
-    prog = op._plans.get(key)
-    if prog is not None:
-        return prog
-    index, tables, alphas, row_prefix = {}, [], [], []
-    for i, word in enumerate(op.words):
-        depth = op._depth(i)
-        if depth == 0:
-            continue
-        tab = np.asarray(word.table(), dtype=np.int32)
-        alpha = np.asarray(word.alpha, dtype=np.float32)
-        L = tab.shape[0]
-        ident = ()
-        for k in range(L):
-            ident += ((tuple(np.trim_zeros(tab[k], "b").tolist()), alpha[k].tobytes()),)
-            if ident not in index:
-                index[ident] = len(tables)
-                tables.append(tab[:k + 1])
-                alphas.append(alpha[:k + 1])
-            if L - k <= depth:
-                row_prefix.append(index[ident])
-    plan = nat.Plan(tables, [1] * len(tables), alphas, wmode)
-    if plan.nodes != len(tables):
-        raise NotImplementedError("the prefix trie of these words is too deep for the walk's "
-                                  "register frames: no backward pass")
-    prog = op._plans[key] = (plan, np.asarray(row_prefix, dtype=np.int32))
-    return prog
-
-
-class _WeightedISSFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, X, op):
-        Xc = X.contiguous()
-        Y = op.transform_device(Xc)          # (K, N, T)
-        ctx.op = op
-        ctx.save_for_backward(Xc)
-        return Y.permute(1, 0, 2)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, G):
-        Xc, = ctx.saved_tensors
-        plan, row_prefix = _weighted_prefix_program(ctx.op)
-        with torch.cuda.device(Xc.device):
-            # (the lookup is a function of T alone: formed again, not kept; the prefix plan
-            # itself never runs - the entry forms the carried sums - so it need not fit the LDS)
-            lookup = ctx.op.lookup_device(Xc)
-            _calls["backward"] += 1
-            return nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix), None
-
-
-def _apply_weighted(op: ISS, X):
-    _check_input(op, X)
-    with torch.cuda.device(X.device):
-        return _WeightedISSFunction.apply(X, op)
-
-
 def _weighted_op(words, mode, weighting) -> ISS:
     if isinstance(words, ISS):
         if weighting is not None and weighting is not words.weighting:
@@ -403,7 +361,7 @@ def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
     The backward pass is ``fr_iss_backward_weighted``: it forms the sums the
     forward pass carries from letter to letter with a prefix scan per inner trie node, then the
     adjoint with suffix scans, the exp factors ``exp(+-g alpha)`` as constants."""
-    op = key = None
+    key = None
     if not isinstance(words, ISS):
         words = list(words)
         # (kept between calls like nn.iss keeps its plain case; the ISS holds the weighting, so
@@ -412,40 +370,21 @@ def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
             key = ("weighted", id(weighting), tuple(str(w) for w in words),
                    tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in words), mode,
                    str(getattr(X, "device", None)))
-            op = _OPS.get(key)
-    if op is None:
-        op = _weighted_op(words, mode, weighting)
-        if key is not None:
-            if len(_OPS) >= _OPS_KEPT:
-                _OPS.pop(next(iter(_OPS)))
-            _OPS[key] = op
+    op = _cached_op(key, lambda: _weighted_op(words, mode, weighting))
     _check_weighted_config(op)
-    return _apply_weighted(op, X)
+    return _apply(op, X)
 
 
-class WeightedISSLayer(torch.nn.Module):
+class WeightedISSLayer(_Layer):
     """``weighted_iss`` as a module without parameters; keeps its device programs between calls."""
 
     def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, weighting=None) -> None:
-        super().__init__()
-        self.op = _weighted_op(words, mode, weighting)
-        _check_weighted_config(self.op)
-
-    @property
-    def words(self):
-        return self.op.words
-
-    @property
-    def mode(self) -> ISSMode:
-        return self.op.mode
+        super().__init__(_weighted_op(words, mode, weighting), _check_weighted_config)
 
     @property
     def weighting(self):
         return self.op.weighting
 
-    def forward(self, X):
-        return _apply_weighted(self.op, X)
-
     def extra_repr(self) -> str:
-        return (f"{len(self.op.words)} words, {self.op.mode.name}, "
+        return (f"{super().extra_repr()}, "
                 f"{type(self.op.weighting).__name__}{' total' if self.op.weighting.total else ''}")

@@ -362,3 +362,22 @@ def test_reals_backward_keeps_its_bits(env):
     nn.iss(Xd, words_of(fr, WORDS), fr.ISSMode.EXTENDED).backward(torch.from_numpy(G).cuda())
     assert gold["dX"].shape == (N, 3, CHUNK + 6) and (gold["dX"] != 0).sum() > 9000
     np.testing.assert_array_equal(Xd.grad.cpu().numpy(), gold["dX"])
+
+
+@pytest.mark.parametrize("semiring", gm.SEMIRINGS)
+def test_max_backward_keeps_its_bits(env, semiring):
+    """The segmented adjoints share their chunk frame, their gather and their input kernel with
+    the additive ones: the gradient on a real-valued two-chunk case is, bit for bit, what the
+    library computed before they were shared (tests/golden/grad_<semiring>_before_shared_frame.npz,
+    written on an MI355X by tools/grad_golden.py on the commit before).  A trend keeps the running
+    maxima rising: more than a thousand entries are heads."""
+    gold = np.load(os.path.join(HERE, "golden", f"grad_{semiring.lower()}_before_shared_frame.npz"))
+    rng = np.random.default_rng([12, semiring == "Arctic"])
+    if semiring == "Arctic":
+        X = rng.standard_normal((N, 3, CHUNK + 6)) + 0.02 * np.arange(CHUNK + 6)
+    else:
+        X = 1 + 0.25 * rng.random((N, 3, CHUNK + 6)) + 0.001 * np.arange(CHUNK + 6)
+    G = rng.standard_normal((N, len(gr.output_prefixes(WORDS, "EXTENDED")), CHUNK + 6))
+    got, _ = device_grad(env, X, G, WORDS, "EXTENDED", semiring)
+    assert gold["dX"].shape == (N, 3, CHUNK + 6) and (gold["dX"] != 0).sum() > 1000
+    np.testing.assert_array_equal(got, gold["dX"])

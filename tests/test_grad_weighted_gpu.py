@@ -3,6 +3,7 @@ fr_iss_backward_weighted): the forward bits, the gradient against the long-doubl
 adjoint recursion - exactly where every exp factor is 1.0, within the derived rounding bound with
 real weights - repeatability, the autograd wiring, a word list whose forward pass splits."""
 import copy
+import os
 import pickle
 
 import numpy as np
@@ -433,3 +434,24 @@ def test_entries_keep_to_their_plans(env):
     with pytest.raises(ValueError, match="fr_iss_backward_weighted: the plan is an unweighted Reals plan - "
                                               "its backward pass is fr_iss_backward"):
         nat.iss_backward_weighted(plan, X, weighted_op.lookup_device(X), G, rows)
+
+
+# ---------------------------------------------------------------- the weighted paths keep their bits
+@pytest.mark.parametrize("total", [False, True], ids=["nontotal", "total"])
+def test_weighted_backward_keeps_its_bits(env, total):
+    """The weighted adjoints share their scans, their gather and their input kernel with the
+    others: the gradient on a real-valued two-chunk case with real weights is, bit for bit, what
+    the library computed before they were shared
+    (tests/golden/grad_weighted_[non]total_before_shared_frame.npz, written on an MI355X by
+    tools/grad_golden.py on the commit before).  The gradient is dense."""
+    name = f"grad_weighted_{'total' if total else 'nontotal'}_before_shared_frame.npz"
+    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name))
+    N, D, T = 3, 3, CHUNK + 6
+    strings = ["[1][2][3]", "[11][2]", "[1][-2]", "[12][2][3][1]"]     # (WORDS of tests/test_grad_max_gpu.py)
+    alphas = drawn_alphas(strings, seed=12)
+    rng = np.random.default_rng(12)
+    X = rng.standard_normal((N, D, T))
+    G = rng.standard_normal((N, len(gw.output_nodes(strings, alphas, "EXTENDED")), T))
+    got, _, _ = device_grad(env, X, G, strings, alphas, "EXTENDED", ("Indices", {"total": total}))
+    assert gold["dX"].shape == (N, D, T) and (gold["dX"] != 0).sum() > 9000
+    np.testing.assert_array_equal(got, gold["dX"])
