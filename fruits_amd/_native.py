@@ -49,6 +49,7 @@ EXPORTS = [
     "fr_letter_rows", "fr_rows_unshift",
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
     "fr_iss_backward", "fr_iss_backward_max", "fr_iss_backward_weighted",
+    "fr_sieve_pick", "fr_iss_backward_picked",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -1246,4 +1247,79 @@ def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=N
         prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
         C.c_int64(rows), dptr(G), C.c_int64(K), sn, sk, st,
         _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
+    return dX
+
+
+# ----------------------------------------------------------------------- differentiable features
+def sieve_pick(Ad, spec, spec_d, cuts_d, q_d, F: int):
+    """fr_sieve_pick: the selecting sieves END / MAX / MIN over every row of the contiguous
+    ``(K, N, T)`` device tensor ``Ad`` in one launch.  ``spec`` ``(n_sieves, 6)`` int32 host
+    array ``{kind, cut_begin, C1, q_begin, Q1, feat_begin}`` per sieve (checked by the library),
+    ``spec_d`` its device copy, ``cuts_d`` int64 and ``q_d`` float64 the flat device tables the
+    spec indexes.  Returns ``(features (N, K, F) float64, positions (N, K, F) int32)``: of every
+    feature its value and the step of its row that it selects, -1 where it selects none."""
+    t = torch()
+    if Ad.dtype != t.float64 or Ad.dim() != 3 or not Ad.is_contiguous():
+        raise TypeError("A must be a contiguous float64 (K, N, T) device tensor")
+    K, N, T = (int(v) for v in Ad.shape)
+    sp = np.ascontiguousarray(spec, dtype=np.int32)
+    if sp.ndim != 2 or sp.shape[1] != 6:
+        raise ValueError("the spec table is (n_sieves, 6)")
+    if (spec_d.dtype != t.int32 or tuple(spec_d.shape) != sp.shape or not spec_d.is_contiguous()
+            or cuts_d.dtype != t.int64 or not cuts_d.is_contiguous()
+            or (q_d is not None and (q_d.dtype != t.float64 or not q_d.is_contiguous()))):
+        raise TypeError("the device tables must be contiguous: spec int32 like the host table, "
+                        "cuts int64, thresholds float64")
+    feat = t.empty((N, K, int(F)), dtype=t.float64, device=Ad.device)
+    pos = t.empty((N, K, int(F)), dtype=t.int32, device=Ad.device)
+    check(lib().fr_sieve_pick(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(spec_d),
+                              _i32p(sp), C.c_int32(sp.shape[0]), dptr(cuts_d),
+                              C.c_int64(int(cuts_d.numel())), dptr(q_d),
+                              C.c_int64(int(q_d.numel()) if q_d is not None else 0),
+                              C.c_int32(int(F)), dptr(feat), dptr(pos), stream_ptr()),
+          "fr_sieve_pick")
+    return feat, pos
+
+
+def iss_backward_picked(prefix_plan: Plan, Xd, pos_d, w_d, row_prefix, Sd=None, lookup_d=None):
+    """fr_iss_backward_picked: the gradient ``(N, D, T)`` of picked features of iterated sums
+    with respect to ``Xd`` - the adjoint the plan's kind names, with a sparse upstream.
+    ``pos_d`` ``(N, K, F)`` int32 and ``w_d`` ``(N, K, F)`` float64, contiguous: the weight
+    ``w_d[n, k, f]`` reaches step ``pos_d[n, k, f]`` of row k, nothing where that is negative.
+    ``Sd``: an unweighted plan's output on ``Xd`` ``(V, N, T)``; ``lookup_d``: a weighted plan's
+    ``(1 | N, T)`` lookup.  ``row_prefix`` as in ``iss_backward``."""
+    t = torch()
+    N, D, T = _rows3(Xd)
+    rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
+    K, V = int(rp.shape[0]), prefix_plan.rows
+    if (pos_d.dtype != t.int32 or pos_d.dim() != 3 or tuple(pos_d.shape[:2]) != (N, K)
+            or not pos_d.is_contiguous() or pos_d.device != Xd.device):
+        raise TypeError("the positions must be a contiguous int32 (N, K, F) tensor on the input's device")
+    F = int(pos_d.shape[2])
+    if (w_d.dtype != t.float64 or tuple(w_d.shape) != (N, K, F) or not w_d.is_contiguous()
+            or w_d.device != Xd.device):
+        raise TypeError("the weights must be a contiguous float64 (N, K, F) tensor on the input's device")
+    cells = V * N * T
+    dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
+    null = C.c_void_p(0)
+    if prefix_plan.weighting != FR_W_NONE:
+        if (lookup_d is None or lookup_d.dtype != t.float64 or lookup_d.dim() != 2
+                or int(lookup_d.shape[1]) != T or int(lookup_d.shape[0]) not in (1, N)
+                or not lookup_d.is_contiguous() or lookup_d.device != Xd.device):
+            raise TypeError("the lookup must be a contiguous float64 (1 | N, T) tensor on the input's device")
+        rows = int(lookup_d.shape[0])
+        aux = 2 * prefix_plan.info(FR_INFO_ALPHAS) * rows * T
+        work = _backward_scratch(None, 2 * cells + aux, "2 V N T + 2 alphas rows T", Xd)
+        # (the scratch in three parts; an empty part still gets a distinct address)
+        Cs, A, ax = (C.c_void_p(work.data_ptr() + 8 * o) for o in (0, cells, 2 * cells))
+        S, lk = null, dptr(lookup_d)
+    else:
+        if Sd is None or Sd.dtype != t.float64 or tuple(Sd.shape) != (V, N, T) or not Sd.is_contiguous():
+            raise TypeError("the prefix sums must be a contiguous float64 (V, N, T) device tensor")
+        work = _backward_scratch(None, cells, "V * N * T", Xd)
+        Cs, A, ax, S, lk, rows = null, dptr(work), null, dptr(Sd), null, 0
+    check(lib().fr_iss_backward_picked(
+        prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), S, lk, C.c_int64(rows),
+        dptr(pos_d), dptr(w_d), C.c_int64(K), C.c_int32(F), _i32p(rp), Cs, A, ax, dptr(dX),
+        stream_ptr()), "fr_iss_backward_picked")
     return dX

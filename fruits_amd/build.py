@@ -45,6 +45,8 @@ def units():
            ("kernels_letters", "kernels_letters.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
            # the backward pass: every product rounded, as the derived bound of its tests counts them
            ("kernels_grad", "kernels_grad.hip", ["-ffp-contract=off"]),
+           # the selecting sieves of the differentiable features: comparisons and moves alone
+           ("kernels_pick", "kernels_pick.hip", []),
            ("jit", "jit.cpp", []),
            # (the registry also holds the mixed kernels of the one-group programs and their
            # tail programs: no contraction, like the programs' own units below)

@@ -1,8 +1,9 @@
 // fr_iss_backward: the gradient of unweighted Reals iterated sums with respect to their input;
 // fr_iss_backward_max: the same for the max semirings Arctic and Bayesian;
-// fr_iss_backward_weighted: the same for weighted Reals plans, total or not.  The trie - parents,
-// children, letters, exp tables - is read off the plan the plan compiler built (plan.cpp); the
-// kernels are those of kernels_grad.hip.  One body (run_backward) serves the three entries.
+// fr_iss_backward_weighted: the same for weighted Reals plans, total or not;
+// fr_iss_backward_picked: any of the three with the sparse upstream of picked features.  The trie -
+// parents, children, letters, exp tables - is read off the plan the plan compiler built (plan.cpp);
+// the kernels are those of kernels_grad.hip.  One body (run_backward) serves the four entries.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -313,8 +314,9 @@ int ensure_tables(fr::Plan &p, const std::string &who, const int32_t *h_row_pref
   return FR_OK;
 }
 
-// What an entry brings besides the arguments all three share.  `S`: the prefix plan's output
-// (fr_iss_backward, fr_iss_backward_max); `lookup`, `C`, `aux`: fr_iss_backward_weighted's.
+// What an entry brings besides the arguments all share.  `S`: the prefix plan's output
+// (fr_iss_backward, fr_iss_backward_max); `lookup`, `C`, `aux`: fr_iss_backward_weighted's;
+// `picked`: the upstream is F pairs (`pos`, `w`) per row instead of d_G (fr_iss_backward_picked).
 enum class Entry { kReals, kMax, kWeighted };
 struct BackwardCall {
   const char *name;
@@ -323,6 +325,10 @@ struct BackwardCall {
   const double *lookup = nullptr;
   int64_t lookup_rows = 0;
   double *C = nullptr, *aux = nullptr;
+  bool picked = false;
+  const int32_t *pos = nullptr;
+  const double *w = nullptr;
+  int32_t F = 0;
 };
 
 // Why the entry does not take the plan, or nullptr (what a plan is never changes after its
@@ -352,7 +358,7 @@ const char *refused_plan(Entry entry, const fr::Plan &p) {
   return nullptr;
 }
 
-// The body of the three entries: the refusals in the entry's order, the tables, then - weighted -
+// The body of the entries: the refusals in the entry's order, the tables, then - weighted -
 // the exp tables and the carried sums root first, the adjoint leaves first, dX.
 int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D,
                  int64_t T, const double *d_G, int64_t K, int64_t g_n_stride, int64_t g_k_stride,
@@ -362,6 +368,10 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, who + ": null plan");
   if (N < 0 || D < 1 || T < 0 || K < 0 || g_n_stride < 0 || g_k_stride < 0 || g_t_stride < 0)
     return fail(FR_E_ARG, who + ": bad shape");
+  if (call.picked && call.F < 1) return fail(FR_E_ARG, who + ": a row needs at least one (position, weight) pair");
+  if (call.picked && call.F > fr::kPickMaxFeatures)
+    return fail(FR_E_LIMIT, who + ": at most 256 pairs per row, not " + std::to_string(call.F));
+  if (call.picked && T > 0x7fffffffLL) return fail(FR_E_LIMIT, who + ": positions are 32-bit, T is not");
   if (weighted && call.lookup_rows != 1 && call.lookup_rows != N)
     return fail(FR_E_ARG, who + ": the lookup has to have 1 or N rows, not " + std::to_string(call.lookup_rows));
   if (K > 0 && !h_row_prefix) return fail(FR_E_ARG, who + ": null host table");
@@ -376,7 +386,8 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   const int64_t V = (int64_t)p.nodes.size();
   if (N > 0 && T > 0) {
     const bool scratch = weighted ? call.C && d_A && call.aux : call.S && d_A;
-    if (!d_X || !d_dX || (weighted && !call.lookup) || (K > 0 && !d_G) || (V > 0 && !scratch))
+    const bool upstream = call.picked ? call.pos && call.w : d_G != nullptr;
+    if (!d_X || !d_dX || (weighted && !call.lookup) || (K > 0 && !upstream) || (V > 0 && !scratch))
       return fail(FR_E_ARG, who + ": null device pointer");
     if (d_X == d_dX) return fail(FR_E_ARG, who + ": the gradient must not alias the input");
     if (weighted && V > 0 && (call.C == d_A || call.aux == d_A || call.aux == call.C))
@@ -399,6 +410,12 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   a.X = d_X;
   a.S = call.S;
   a.G = d_G;
+  if (call.picked) {
+    // (the pairs of row (n, k) at (n * K + k) * F)
+    a.pos = call.pos;
+    a.w = call.w;
+    a.F = call.F;
+  }
   a.A = d_A;
   a.dX = d_dX;
   a.g_n = g_n_stride;
@@ -466,6 +483,38 @@ int fr_iss_backward_max(fr_plan_t *prefix_plan, const double *d_X, int64_t N, in
                         double *d_A, double *d_dX, void *stream) {
   return run_backward({"fr_iss_backward_max", Entry::kMax, d_S}, prefix_plan, d_X, N, D, T, d_G, K,
                       g_n_stride, g_k_stride, g_t_stride, h_row_prefix, d_A, d_dX, stream);
+}
+
+int fr_iss_backward_picked(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                           const double *d_S, const double *d_lookup, int64_t lookup_rows,
+                           const int32_t *d_pos, const double *d_w, int64_t K, int32_t F,
+                           const int32_t *h_row_prefix, double *d_C, double *d_A, double *d_aux,
+                           double *d_dX, void *stream) {
+  // the plan's kind names the adjoint, as the three dense entries name it themselves
+  BackwardCall call{"fr_iss_backward_picked", Entry::kReals};
+  if (prefix_plan && prefix_plan->p) {
+    const fr::Plan &p = *prefix_plan->p;
+    if (p.cos) return fail(FR_E_ARG, std::string(call.name) + ": a CosWISS plan has no backward pass");
+    if (p.weighting != 0)
+      call.entry = Entry::kWeighted;
+    else if (p.semiring != fr::kSemiReals)
+      call.entry = Entry::kMax;
+  }
+  if (call.entry == Entry::kWeighted) {
+    call.lookup = d_lookup;
+    call.lookup_rows = lookup_rows;
+    call.C = d_C;
+    call.aux = d_aux;
+  } else {
+    call.S = d_S;
+  }
+  call.picked = true;
+  call.pos = d_pos;
+  call.w = d_w;
+  call.F = F;
+  const int64_t row = F > 0 ? (int64_t)F : 0;   // (run_backward names a bad F itself)
+  return run_backward(call, prefix_plan, d_X, N, D, T, nullptr, K, K * row, row, 0, h_row_prefix, d_A,
+                      d_dX, stream);
 }
 
 }  // extern "C"

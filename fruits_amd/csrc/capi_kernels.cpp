@@ -409,4 +409,44 @@ int fr_rows_unshift(const double *d_A, int64_t K, int64_t N, int64_t T, const in
   return launched(e, "rows unshift launch", "fr_rows_unshift: grid too large");
 }
 
+int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_spec,
+                  const int32_t *h_spec, int32_t n_sieves, const int64_t *d_cuts, int64_t n_cuts,
+                  const double *d_q, int64_t n_q, int32_t F, double *d_feat, int32_t *d_pos,
+                  void *stream) {
+  const std::string who = "fr_sieve_pick";
+  if (K < 0 || N < 0 || T < 1 || n_sieves < 1 || n_cuts < 0 || n_q < 0 || F < 1)
+    return fail(FR_E_ARG, who + ": bad shape");
+  if (F > fr::kPickMaxFeatures)
+    return fail(FR_E_LIMIT, who + ": at most 256 features per row, not " + std::to_string(F));
+  if (T > 0x7fffffffLL) return fail(FR_E_LIMIT, who + ": positions are 32-bit, T is not");
+  if (!h_spec) return fail(FR_E_ARG, who + ": null host table");
+  // every entry of the table, before a kernel reads the device copy
+  int64_t features = 0;
+  for (int32_t s = 0; s < n_sieves; ++s) {
+    const int32_t *sp = h_spec + 6 * (int64_t)s;
+    const std::string sieve = who + ": sieve " + std::to_string(s);
+    const int32_t kind = sp[0], cut_begin = sp[1], C1 = sp[2], q_begin = sp[3], Q1 = sp[4];
+    if (kind != FR_SIEVE_END && kind != FR_SIEVE_MAX && kind != FR_SIEVE_MIN)
+      return fail(FR_E_ARG, sieve + " is no selecting sieve (END, MAX, MIN): kind " + std::to_string(kind));
+    if (C1 < 2 || cut_begin < 0 || (int64_t)cut_begin + C1 > n_cuts)
+      return fail(FR_E_ARG, sieve + " has a cut row outside the cut table");
+    if (kind != FR_SIEVE_END && (Q1 < 2 || q_begin < 0 || (int64_t)q_begin + Q1 > n_q))
+      return fail(FR_E_ARG, sieve + " has thresholds outside the threshold table");
+    if (sp[5] != features)
+      return fail(FR_E_ARG, sieve + " begins at feature " + std::to_string(sp[5]) + ", not at " +
+                                std::to_string(features));
+    features += (int64_t)(C1 - 1) * (kind == FR_SIEVE_END ? 1 : Q1 - 1);
+    if (features > F) break;
+  }
+  if (features != F)
+    return fail(FR_E_ARG, who + ": the sieves have " + std::string(features > F ? "more than " : "") +
+                              std::to_string(features > F ? F : features) + " features, not F = " + std::to_string(F));
+  if (K == 0 || N == 0) return FR_OK;
+  if (!d_A || !d_spec || !d_cuts || !d_feat || !d_pos || (n_q > 0 && !d_q))
+    return fail(FR_E_ARG, who + ": null device pointer");
+  hipError_t e = fr::launch_sieve_pick(d_A, K, N, T, reinterpret_cast<const fr::PickSieve *>(d_spec), n_sieves,
+                                       d_cuts, d_q, F, d_feat, d_pos, (hipStream_t)stream);
+  return launched(e, "sieve pick launch", "fr_sieve_pick: grid too large (K * N)");
+}
+
 }  // extern "C"

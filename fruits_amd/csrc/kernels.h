@@ -132,6 +132,20 @@ hipError_t launch_letter_rows(const double *X, int64_t N, int64_t D, int64_t T, 
                               hipStream_t st);
 hipError_t launch_rows_unshift(const double *A, int64_t K, int64_t N, int64_t T,
                                const int32_t *shift, double *out, hipStream_t st);
+// The selecting sieves END / MAX / MIN over every row of a (K, N, T) buffer at once
+// (kernels_pick.hip): value and position of each feature.  One sieve of the spec table.
+struct PickSieve {
+  int32_t kind;         // FR_SIEVE_END, FR_SIEVE_MAX or FR_SIEVE_MIN
+  int32_t cut_begin;    // its sorted cut row with the leading 0: cuts[cut_begin ... cut_begin + C1)
+  int32_t C1;
+  int32_t q_begin;      // its sorted thresholds q[q_begin ... q_begin + Q1) (END: none, Q1 = 0)
+  int32_t Q1;
+  int32_t feat_begin;   // its first feature among the F of a row
+};
+// feat, pos: (N, K, F), row (k, n) of A at (n * K + k) * F; hipErrorInvalidValue: a grid limit
+hipError_t launch_sieve_pick(const double *A, int64_t K, int64_t N, int64_t T, const PickSieve *spec,
+                             int n_sieves, const int64_t *cuts, const double *q, int F, double *feat,
+                             int32_t *pos, hipStream_t st);
 // the backward pass of the trie walk (kernels_grad.hip): which adjoint, and the
 // tables of the prefix trie, all on the device.  Node v is the plan's node v (DFS preorder); CSR
 // tables have V + 1 (D + 1) offsets.
@@ -146,6 +160,12 @@ struct GradArgs {
   const double *X;      // (N, D, T)
   const double *S;      // (V, N, T): row r = the iterated sum of the prefix with output row r (unweighted kinds)
   const double *G;      // upstream gradient, element (n, k, t) at n * g_n + k * g_k + t * g_t
+  // ... or, with `pos` set, the SPARSE upstream of picked features: row (n, k)
+  // is F pairs, pair f at n * g_n + k * g_k + f of both tables (G is null and g_t unused): the
+  // weight w reaches step pos of the row, a pair with pos < 0 nothing
+  const int32_t *pos;   // (N, K, F) positions in [-1, T)
+  const double *w;      // (N, K, F) weights
+  int F;                // pairs per row, 1 ... kPickMaxFeatures
   double *A;            // (V, N, T) scratch: the suffix sums, by node
   double *dX;           // (N, D, T), every element written
   int64_t N, D, T;
@@ -167,9 +187,11 @@ struct GradArgs {
   const int32_t *tab;   // three tables per node: its own E+, its own E-, its parent's E- (-1: unused)
   const int32_t *inner_nodes;   // the nodes that have children, by rising depth
 };
+constexpr int kPickMaxFeatures = 256;   // features of a row of fr_sieve_pick, pairs of a row of the sparse upstream
 constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)
 // Every launcher: hipErrorInvalidValue for a kind that is not its own, or a grid limit.
 // A of `count` nodes of one depth, level_nodes[first ...]: their children's A must be complete.
+// The scan launchers take the sparse upstream when a.pos is set, the dense one otherwise.
 // Additive suffix sums (kGradReals, kGradTotal, kGradNonTotal) ...
 hipError_t launch_grad_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st);
 // ... and SEGMENTED ones between the heads of S_v, the gather without a shift (kGradArctic, kGradBayesian)

@@ -18,7 +18,9 @@
 //     order).  The slots are double-buffered by the chunk's parity: a wave that runs ahead writes
 //     the other buffer, and nobody reaches the chunk after that before every wave has passed this
 //     chunk's barrier.
-//   * gather_upstream adds the node's rows of G; the children's terms are the adjoint's own.
+//   * gather_upstream adds the node's rows of G - or gather_picked the pairs (position, weight) of
+//     a sparse upstream, a compile-time switch of the scan kernels -; the
+//     children's terms are the adjoint's own.
 //   * grad_input_kernel: one thread per element of dX, which adds the terms dm_v * d(letter)/dx of
 //     the nodes in the fixed order of the table (dim_item); the adjoints differ in dm_v alone.
 // Every sum has one association, whatever the grid: the result is the same bits from run to run.
@@ -162,6 +164,25 @@ __device__ __forceinline__ void gather_upstream(const GradArgs &a, const double 
   }
 }
 
+// The same from the SPARSE upstream of picked features: a row of the series
+// `n` is a.F pairs (position, weight), and a pair adds its weight to b[j] where its position is
+// the step t0 + j.  The order is fixed - the rows in g_row order, a row's pairs in column order,
+// each added in turn - and so are the bits.  A position < 0 (an empty band) matches no step.
+// n and the node are workgroup-uniform: the pairs are scalar loads, every lane sees every pair.
+__device__ __forceinline__ void gather_picked(const GradArgs &a, int64_t n, int gb, int ge, int64_t t0,
+                                              double (&b)[4]) {
+  for (int g = gb; g < ge; ++g) {
+    const int64_t at = n * a.g_n + (int64_t)as_const(a.g_row)[g] * a.g_k;
+    for (int f = 0; f < a.F; ++f) {
+      const int64_t p = as_const(a.pos)[at + f];
+      const double w = as_const(a.w)[at + f];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (p == t0 + j && t0 + j < a.T) b[j] += w;
+    }
+  }
+}
+
 // `count` workgroups per series, blockIdx.y < 65535 each launch: nodes [first, first + count) of
 // a per-depth table.
 template <typename Args>
@@ -180,7 +201,8 @@ hipError_t launch_per_depth(void (*kernel)(Args, int), const Args &a, int first,
 // ------------------------------------------------------------------ the additive suffix scans
 // KIND: kGradReals, kGradTotal or kGradNonTotal.  Slot 0 scans B_v (non-total: G_v), slot 1 - of
 // the non-total body alone - Q_v; the unweighted kernel has no exp factor and always scans.
-template <int KIND>
+// SPARSE: the upstream is the pairs of picked features (gather_picked), not G.
+template <int KIND, bool SPARSE>
 __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first) {
   constexpr bool WEIGHTED = grad_weighted(KIND), TOTAL = KIND == kGradTotal;
   __shared__ double wave_total[2][KIND == kGradNonTotal ? 2 : 1][4];
@@ -188,7 +210,7 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
   const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
   const int64_t N = a.N, T = a.T;
   const double *__restrict__ xn = a.X + n * a.D * T;
-  const double *__restrict__ gn = a.G + n * a.g_n;
+  const double *__restrict__ gn = SPARSE ? nullptr : a.G + n * a.g_n;
   const double *__restrict__ en = WEIGHTED ? a.aux + n * a.aux_n : nullptr;
   double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
   const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
@@ -207,7 +229,10 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
     const int64_t t0 = reversed_t0(c);
     double b[4] = {0.0, 0.0, 0.0, 0.0};   // B_v; non-total: G_v
     double q[4] = {0.0, 0.0, 0.0, 0.0};   // non-total: Q_v
-    gather_upstream(a, gn, gb, ge, t0, b);
+    if constexpr (SPARSE)
+      gather_picked(a, n, gb, ge, t0, b);
+    else
+      gather_upstream(a, gn, gb, ge, t0, b);
     if (TOTAL && has_g) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
@@ -263,11 +288,27 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
   }
 }
 
+// The form of the upstream a call brings: pairs when a.pos is set (1 <= F <= kPickMaxFeatures,
+// both tables there), G otherwise.
+static bool sparse_upstream(const GradArgs &a, bool &ok) {
+  ok = !a.pos || (a.w && a.F >= 1 && a.F <= kPickMaxFeatures);
+  return a.pos != nullptr;
+}
+
 hipError_t launch_grad_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st) {
+  bool ok;
+  const bool sparse = sparse_upstream(a, ok);
+  if (!ok) return hipErrorInvalidValue;
   switch (kind) {
-    case kGradReals: return launch_per_depth(grad_suffix_kernel<kGradReals>, a, first, count, st);
-    case kGradTotal: return launch_per_depth(grad_suffix_kernel<kGradTotal>, a, first, count, st);
-    case kGradNonTotal: return launch_per_depth(grad_suffix_kernel<kGradNonTotal>, a, first, count, st);
+    case kGradReals:
+      return sparse ? launch_per_depth(grad_suffix_kernel<kGradReals, true>, a, first, count, st)
+                    : launch_per_depth(grad_suffix_kernel<kGradReals, false>, a, first, count, st);
+    case kGradTotal:
+      return sparse ? launch_per_depth(grad_suffix_kernel<kGradTotal, true>, a, first, count, st)
+                    : launch_per_depth(grad_suffix_kernel<kGradTotal, false>, a, first, count, st);
+    case kGradNonTotal:
+      return sparse ? launch_per_depth(grad_suffix_kernel<kGradNonTotal, true>, a, first, count, st)
+                    : launch_per_depth(grad_suffix_kernel<kGradNonTotal, false>, a, first, count, st);
     default: return hipErrorInvalidValue;
   }
 }
@@ -343,8 +384,8 @@ __device__ __forceinline__ double wave_segmented_scan(double o, unsigned long lo
   return o;
 }
 
-// KIND: kGradArctic or kGradBayesian.
-template <int KIND>
+// KIND: kGradArctic or kGradBayesian; SPARSE as in grad_suffix_kernel.
+template <int KIND, bool SPARSE>
 __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int first) {
   __shared__ double wave_total[2][4];
   __shared__ int wave_head[2][4];
@@ -353,7 +394,7 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
   const int64_t N = a.N, T = a.T;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double *__restrict__ xn = a.X + n * a.D * T;
-  const double *__restrict__ gn = a.G + n * a.g_n;
+  const double *__restrict__ gn = SPARSE ? nullptr : a.G + n * a.g_n;
   const double *__restrict__ sv = a.S + ((int64_t)as_const(a.self_srow)[v] * N + n) * T;
   double *__restrict__ av = a.A + ((int64_t)v * N + n) * T;
   const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
@@ -370,7 +411,10 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
 #pragma unroll
     for (int j = 0; j < 4; ++j) h[j] = t0 + j < T && (t0 + j == 0 || s[j + 1] > s[j]);
     double b[4] = {0.0, 0.0, 0.0, 0.0};
-    gather_upstream(a, gn, gb, ge, t0, b);
+    if constexpr (SPARSE)
+      gather_picked(a, n, gb, ge, t0, b);
+    else
+      gather_upstream(a, gn, gb, ge, t0, b);
     for (int ci = cb; ci < ce; ++ci) {
       const int ch = as_const(a.child)[ci];
       const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
@@ -420,9 +464,16 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
 }
 
 hipError_t launch_grad_max_suffix(const GradArgs &a, int kind, int first, int count, hipStream_t st) {
+  bool ok;
+  const bool sparse = sparse_upstream(a, ok);
+  if (!ok) return hipErrorInvalidValue;
   switch (kind) {
-    case kGradArctic: return launch_per_depth(grad_max_suffix_kernel<kGradArctic>, a, first, count, st);
-    case kGradBayesian: return launch_per_depth(grad_max_suffix_kernel<kGradBayesian>, a, first, count, st);
+    case kGradArctic:
+      return sparse ? launch_per_depth(grad_max_suffix_kernel<kGradArctic, true>, a, first, count, st)
+                    : launch_per_depth(grad_max_suffix_kernel<kGradArctic, false>, a, first, count, st);
+    case kGradBayesian:
+      return sparse ? launch_per_depth(grad_max_suffix_kernel<kGradBayesian, true>, a, first, count, st)
+                    : launch_per_depth(grad_max_suffix_kernel<kGradBayesian, false>, a, first, count, st);
     default: return hipErrorInvalidValue;
   }
 }

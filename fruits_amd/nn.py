@@ -20,6 +20,13 @@ the weightings whose lookup does not depend on the input (``Indices``, ``Plateau
 backward pass forms the sums the forward pass carries from letter to letter itself, with a prefix
 scan per inner node of the trie, instead of a second walk (DESIGN.md 4.14.2,
 ``fr_iss_backward_weighted``).
+
+``iss_features(X, words, mode, sieves, semiring=..., weighting=...)`` and ``FeatureLayer`` return
+what a classifier is fed instead of the rows: the ``END`` / ``MAX`` / ``MIN`` features of every
+iterated sum, ``(N, K * F)`` in ``Fruit``'s column order, for any of the three configurations
+above.  Each such feature is one element of one row, so the backward pass is handed the position
+of that element and the feature's gradient - a sparse upstream (DESIGN.md 4.14.4,
+``fr_sieve_pick``, ``fr_iss_backward_picked``) - and no ``(N, K, T)`` tensor outlives the call.
 """
 from __future__ import annotations
 
@@ -34,9 +41,10 @@ from .iss.cos import CosWISS
 from .iss.iss import ISS, ISSMode
 from .iss.semiring import Arctic, Bayesian, Reals
 from .iss.words.word import SimpleWord
+from .sieving import END, MAX, MIN
 
 __all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "weighted_iss", "WeightedISSLayer",
-           "backward_calls"]
+           "iss_features", "FeatureLayer", "backward_calls"]
 
 _calls = {"backward": 0}
 _OPS: dict = {}      # the functional form's ISS objects by (word strings, mode, device), oldest first
@@ -45,7 +53,7 @@ _OPS_KEPT = 8
 
 def backward_calls() -> int:
     """Backward passes launched by this process so far (one ``fr_iss_backward``,
-    ``fr_iss_backward_max`` or ``fr_iss_backward_weighted`` each)."""
+    ``fr_iss_backward_max``, ``fr_iss_backward_weighted`` or ``fr_iss_backward_picked`` each)."""
     return _calls["backward"]
 
 
@@ -264,19 +272,23 @@ class _Layer(torch.nn.Module):
 
 
 # ----------------------------------------------------------------------- Reals, unweighted
+def _reals_op(X, words, mode, semiring, weighting) -> ISS:
+    """The ISS of an ``iss`` call: ``words`` itself if it is one, else kept between calls."""
+    if isinstance(words, ISS):
+        return words
+    words = list(words)
+    key = None
+    if X is not None and semiring is None and weighting is None and all(isinstance(w, SimpleWord) for w in words):
+        # (found by the words' strings; a plan's tables live on one device; no X: a layer's own)
+        key = (tuple(str(w) for w in words), mode, str(getattr(X, "device", None)))
+    return _cached_op(key, lambda: ISS(words, mode=mode, semiring=semiring, weighting=weighting))
+
+
 def iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, weighting=None):
     """Iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the row order of
     ``ISS(words, mode).transform(X)`` and with its bits; differentiable with respect to ``X``.
     ``words`` may also be an ``ISS`` that carries the configuration."""
-    if isinstance(words, ISS):
-        op = words
-    else:
-        words = list(words)
-        key = None
-        if semiring is None and weighting is None and all(isinstance(w, SimpleWord) for w in words):
-            # (found by the words' strings; a plan's tables live on one device)
-            key = (tuple(str(w) for w in words), mode, str(getattr(X, "device", None)))
-        op = _cached_op(key, lambda: ISS(words, mode=mode, semiring=semiring, weighting=weighting))
+    op = _reals_op(X, words, mode, semiring, weighting)
     _check_config(op)
     return _apply(op, X)
 
@@ -302,6 +314,19 @@ def _max_op(words, mode, semiring) -> ISS:
     return ISS(list(words), mode=mode, semiring=semiring)
 
 
+def _cached_max_op(X, words, mode, semiring) -> ISS:
+    """``_max_op``, kept between calls like ``nn.iss`` keeps its plain case."""
+    key = None
+    if not isinstance(words, ISS) and X is not None:
+        words = list(words)
+        # (an argmax Arctic is refused by the configuration check)
+        plain = type(semiring) is Bayesian or (type(semiring) is Arctic and not semiring._argmax)
+        if plain and all(isinstance(w, SimpleWord) for w in words):
+            key = ("max", type(semiring).__name__, tuple(str(w) for w in words), mode,
+                   str(getattr(X, "device", None)))
+    return _cached_op(key, lambda: _max_op(words, mode, semiring))
+
+
 def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
     """Arctic (max, +) or Bayesian (max, x) iterated sums ``(N, K, T)`` of the device tensor ``X``
     ``(N, D, T)``, in the row order of ``ISS(words, mode, semiring=semiring).transform(X)`` and
@@ -315,15 +340,7 @@ def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
     is a valid subgradient at a tie.  For Bayesian this holds on positive inputs; where ``X`` has
     negative values the reference's recursion (a running maximum per letter) is not the maximum
     over index tuples, and the gradient is that of the recursion as the reference defines it."""
-    key = None
-    if not isinstance(words, ISS):
-        words = list(words)
-        # (kept between calls like nn.iss keeps its plain case; an argmax Arctic is refused below)
-        plain = type(semiring) is Bayesian or (type(semiring) is Arctic and not semiring._argmax)
-        if plain and all(isinstance(w, SimpleWord) for w in words):
-            key = ("max", type(semiring).__name__, tuple(str(w) for w in words), mode,
-                   str(getattr(X, "device", None)))
-    op = _cached_op(key, lambda: _max_op(words, mode, semiring))
+    op = _cached_max_op(X, words, mode, semiring)
     _check_max_config(op)
     return _apply(op, X)
 
@@ -351,6 +368,19 @@ def _weighted_op(words, mode, weighting) -> ISS:
     return ISS(list(words), mode=mode, weighting=weighting)
 
 
+def _cached_weighted_op(X, words, mode, weighting) -> ISS:
+    """``_weighted_op``, kept between calls like ``nn.iss`` keeps its plain case."""
+    key = None
+    if not isinstance(words, ISS) and X is not None:
+        words = list(words)
+        # (the ISS holds the weighting, so its id names it for as long as the entry lives)
+        if weighting is not None and all(isinstance(w, SimpleWord) for w in words):
+            key = ("weighted", id(weighting), tuple(str(w) for w in words),
+                   tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in words), mode,
+                   str(getattr(X, "device", None)))
+    return _cached_op(key, lambda: _weighted_op(words, mode, weighting))
+
+
 def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
     """Weighted Reals iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the
     row order of ``ISS(words, mode, weighting=weighting).transform(X)`` and with its bits;
@@ -361,16 +391,7 @@ def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
     The backward pass is ``fr_iss_backward_weighted``: it forms the sums the
     forward pass carries from letter to letter with a prefix scan per inner trie node, then the
     adjoint with suffix scans, the exp factors ``exp(+-g alpha)`` as constants."""
-    key = None
-    if not isinstance(words, ISS):
-        words = list(words)
-        # (kept between calls like nn.iss keeps its plain case; the ISS holds the weighting, so
-        # its id names it for as long as the entry lives)
-        if weighting is not None and all(isinstance(w, SimpleWord) for w in words):
-            key = ("weighted", id(weighting), tuple(str(w) for w in words),
-                   tuple(np.asarray(w.alpha, dtype=np.float32).tobytes() for w in words), mode,
-                   str(getattr(X, "device", None)))
-    op = _cached_op(key, lambda: _weighted_op(words, mode, weighting))
+    op = _cached_weighted_op(X, words, mode, weighting)
     _check_weighted_config(op)
     return _apply(op, X)
 
@@ -388,3 +409,210 @@ class WeightedISSLayer(_Layer):
     def extra_repr(self) -> str:
         return (f"{super().extra_repr()}, "
                 f"{type(self.op.weighting).__name__}{' total' if self.op.weighting.total else ''}")
+
+
+# ----------------------------------------------------------------------- features of the rows
+_PICK_MAX_FEATURES = 256      # features of a row (csrc/kernels.h, kPickMaxFeatures)
+
+
+def _check_sieves(sieves) -> list:
+    """The refusals that depend on the sieves alone: raised before any launch.  What remains is
+    END, MAX and MIN with integer cuts - the sieves whose feature is ONE element of the row."""
+    from .sieving.abstract import FeatureSieve
+    if isinstance(sieves, FeatureSieve) or not isinstance(sieves, Sequence):
+        raise TypeError("sieves has to be a sequence of sieves")
+    sieves = list(sieves)
+    if not sieves:
+        raise ValueError("sieves has to name at least one sieve")
+    for sieve in sieves:
+        name = type(sieve).__name__
+        if not isinstance(sieve, FeatureSieve):
+            raise TypeError(f"sieves has to hold sieves, not {name}")
+        if name in ("INC", "INT"):
+            raise NotImplementedError(
+                f"the sieve {sieve} has no backward pass here: the wrappers INC / INT sieve "
+                "increments or sums of the row, not the row - only END, MAX and MIN themselves have")
+        if name in ("NPI", "XPI", "LPI", "PPV", "CPV"):
+            raise NotImplementedError(
+                f"the sieve {sieve} has no backward pass: {name} counts, and the gradient of a "
+                "count is zero almost everywhere")
+        if name in ("MPI", "CUR", "AVG", "STD"):
+            raise NotImplementedError(
+                f"the sieve {sieve} has no backward pass here: {name} is no selection of one "
+                "element of the row - only END, MAX and MIN have")
+        if type(sieve) not in (END, MAX, MIN):
+            raise NotImplementedError(
+                f"the sieve {sieve} has no backward pass: only END, MAX and MIN have")
+        if sieve._has_float_cuts():
+            raise NotImplementedError(
+                f"the sieve {sieve} has a float (coquantile) cut: its position depends on the "
+                "input's path length, which has no backward pass - only integer cuts have")
+    F = sum(sieve.nfeatures() for sieve in sieves)
+    if F > _PICK_MAX_FEATURES:
+        raise ValueError(f"the sieves have {F} features per iterated sum: at most "
+                         f"{_PICK_MAX_FEATURES} are picked in one launch")
+    return sieves
+
+
+def _thresholds(sieve) -> np.ndarray:
+    """The sieve's sorted value thresholds, constants of the adjoint: those of its q in
+    {-1, 0, 1}, or the fitted ones - what ``quantiles_device`` uploads."""
+    if not sieve.requires_fitting:
+        sieve._get_unfitted_quantiles()
+    elif getattr(sieve, "_quantiles", None) is None:
+        raise RuntimeError("Sieve has not been fitted properly")
+    return np.ascontiguousarray(sieve._quantiles, dtype=np.float64)
+
+
+class _Head:
+    """The sieves of an ``iss_features`` call and their device tables (fr_sieve_pick), kept by
+    what they are a function of: the length of the series, the thresholds, the device."""
+
+    def __init__(self, sieves) -> None:
+        self.sieves = _check_sieves(sieves)
+        self.F = sum(sieve.nfeatures() for sieve in self.sieves)
+        self._tables: dict = {}
+
+    def host_tables(self, T: int):
+        """(spec (n_sieves, 6) int32, cuts int64, thresholds float64) for series of T steps;
+        an END cut outside the series is the IndexError of ``END`` itself."""
+        spec, cuts, qs, feat = [], [], [], 0
+        for sieve in self.sieves:
+            row = sieve._int_cut_row(T)
+            q = np.zeros(0) if isinstance(sieve, END) else _thresholds(sieve)
+            spec.append([sieve._kind, sum(len(c) for c in cuts), len(row),
+                         sum(len(v) for v in qs), len(q), feat])
+            cuts.append(row)
+            qs.append(q)
+            feat += sieve.nfeatures()
+        return (np.asarray(spec, dtype=np.int32), np.concatenate(cuts).astype(np.int64),
+                np.concatenate(qs).astype(np.float64))
+
+    def tables(self, T: int, device):
+        spec, cuts, q = self.host_tables(T)
+        key = (T, str(device), q.tobytes())
+        hit = self._tables.get(key)
+        if hit is None:
+            if len(self._tables) >= _OPS_KEPT:
+                self._tables.pop(next(iter(self._tables)))
+            with torch.cuda.device(device):
+                hit = self._tables[key] = (spec, nat.to_device(spec, dtype=np.int32),
+                                           nat.to_device(cuts, dtype=np.int64),
+                                           nat.to_device(q) if len(q) else None)
+        return hit
+
+    def __getstate__(self):
+        return {"sieves": self.sieves, "F": self.F, "_tables": {}}
+
+
+class _FeatureFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, op, head):
+        Xc = X.contiguous()
+        N, T = int(Xc.shape[0]), int(Xc.shape[2])
+        spec, spec_d, cuts_d, q_d = head.tables(T, Xc.device)
+        Y = op.transform_device(Xc)          # (K, N, T): dies with this call
+        feat, pos = nat.sieve_pick(Y, spec, spec_d, cuts_d, q_d, head.F)
+        ctx.op = op
+        ctx.save_for_backward(Xc, pos)
+        return feat.view(N, -1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        Xc, pos = ctx.saved_tensors
+        op = ctx.op
+        plan, row_prefix = _prefix_program(op)
+        # (N, K * F), tiny: an expanded scalar or a slice is made contiguous, never dense in T
+        w = g.to(device=Xc.device, dtype=torch.float64).contiguous().view(pos.shape)
+        with torch.cuda.device(Xc.device):
+            if op.weighting is not None:
+                lookup = op.lookup_device(Xc)
+                _calls["backward"] += 1
+                return nat.iss_backward_picked(plan, Xc, pos, w, row_prefix, lookup_d=lookup), None, None
+            S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
+            _calls["backward"] += 1
+            return nat.iss_backward_picked(plan, Xc, pos, w, row_prefix, Sd=S), None, None
+
+
+def _feature_op(X, words, mode, semiring, weighting):
+    """(ISS, its configuration check) of an ``iss_features`` call: the configuration decides which
+    adjoint runs, exactly as ``iss``, ``max_iss`` and ``weighted_iss`` decide - a weighting: the
+    weighted adjoint; else Arctic or Bayesian: the max adjoint; else Reals."""
+    carried = words if isinstance(words, ISS) else None
+    if weighting is not None or (carried is not None and carried.weighting is not None):
+        if semiring is not None and not isinstance(semiring, Reals) and carried is None:
+            # (no such adjoint: the weighted check names the semiring)
+            return ISS(list(words), mode=mode, semiring=semiring, weighting=weighting), _check_weighted_config
+        return _cached_weighted_op(X, words, mode, weighting), _check_weighted_config
+    if carried is not None and semiring is None:
+        semiring = carried.semiring
+    if semiring is not None and not isinstance(semiring, Reals):
+        return _cached_max_op(X, words, mode, semiring), _check_max_config
+    return _reals_op(X, words, mode, semiring, None), _check_config
+
+
+def _apply_features(op: ISS, head: _Head, X, lengths=None):
+    if lengths is not None:
+        raise NotImplementedError("lengths= has no backward pass: the differentiable features "
+                                  "take series of one length")
+    for sieve in head.sieves:
+        if not isinstance(sieve, END):
+            _thresholds(sieve)           # (an unfitted sieve: before the input is looked at)
+    _check_input(op, X)
+    if op.weighting is None and len(op.words) > 0 and not _prefix_program(op)[0].fits(int(X.shape[2])):
+        raise NotImplementedError("the words name more input dimensions than a workgroup stages")
+    if int(X.shape[2]) < 1:
+        raise ValueError("the features of series without a time step are undefined")
+    with torch.cuda.device(X.device):
+        return _FeatureFunction.apply(X, op, head)
+
+
+def iss_features(X, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
+                 weighting=None, lengths=None):
+    """The selecting features ``(N, K * F)`` of the iterated sums of the device tensor ``X``
+    ``(N, D, T)``: what ``sieve.transform_device`` returns on each row of
+    ``ISS(words, mode, ...).transform_device(X)``, with its bits, in ``Fruit``'s column order -
+    iterated sum, then sieve, then the sieve's own (segment, band) order; differentiable with
+    respect to ``X``.
+
+    ``sieves``: ``END``, ``MAX`` and ``MIN`` of ``fruits_amd.sieving`` with integer cuts, with
+    thresholds q in {-1, 0, 1} or fitted already - the thresholds are constants of the adjoint.
+    ``semiring`` / ``weighting`` choose the iterated sums as ``iss`` (neither), ``max_iss``
+    (``Arctic()``, ``Bayesian()``) and ``weighted_iss`` (``Indices``, ``Plateaus``) take them.
+
+    A feature's gradient goes to the one element of its row that it selects: ``END`` the element
+    at ``cut - 1``, ``MAX`` / ``MIN`` the FIRST step of the segment that attains the extreme
+    inside the band ``q_k < v <= q_(k+1)`` (``np.argmax``'s rule, the tie rule of ``max_iss``).
+    An empty segment or band is the feature 0 and carries no gradient.  Only ``X`` and the
+    ``(N, K, F)`` int32 positions are kept for the backward pass, whose upstream is those
+    positions with the feature gradients."""
+    head = _Head(sieves)
+    op, check = _feature_op(X, words, mode, semiring, weighting)
+    check(op)
+    return _apply_features(op, head, X, lengths)
+
+
+class FeatureLayer(_Layer):
+    """``iss_features`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
+                 weighting=None, lengths=None) -> None:
+        if lengths is not None:
+            raise NotImplementedError("lengths= has no backward pass: the differentiable features "
+                                      "take series of one length")
+        head = _Head(sieves)
+        # (no X: the layer's ISS is its own, as every layer's)
+        op, check = _feature_op(None, words, mode, semiring, weighting)
+        super().__init__(op, check)
+        self.head = head
+
+    @property
+    def sieves(self):
+        return self.head.sieves
+
+    def forward(self, X):
+        return _apply_features(self.op, self.head, X)
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, {self.head.F} features per iterated sum"

@@ -765,6 +765,58 @@ int fr_iss_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t 
                              int64_t g_t_stride, const int32_t *h_row_prefix, double *d_C,
                              double *d_A, double *d_aux, double *d_dX, void *stream);
 
+/* ------------------------------------------------------------------ differentiable features
+ * fr_sieve_pick: the SELECTING sieves END, MAX and MIN (fruits/sieving/segment.py:107-225) over
+ * every row of a materialised (K, N, T) buffer of iterated sums in one launch: of each feature
+ * its value - the bits fr_sieve returns for that row - and the position of the element it
+ * selects, which is all a backward pass needs of it.  Not in the reference.
+ *
+ *   d_A      (K, N, T) f64, contiguous (the layout of fr_iss_run)
+ *   h_spec, d_spec  (n_sieves, 6) i32, the same table on the host (every entry is checked
+ *            there) and on the device: per sieve
+ *              {kind, cut_begin, C1, q_begin, Q1, feat_begin}
+ *            kind: FR_SIEVE_END, FR_SIEVE_MAX or FR_SIEVE_MIN; its cut row - sorted, leading 0,
+ *            as fr_sieve takes it - is d_cuts[cut_begin ... cut_begin + C1), C1 >= 2; its sorted
+ *            thresholds are d_q[q_begin ... q_begin + Q1), Q1 >= 2 (END: ignored); feat_begin:
+ *            its first feature among the F of a row - the sieves' features follow each other
+ *            without a gap, END has C1 - 1, MAX / MIN (C1 - 1) * (Q1 - 1) in (segment, band) order
+ *   d_cuts   (n_cuts) i64, d_q (n_q) f64: the cut rows and thresholds of all sieves
+ *   F        features of a row, 1 ... 256 (FR_E_LIMIT beyond)
+ *   d_feat   (N, K, F) f64 and d_pos (N, K, F) i32: feature f of row (k, n) at (n * K + k) * F + f
+ * END: the element at cut - 1, index -1 wrapping to T - 1; out of range: NaN and position -1.
+ * MAX / MIN: of the elements t of the segment [cut_j, cut_(j+1)) with q_k < v <= q_(k+1) the
+ * largest / smallest, and the FIRST t whose value equals it (np.argmax's rule; -0.0 equals +0.0);
+ * an empty segment or band: 0.0 and position -1.  FR_E_ARG for a bad table, on the host and before
+ * the launch. */
+int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_spec,
+                  const int32_t *h_spec, int32_t n_sieves, const int64_t *d_cuts, int64_t n_cuts,
+                  const double *d_q, int64_t n_q, int32_t F, double *d_feat, int32_t *d_pos,
+                  void *stream);
+
+/* fr_iss_backward_picked: the backward pass of fr_iss_backward, fr_iss_backward_max or
+ * fr_iss_backward_weighted - whichever the plan's kind names - with a SPARSE upstream gradient:
+ * row (n, k) of the differentiated rows has F pairs (position, weight), pair f at
+ * (n * K + k) * F + f of d_pos (i32) and d_w (f64), instead of T gradient values.  The weight
+ * reaches step `position` of the row; a pair with a position < 0 reaches nothing.  No dense
+ * (N, K, T) gradient exists anywhere.  What a node gathers is formed in a fixed order - its rows
+ * in the order of h_row_prefix, a row's pairs in the order f = 0 ... F - 1, each added in turn -
+ * so the result is the same bits from run to run and whatever the batch split, and the bits of
+ * the dense entry on the scattered gradient wherever those sums are exact.
+ *
+ *   prefix_plan   a prefix plan of any of the three entries; it decides which adjoint runs
+ *   d_S           (V, N, T): the plan's output on d_X - an unweighted plan's; else null
+ *   d_lookup, lookup_rows, d_C, d_aux   a weighted plan's, as fr_iss_backward_weighted takes
+ *                 them; else null / 0
+ *   d_pos, d_w, K, F   the pairs; 1 <= F <= 256 (FR_E_LIMIT beyond); positions < T
+ *   the rest      as in fr_iss_backward
+ * FR_E_ARG, on the host and before any launch, for what the plan's own entry refuses and for a
+ * null d_pos / d_w. */
+int fr_iss_backward_picked(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
+                           const double *d_S, const double *d_lookup, int64_t lookup_rows,
+                           const int32_t *d_pos, const double *d_w, int64_t K, int32_t F,
+                           const int32_t *h_row_prefix, double *d_C, double *d_A, double *d_aux,
+                           double *d_dX, void *stream);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest

@@ -9,7 +9,15 @@ warm-up round; the medians per call, the smallest and largest round of forward p
 the ratio of the medians as one JSON line.  With a max semiring, or with `--weighting` (the
 weighted Reals sums of `nn.WeightedISSLayer`, `Indices()` with the words' default alphas, total or
 not), the unweighted Reals pair (`nn.ISSLayer`) runs interleaved in the same rounds, for
-comparison."""
+comparison.
+
+`--features[=dense|picked]` measures a training step on FEATURES instead: the
+last value and the maximum of every iterated sum, forward plus backward with an `(N, 2 K)`
+upstream gradient.  `picked` is `nn.FeatureLayer` with `[END([-1]), MAX([-1])]`; `dense` is the
+same loss through the rows - `nn.ISSLayer`, then `Y[..., -1]` and `Y.amax(-1)` by torch - which
+needs nothing of this option's own code and so also runs on a tree without `nn.FeatureLayer`.
+Without a value both run interleaved.  The JSON line carries the medians, the smallest and largest
+round and `torch.cuda.max_memory_allocated()` of each route, measured over a step of its own."""
 import json
 import statistics
 import sys
@@ -19,8 +27,10 @@ from fruits_amd import _native as nat
 from fruits_amd import nn
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
-semiring, weighting = "reals", ""
+semiring, weighting, features = "reals", "", None
 for a in sys.argv[1:]:
+    if a == "--features" or a.startswith("--features="):
+        features = a.split("=", 1)[1].lower().split(",") if "=" in a else ["dense", "picked"]
     if a.startswith("--semiring="):
         semiring = a.split("=", 1)[1].lower()
     if a.startswith("--weighting="):
@@ -29,6 +39,8 @@ if semiring not in ("reals", "arctic", "bayesian"):
     sys.exit("--semiring: reals, arctic or bayesian")
 if weighting not in ("", "indices", "indices,total") or (weighting and semiring != "reals"):
     sys.exit("--weighting: indices or indices,total, with the Reals semiring")
+if features is not None and (semiring != "reals" or weighting or set(features) - {"dense", "picked"}):
+    sys.exit("--features: dense, picked or both, with the unweighted Reals semiring")
 reps = int(args[0]) if len(args) > 0 else 15
 launches = int(args[1]) if len(args) > 1 else 10
 t = nat.torch()
@@ -36,6 +48,67 @@ nat.require_device()
 N, D, T = 2048, 3, 1024
 words = fr.words.of_weight(2, dim=3)
 K = fr.ISS(words, mode=fr.ISSMode.EXTENDED).n_iterated_sums()
+
+
+def timed(fn):
+    a, b = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(launches):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / launches
+
+
+def feature_routes():
+    """{route: one training step on the 2 K features of a batch}"""
+    X = t.randn((N, D, T), dtype=t.float64, device="cuda").requires_grad_(True)
+    g = t.randn((N, 2 * K), dtype=t.float64, device="cuda")
+    rows = nn.ISSLayer(words, fr.ISSMode.EXTENDED)
+
+    def dense():
+        X.grad = None
+        Y = rows(X)                                                       # (N, K, T)
+        t.stack((Y[..., -1], Y.amax(-1)), dim=-1).reshape(N, 2 * K).backward(g)
+
+    routes = {"dense": dense}
+    if "picked" in features:
+        layer = nn.FeatureLayer(words, fr.ISSMode.EXTENDED, [fr.sieving.END([-1]), fr.sieving.MAX([-1])])
+
+        def picked():
+            X.grad = None
+            layer(X).backward(g)
+
+        routes["picked"] = picked
+    return {k: routes[k] for k in features}
+
+
+if features is not None:
+    routes = feature_routes()
+    times, peak = {k: [] for k in routes}, {}
+    for r in range(reps + 1):
+        for k, fn in routes.items():
+            ms = timed(fn)
+            if r:                      # (round 0 uploads the tables and warms everything up)
+                times[k].append(ms)
+    for k, fn in routes.items():
+        t.cuda.synchronize()
+        t.cuda.reset_peak_memory_stats()
+        base = t.cuda.memory_allocated()
+        fn()
+        t.cuda.synchronize()
+        peak[k] = [t.cuda.max_memory_allocated() - base, t.cuda.max_memory_allocated()]
+    out = {"shape": [N, D, T], "words": "of_weight(2, 3) EXTENDED", "rows": K, "reps": reps,
+           "launches": launches, "features": "END([-1]), MAX([-1])"}
+    for k in routes:
+        out.update({k + "_step_ms": round(statistics.median(times[k]), 4),
+                    k + "_step_minmax_ms": [round(min(times[k]), 4), round(max(times[k]), 4)],
+                    k + "_peak_bytes_above_start": peak[k][0], k + "_max_memory_allocated": peak[k][1]})
+    if len(routes) == 2:
+        out["picked_over_dense"] = round(out["picked_step_ms"] / out["dense_step_ms"], 3)
+    print(json.dumps(out))
+    sys.exit(0)
+
 G = t.randn((N, K, T), dtype=t.float64, device="cuda")
 
 
@@ -65,16 +138,6 @@ if weighting:
     fns = {"": pair(nn.WeightedISSLayer(words, fr.ISSMode.EXTENDED, weighting=w),
                     X.detach().clone().requires_grad_(True)),
            "reals_": fns[""]}
-
-
-def timed(fn):
-    a, b = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(launches):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / launches
 
 
 times = {(k, i): [] for k in fns for i in (0, 1)}
