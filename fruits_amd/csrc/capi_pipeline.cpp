@@ -363,12 +363,12 @@ void set_pipeline_jit_ops(fr_pipeline_t *pl, const std::vector<fr::FeatOp> &ops)
   pl->jit_ops.n_padded = pl->n_ops_padded;
   pl->jit_ops.full_chunks = pl->T % fr::walk_chunk_elems(pl->T) == 0;
   for (const PipeSieve &sv : pl->sieves) {   // (a slot pair per differencing order >= 3 and per
-    if (sv.kind == FR_SIEVE_END) continue;    // cumulation of a row: walk_fused.h, fop)
+    if (sv.kind == FR_SIEVE_END) continue;    // cumulation of a row: walk_device.h, fop)
     if (sv.inc > 2) pl->jit_ops.cps = std::max(pl->jit_ops.cps, 3 + 2 * (sv.inc - 2));
     if (sv.inc < 0) pl->jit_ops.cps = std::max(pl->jit_ops.cps, 15 + 2 * (-sv.inc));
   }
   // CPV: the value of the row in front of a time chunk, one slot behind all the others (the
-  // LAST of the node's slots: walk_fused.h, fop_implicit)
+  // LAST of the node's slots: walk_fused.h, WindowEpilogue)
   for (const PipeSieve &sv : pl->sieves)
     if (sv.kind == FR_SIEVE_CPV) {
       pl->jit_ops.cps += 1;

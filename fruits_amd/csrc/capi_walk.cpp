@@ -302,7 +302,7 @@ int launch_pieces(const WalkCall &c, const fr::IssArgs &a, bool &done) {
       return fail(FR_E_LIMIT, std::string(c.who) + ": a piece kernel was compiled for another feature window");
     if (b.feat_window == 0)
       return fail(FR_E_LIMIT, std::string(c.who) + ": the chunk carries and the features of one node do not fit the LDS");
-    const size_t lds = other + fr::feat_window_bytes(b.feat_window, b.has_mpi != 0, false);
+    const size_t lds = other + fr::feat_window_bytes(b.feat_window, b.has_mpi != 0);
     hipError_t je = fr::jit_launch_fused(pcs.progs[t], b, lds, c.st);
     if (je != hipSuccess) return hip_fail(je, "fused walk (a piece type) launch");
   }
@@ -332,7 +332,7 @@ int launch_own_kernel(const WalkCall &c, const fr::GroupedProgram &gp, fr::IssAr
   const int64_t chunk = fr::walk_chunk_elems(c.T);
   a.nchunks = (int32_t)((c.T + chunk - 1) / chunk);
   const size_t lds = ((size_t)a.R * chunk + 16 + 8 + (a.nchunks > 1 ? a.carry_slots : 0)) * 8 +
-                     fr::feat_window_bytes(a.feat_window, a.has_mpi != 0, false);
+                     fr::feat_window_bytes(a.feat_window, a.has_mpi != 0);
   hipError_t je = fr::jit_launch_fused(own, a, lds, c.st);
   if (je != hipSuccess) return hip_fail(je, "fused walk (run-time compiled) launch");
   done = true;

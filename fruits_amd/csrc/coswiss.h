@@ -226,7 +226,16 @@ __device__ __forceinline__ void cos_scan_all(WalkCtx &cx, CosState<C, S> &st,
       c[h * E + E - 1] = b + incl[m * P + h];
       b += ptot[m * P + h];
     }
-    if (st.last) cos_add_result<C, S>(st, m, c, res);
+    if (st.last) {
+      cos_add_result<C, S>(st, m, c, res);
+      // (the fused wave-per-unit kernel with E = 4: this stays a branch.  These units compile
+      // with a*b+c contraction, and WHICH product of the local sums above is fused into its add
+      // follows the shape of this code: speculated into selects, that kernel rounded another
+      // product than it did before the epilogue became walk_device.h's fop - one ulp in the row.
+      // Only there: in the E = 2 kernels the barrier costs 18 to 42 VGPRs, an occupancy step.
+      // It follows the compiler, not the source - tests/test_epilogue_gpu.py holds the bits.)
+      if constexpr (C::MODE == 1 && C::TEAM == 1 && C::E == 4) asm volatile("" ::: "memory");
+    }
   }
 }
 
@@ -256,8 +265,6 @@ __device__ __forceinline__ void coswiss_unit(WalkCtx &cx, const double *xrow, co
     load_global_row<C>(cx, trig + a.T, cs);
     build_q<S, 0, EP>(st.q, sn, cs);
   }
-  Ops2 pre;
-  if constexpr (C::MODE == 1) pre = load_ops2(a, k_out, 0);
 #pragma unroll
   for (int i = 0; i < EP; ++i) res[i] = resx[i] = 0.0;
   const int L = le - lb;
@@ -313,7 +320,7 @@ __device__ __forceinline__ void coswiss_unit(WalkCtx &cx, const double *xrow, co
     cx.slot = kCosMaxLetters * (S + 1);
     if (total) prev_first_differences<C>(cx, res, resx);  // resx[t] = res[t-1]
     cx.slot += 3;
-    fused_all<C>(cx, nd, pre, res, resx, s, !total);
+    fops_rows<C>(cx, nd, res, resx, s, !total);
   } else {
     emit_store<C>(cx, res, cx.out_base + (int64_t)k_out * a.out_k_stride);
   }
@@ -343,7 +350,6 @@ __global__ __launch_bounds__(kWalkThreads) void coswiss_kernel(const IssArgs a) 
     double *fw = cx.carry + (kCosMaxLetters * (S + 1) + 8);
     cx.fl_val = (lds_f64 *)fw;
     cx.fl_cnt = (lds_f64 *)(fw + a.feat_window);
-    cx.fl_col = (lds_i32 *)(fw + (a.has_mpi ? 2 : 1) * a.feat_window);
     for (int sl = tid; sl < a.feat_window; sl += kWalkThreads) {
       cx.fl_val[sl] = 0.0;
       if (a.has_mpi) cx.fl_cnt[sl] = 0.0;
@@ -367,8 +373,7 @@ __global__ __launch_bounds__(kWalkThreads) void coswiss_kernel(const IssArgs a) 
       if constexpr (C::MODE == 1) {
         cx.feat_row = a.feats + n * a.feat_stride;
         cx.cnt_row = a.cnt + n * a.feat_stride;
-        cx.cut_row = a.series_cuts ? a.series_cuts + n * a.cut_slots : nullptr;
-      cx.series = n;
+        cx.series = n;
       }
       coswiss_unit<C, S>(cx, a.X + (int64_t)j * a.cw_x_unit_stride + n * a.D * a.T + t0,
                          a.aux + (int64_t)f * 2 * a.T + t0, lb, le, a.cw_total != 0, j, tot_all,
@@ -376,6 +381,7 @@ __global__ __launch_bounds__(kWalkThreads) void coswiss_kernel(const IssArgs a) 
     }
     if constexpr (C::MODE == 1) {
       cx.fused_used = a.n_ops;
+      cx.frow0 = j;   // (the unit's row: no slot_rows table in a CosWISS launch)
       feat_flush<C>(cx, false);
     }
   }
@@ -403,6 +409,7 @@ __global__ __launch_bounds__(kWalkThreads) void coswiss_packed_kernel(const IssA
   cx.t0 = 0;
   cx.first_chunk = true;
   cx.full_chunk = C::CHUNK <= a.T;
+  cx.fslot = 0;
   const int64_t per_series = (int64_t)a.cw_W * a.cw_F;
   const int64_t units = a.N * per_series;
   for (int64_t u = (int64_t)blockIdx.x * C::TEAMS + cx.team; u < units;
@@ -415,7 +422,6 @@ __global__ __launch_bounds__(kWalkThreads) void coswiss_packed_kernel(const IssA
     if constexpr (C::MODE == 1) {
       cx.feat_row = a.feats + n * a.feat_stride;
       cx.cnt_row = a.cnt + n * a.feat_stride;
-      cx.cut_row = a.series_cuts ? a.series_cuts + n * a.cut_slots : nullptr;
       cx.series = n;
     }
     coswiss_unit<C, S>(cx, a.X + (int64_t)j * a.cw_x_unit_stride + n * a.D * a.T,

@@ -122,10 +122,10 @@ inline int feat_window_sized(int widest, int largest_group, size_t other_lds_byt
   const size_t budget = 38 * 1024;
   int W = 64;
   while (W < 1024 && W < largest_group &&
-         other_lds_bytes + feat_window_bytes(2 * W, mpi, false) <= budget)
+         other_lds_bytes + feat_window_bytes(2 * W, mpi) <= budget)
     W *= 2;
   if (W < widest) W = (widest + 1) / 2 * 2;
-  if (other_lds_bytes + feat_window_bytes(W, mpi, false) > 160 * 1024) return 0;
+  if (other_lds_bytes + feat_window_bytes(W, mpi) > 160 * 1024) return 0;
   fits = largest_group <= W;
   return W;
 }

@@ -11,16 +11,14 @@
 namespace fr {
 
 // ---------------------------------------------------------------- launch
-template <int E, int P, int LV, int MULTI, bool VEC, bool W, int TEAM = 4, int MODE = 0,
-          int SEMI = 0, bool NT = false, bool TI = false>
+// launch of the materialising interpreter (iss_walk_kernel, walk_device.h)
+template <int E, int P, int LV, int MULTI, bool VEC, bool W, int SEMI = 0, bool NT = false>
 static hipError_t launch_walk_cfg(const IssArgs &a, hipStream_t st) {
-  using C = WalkCfg<E, P, LV, MULTI, VEC, W, TEAM, MODE, SEMI, NT, TI>;
-  // rows, wave totals, LDS carries, then (fused, cooperative) the feature window: value,
-  // population (MPI) and column of every slot
+  using C = WalkCfg<E, P, LV, MULTI, VEC, W, 4, 0, SEMI, NT>;
+  // rows, wave totals, LDS carries
   const size_t lds = ((size_t)a.R * C::CHUNK + 2 * C::NW + 2 * C::NW +
                       (MULTI == 1 ? a.carry_slots : 0)) *
-                         sizeof(double) +
-                     ((MODE == 1 && TEAM != 1) ? feat_window_bytes(a.feat_window, a.has_mpi != 0) : 0);
+                     sizeof(double);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   static LaunchCache cache;  // per instantiation; per-device entries, thread-safe
   int per_cu = 1;
@@ -57,7 +55,7 @@ static hipError_t launch_fused_mode(const IssArgs &a, hipStream_t st) {
   // instruction of a wave then covers its 1 KiB without holes)
   using C = WalkCfg<MODE == 2 ? 2 : E, (MODE == 2 && E == 4) ? 2 : 1, LV, MULTI, true, W, 4, MODE, SEMI, false, TI, HO>;
   const size_t lds = ((size_t)a.R * C::CHUNK + 16 + 8 + (MULTI == 1 ? a.carry_slots : 0)) * sizeof(double) +
-                     feat_window_bytes(a.feat_window, a.has_mpi != 0, false) + (size_t)a.lds_pad;
+                     feat_window_bytes(a.feat_window, a.has_mpi != 0) + (size_t)a.lds_pad;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   static LaunchCache cache;  // per instantiation; per-device entries, thread-safe
   int per_cu = 1;

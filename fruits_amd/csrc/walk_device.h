@@ -108,17 +108,15 @@ struct WalkCtx {
   double *out_base;     // out + n*out_n_stride + t0
   double *feat_row;     // MODE 1: feats + n*feat_stride
   double *cnt_row;      // MODE 1: band population of MPI features
-  // MODE 1, cooperative kernels: the features of a unit accumulate in an LDS window (value,
-  // MPI population, column of every slot) and leave with plain stores (feat_flush); a unit
-  // owns its feature columns, so nothing in global memory is ever added to atomically
+  // MODE 1, cooperative kernels: the features of a unit accumulate in an LDS window (value and
+  // MPI population of every slot) and leave with plain stores (feat_flush); a unit owns its
+  // feature columns, so nothing in global memory is ever added to atomically
   lds_f64 *fl_val;
   lds_f64 *fl_cnt;
-  lds_i32 *fl_col;
   int fslot;            // first window slot of the node being processed
   int fused_used;       // slots of the window in use
-  int frow0;            // fused walk: position in IssArgs::slot_rows of the window's first output row
+  int frow0;            // the window's first output row: its position in IssArgs::slot_rows (feat_flush)
   int feat_window;      // slots of the window (a huge number when every group's features fit)
-  const int32_t *cut_row;  // MODE 1: this series' row of IssArgs::series_cuts (or nullptr)
   int64_t series;          // MODE 1: index of the series being walked
   double *carry;        // carry slots of this series (multi-chunk; LDS or global) or nullptr
   int64_t t0;           // first time index of the chunk
@@ -464,17 +462,70 @@ __device__ __forceinline__ void emit_all(const WalkCtx &cx, const Rec &nd,
 // flattens the sieves of row k into n_ops fixed-size "feature ops" (FeatOp) whose
 // cuts and fitted thresholds are already resolved, so one scalar load per op
 // brings everything and there are no dependent table look-ups.
-struct Ops2 {
-  int32_t w[16];  // two FeatOps
-};
+//
+// ONE evaluator (fop) serves every kernel with a fused epilogue: the cooperative fused walk
+// (walk_fused.h), the wave-per-series kernel (walk_packed.h) and both CosWISS kernels (coswiss.h).
+// What a family decides for itself:
+//   * where a result goes (feat_put_*): a slot of the LDS feature window (TEAM 4; feat_flush
+//     writes it to its column) or, where one wave holds the whole row (TEAM 1), the series'
+//     feature and population rows directly;
+//   * the policy EPI: the scan a cumulation (inc < 0) takes and the node's carry slot of the CPV
+//     exchange - RowEpilogue below (packed, CosWISS), WindowEpilogue of walk_fused.h.
 
-__device__ __forceinline__ Ops2 load_ops2(const IssArgs &a, int64_t k, int first) {
-  cptr<int32_t> q = as_const(reinterpret_cast<const int32_t *>(
-      __builtin_assume_aligned(a.ops + (k * a.n_ops_padded + first), 64)));
-  Ops2 o;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) o.w[i] = q[i];
-  return o;
+// feature-op flags (FeatOp::kind_inc), resolved by the host (capi_pipeline.cpp, fr_pipeline_set_quantiles)
+constexpr int32_t OPF_SERIES_CUTS = 1 << 16;   // lo / hi name slots of the series' cut row
+// bits 20-22: the op's SHAPE when it is one of the common ones (0: none of them)
+constexpr int OPF_SHAPE_SHIFT = 20;
+constexpr int OPF_SHAPE_END = 1;     // END at a fixed index (lo)
+constexpr int OPF_SHAPE_BAND1 = 2;   // NPI over the whole series, qlo < v (qhi = +inf); | 1: of the first differences
+constexpr int OPF_SHAPE_BAND2 = 4;   // NPI over the whole series, qlo < v <= qhi;       | 1: of the first differences
+
+// Single-lane LDS operations of a whole wave in uniform control flow (EXEC all ones before and
+// after): the lane is selected by writing EXEC, not by a compare + saved mask + branch - two
+// scalar instructions, no mask registers kept alive.  `off` is an LDS BYTE address.
+__device__ __forceinline__ void lds_store_lane63(int off, double v) {
+  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_write_b64 %0, %1\n\ts_mov_b64 exec, -1"
+               :: "v"(off), "v"(v) : "memory", "scc");   // (s_lshl_b64 writes SCC)
+}
+__device__ __forceinline__ void lds_store_lane(int lane, int off, double v) {
+  asm volatile("s_lshl_b64 exec, 1, %2\n\tds_write_b64 %0, %1\n\ts_mov_b64 exec, -1"
+               :: "v"(off), "v"(v), "s"(__builtin_amdgcn_readfirstlane(lane)) : "memory", "scc");
+}
+__device__ __forceinline__ void lds_store_lane0_i32(int off, int v) {
+  asm volatile("s_mov_b64 exec, 1\n\tds_write_b32 %0, %1\n\ts_mov_b64 exec, -1"
+               :: "v"(off), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_add_lane0(int off, double v) {
+  asm volatile("s_mov_b64 exec, 1\n\tds_add_f64 %0, %1\n\ts_mov_b64 exec, -1"
+               :: "v"(off), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_add_lane63(int off, double v) {
+  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_add_f64 %0, %1\n\ts_mov_b64 exec, -1"
+               :: "v"(off), "v"(v) : "memory", "scc");
+}
+__device__ __forceinline__ void lds_add2_lane63(int off0, double v0, int off1, double v1) {
+  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_add_f64 %0, %1\n\tds_add_f64 %2, %3\n\ts_mov_b64 exec, -1"
+               :: "v"(off0), "v"(v0), "v"(off1), "v"(v1) : "memory", "scc");
+}
+__device__ __forceinline__ int lds_offset(const void __attribute__((address_space(3))) *p) {
+  return (int)(unsigned)(__UINTPTR_TYPE__)p;
+}
+
+// The kernel arguments as seen from code that rarely runs (flushes, reciprocal factors, further
+// output rows, per-series cuts): read through a pointer the optimiser cannot look through, so
+// that they are loaded where they are used instead of being hoisted out of the node loop into
+// scalar registers - there are only 102 of those, and the hot path needs them.
+// (The IssArgs struct is the only argument of every kernel with a fused epilogue: it starts the
+// kernel-argument segment.)
+__device__ __forceinline__ cptr<IssArgs> cold_args() {
+  cptr<IssArgs> ap = (cptr<IssArgs>)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ap));
+  return ap;
+}
+// this series' row of IssArgs::series_cuts (ops with OPF_SERIES_CUTS: coquantile positions,
+// per-series lengths) - the one place series cuts are resolved
+__device__ __forceinline__ cptr<int32_t> series_cut_row(const WalkCtx &cx, cptr<IssArgs> ca = cold_args()) {
+  return as_const(ca->series_cuts + cx.series * ca->cut_slots);
 }
 
 __device__ __forceinline__ double bits_to_double(int lo, int hi) {
@@ -542,191 +593,307 @@ struct FusedScratch {
   bool have_cp = false;
 };
 
-// `s` is the scan input the values came from (c = cumsum(s)) when seq_steps.  Then a
-// Reals first difference is formed as fl(x + s) - x, the step a SEQUENTIAL cumsum
-// takes from the same prefix (np.cumsum in the reference): a summand the running sum
+// The epilogue policy of the kernels that hold a whole record (wave-per-series kernel, CosWISS):
+// a cumulation is a block_scan - one-chunk series only, the host refuses longer ones: every
+// cumulation would need a carry of its own -, the CPV exchange carries in the node's slot 3.
+// No short paths for the shapes the host flags (OPF_SHAPE_*): these kernels never took them, and
+// with them the deep wave-per-series instances need four more VGPRs (an occupancy step).
+struct RowEpilogue {
+  template <class CR>
+  static __device__ __forceinline__ void cumulate(WalkCtx &cx, int, const double (&d)[CR::EP],
+                                                  double (&cs)[CR::EP]) {
+    double xs[CR::EP];
+    block_scan<CR>(cx, d, cs, xs, 0);
+  }
+  static constexpr bool short_paths = false;
+  static __device__ __forceinline__ int cpv_slot() { return 3; }
+};
+
+// Where a result goes (see above).  Counts are the same in every lane; a sum is its wave's total
+// in lane 63 (wave_inclusive_scan); a key is the wave's largest in every lane.
+template <class C>
+__device__ __forceinline__ void feat_put_count(WalkCtx &cx, int slot, int col, int cnt) {
+  if constexpr (C::TEAM != 1) lds_add_lane0(lds_offset(cx.fl_val + slot), (double)cnt);
+  else if (cx.lane == 0) cx.feat_row[col] = (double)cnt;
+}
+template <class C>
+__device__ __forceinline__ void feat_put_sum(WalkCtx &cx, int slot, int col, double sum) {
+  if constexpr (C::TEAM != 1) lds_add_lane63(lds_offset(cx.fl_val + slot), sum);
+  else if (cx.lane == 63) cx.feat_row[col] = sum;
+}
+template <class C>
+__device__ __forceinline__ void feat_put_mean(WalkCtx &cx, int slot, int col, double sum, int cnt) {
+  if constexpr (C::TEAM != 1) {
+    // one LDS instruction pair per wave (ds_add_f64, nothing returned)
+    lds_add2_lane63(lds_offset(cx.fl_val + slot), sum, lds_offset(cx.fl_cnt + slot), (double)cnt);
+  } else if (cx.lane == 63) {
+    cx.feat_row[col] = sum;
+    cx.cnt_row[col] = (double)cnt;
+  }
+}
+template <class C>
+__device__ __forceinline__ void feat_put_key(WalkCtx &cx, int slot, int col, uint64_t key) {
+  if (cx.lane == 0) {
+    // (one ds_max_u64; the flush combines a window's keys with the row's by maximum)
+    if constexpr (C::TEAM != 1) lds_max_u64(cx.fl_val + slot, key);
+    else cx.feat_row[col] = __builtin_bit_cast(double, key);
+  }
+}
+
+// c[eu] for a uniform eu: a chain of uniform branches (the empty asm keeps the arms apart: as
+// selects, or as an index, the compiler would send the whole array through scratch memory)
+template <int EP, int K>
+__device__ __forceinline__ double pick_uniform(int eu, const double (&c)[EP]) {
+  if constexpr (K + 1 >= EP) {
+    return c[K];
+  } else {
+    double v;
+    if (eu == K) {
+      v = c[K];
+      asm volatile("" : "+v"(v));
+    } else {
+      v = pick_uniform<EP, K + 1>(eu, c);
+    }
+    return v;
+  }
+}
+
+// END: the value at series index `pick`
+template <class C>
+__device__ __forceinline__ void end_pick(WalkCtx &cx, int pick, int slot, int col,
+                                         const double (&c)[C::EP]) {
+  constexpr int E = C::E;
+  const unsigned rel = (unsigned)(pick - (int)cx.t0);
+  if (rel >= (unsigned)C::CHUNK) return;           // another time chunk's element
+  if ((int)(rel / C::SPAN) != cx.wave) return;     // another wave's
+  // the position is uniform: uniform selects of the register, ONE lane stores
+  const unsigned q = rel % C::SPAN, r = q % C::PIECE;   // (piece q / PIECE, lane r / E, element r % E)
+  const double v = pick_uniform<C::EP, 0>((int)(q / C::PIECE * E + r % E), c);
+  if constexpr (C::TEAM != 1) lds_store_lane((int)(r / E), lds_offset(cx.fl_val + slot), v);
+  else if (cx.lane == (int)(r / E)) cx.feat_row[col] = v;
+}
+
+// series index of the lane's element (h = 0, e = 0); element (h, e) is h * PIECE + e behind it
+template <class C>
+__device__ __forceinline__ int first_index(const WalkCtx &cx) {
+  return (int)cx.t0 + cx.wave * C::SPAN + cx.lane * C::E;
+}
+
+// The band of an op: segment [lo, hi) x thresholds (qlo, qhi].  `count`: the elements of the wave
+// inside, element by element (the AND of the compare masks: as one predicate it goes through a
+// vector register).
+struct Band {
+  int lo, hi;
+  double qlo, qhi;
+  __device__ __forceinline__ bool in(int t, double v) const {
+    return t >= lo && t < hi && qlo < v && v <= qhi;
+  }
+  __device__ __forceinline__ int count(int t, double v) const {
+    return __popcll(__ballot(t >= lo && t < hi) & __ballot(qlo < v) & __ballot(v <= qhi));
+  }
+};
+
+// PPV / CPV (fruits/sieving/implicit.py:114-129, 169-190): the indicator is closed BELOW -
+// v >= qlo, or with OPF_SEGMENTS qlo <= v < qhi, a conjunction per element (the thresholds are
+// not sorted: a band with qlo > qhi is empty; a NaN is never in, +inf is in above a finite qlo).
+// PPV counts it; CPV counts its rising edges at t >= 1 - the first difference of the indicator
+// is zero-padded (fruits/cache.py:8-13), a component that starts at t = 0 is not counted.  The
+// indicator at t - 1 is taken from the VALUE the row holds there (c, what MODE 2 stores): the
+// lane's own register, the neighbour lane's, the wave's in front through LDS, and across time
+// chunks the node's carry slot EPI::cpv_slot().  The exchange is made once per node and chunk,
+// whatever the number of CPV ops (FusedScratch, like the first differences of the inc = 2 ops),
+// so one slot does.  Counts are integers; implicit_finalize_kernel divides them.  `hi`: T, or
+// with OPF_SERIES_CUTS the slot of the series' own length.
+template <class C, class EPI, class W>
+__device__ __forceinline__ void fop_implicit(WalkCtx &cx, W w, int slot,
+                                             const double (&c)[C::EP], FusedScratch<C::EP> &sc) {
+  constexpr int E = C::E, P = C::P;
+  const bool cpv = (w[0] & 0xff) == FR_SIEVE_CPV_K, seg = (w[0] & OPF_SEGMENTS) != 0;
+  int hi = w[3];
+  if ((w[0] & OPF_SERIES_CUTS) != 0) hi = series_cut_row(cx)[w[3]];
+  const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
+  if (cpv && !sc.have_cp) {
+    int at = 0;
+    if constexpr (C::MULTI != 0) at = EPI::cpv_slot();
+    prev_first_differences<C>(cx, c, sc.cp, at);   // cp[t] = c[t - 1]
+    sc.have_cp = true;
+  }
+  const auto inside = [&](double v) { return seg ? (qlo <= v && v < qhi) : (v >= qlo); };
+  const int t_first = first_index<C>(cx);
+  int cnt = 0;
+#pragma unroll
+  for (int h = 0; h < P; ++h)
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const int t = t_first + h * C::PIECE + e;
+      bool in = inside(c[h * E + e]);
+      if (cpv) in = in && !inside(sc.cp[h * E + e]) && t >= 1;
+      cnt += __popcll(__ballot(in && t < hi));
+    }
+  feat_put_count<C>(cx, slot, w[1], cnt);
+}
+
+// First differences d[t] = c[t] - c[t-1], zero-padded at element 0 of the series
+// (fruits/cache.py:8-13).  `s` is the scan input the values came from (c = cumsum(s)) when
+// seq_steps.  Then a Reals first difference is formed as fl(x + s) - x, the step a SEQUENTIAL
+// cumsum takes from the same prefix (np.cumsum in the reference): a summand the running sum
 // absorbs gives an increment of exactly 0, as in the reference, where the difference of
 // two parallel-scan values is +-1 ulp of noise - which "number of positive increments"
 // (NPI with its default q = (0, 1)) would count at random.
 template <class C>
-__device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot,
-                                         const double (&c)[C::EP], const double (&x)[C::EP],
-                                         const double (&s)[C::EP], bool seq_steps,
-                                         FusedScratch<C::EP> &sc) {
-  constexpr int E = C::E, P = C::P, EP = C::EP;
-  const int kind = w[0] & 0xff, inc = (int)(int8_t)((w[0] >> 8) & 0xff), col = w[1];   // inc: signed
-  // per-series cuts (coquantile positions): lo / hi name slots of the series' cut row
-  const bool series_cuts = (w[0] >> 16) & 1;
-  const bool keyed = kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K;
-  if constexpr (C::TEAM != 1) {
-    // (the flush needs the column of every slot, also of one no lane adds to; ~col: a MAX / MIN
-    // slot, combined by maximum of keys)
-    if (cx.wave == 0 && cx.lane == 0) cx.fl_col[slot] = keyed ? ~col : col;
+__device__ __forceinline__ void first_differences(const WalkCtx &cx, const double (&c)[C::EP],
+                                                  const double (&x)[C::EP], const double (&s)[C::EP],
+                                                  bool seq_steps, double (&d)[C::EP]) {
+#pragma unroll
+  for (int i = 0; i < C::EP; ++i) {
+    double step = c[i] - x[i];
+    if (C::SEMI == 0 && seq_steps) step = (x[i] + s[i]) - x[i];
+    d[i] = step;
   }
+  d[0] = (cx.first_chunk && cx.wave == 0 && cx.lane == 0) ? 0.0 : d[0];
+}
+
+// One feature op on the node's values: w = the op's eight words (FeatOp; loaded by the caller), `slot` its
+// window slot.
+template <class C, class EPI, class W>
+__device__ __forceinline__ void fop(WalkCtx &cx, W w, int slot, const double (&c)[C::EP],
+                                    const double (&x)[C::EP], const double (&s)[C::EP],
+                                    bool seq_steps, FusedScratch<C::EP> &sc) {
+  constexpr int E = C::E, P = C::P, EP = C::EP;
+  // The shapes the host flags (OPF_SHAPE_*: END at a fixed index; a counting band over the whole
+  // series, of the values or of their first differences, with or without an upper threshold)
+  // are short straight-line paths where the family takes them (EPI::short_paths); everything else
+  // takes the general one below, which gives the same counts.
+  const int shape = EPI::short_paths ? (w[0] >> OPF_SHAPE_SHIFT) & 7 : 0;
+  if (shape == OPF_SHAPE_END) {
+    end_pick<C>(cx, w[2], slot, w[1], c);
+    return;
+  }
+  if (shape != 0 && cx.full_chunk) {
+    const double qlo = bits_to_double(w[4], w[5]);
+    double d[EP];
+    if (shape & 1) {
+      first_differences<C>(cx, c, x, s, seq_steps, d);
+    } else {
+#pragma unroll
+      for (int i = 0; i < EP; ++i) d[i] = c[i];
+    }
+    int cnt = 0;
+    if (shape >= OPF_SHAPE_BAND2) {
+      const double qhi = bits_to_double(w[6], w[7]);
+#pragma unroll
+      for (int i = 0; i < EP; ++i) cnt += __popcll(__ballot(qlo < d[i]) & __ballot(d[i] <= qhi));
+    } else {
+#pragma unroll
+      for (int i = 0; i < EP; ++i) cnt += __popcll(__ballot(qlo < d[i]));
+    }
+    feat_put_count<C>(cx, slot, w[1], cnt);
+    return;
+  }
+  const int kind = w[0] & 0xff, inc = (int)(int8_t)((w[0] >> 8) & 0xff);   // inc: signed
+  const bool series_cuts = (w[0] & OPF_SERIES_CUTS) != 0;
   if (kind == FR_SIEVE_END_K) {
     int pick = w[2];                    // index of the value to pick
     if (series_cuts) {                  // X[:, cut - 1], index -1 wrapping like numpy
-      pick = as_const(cx.cut_row)[w[2]] - 1;
-      if (pick < 0) pick += (int)cx.a->T;
+      cptr<IssArgs> ca = cold_args();
+      pick = series_cut_row(cx, ca)[w[2]] - 1;
+      if (pick < 0) pick += (int)ca->T;
     }
-    const int rel = pick - (int)cx.t0;
-    if (rel >= 0 && rel < C::CHUNK) {
-      const int wv = rel / C::SPAN;
-      if (cx.wave == wv) {
-        // the position is uniform: pick the register with uniform selects (static register
-        // indices: a computed index into c[] would send the array through scratch), then ONE
-        // lane stores it
-        const int r = rel - wv * C::SPAN;
-        const int hu = r / C::PIECE, q = r - hu * C::PIECE;
-        const int owner = q / E, eu = q - owner * E;
-        double v = c[0];
-#pragma unroll
-        for (int h = 0; h < P; ++h)
-#pragma unroll
-          for (int e = 0; e < E; ++e)
-            if (h * E + e > 0 && hu == h && eu == e) v = c[h * E + e];
-        if (cx.lane == owner) {
-          if constexpr (C::TEAM != 1) cx.fl_val[slot] = v;
-          else cx.feat_row[col] = v;
-        }
-      }
-    }
+    end_pick<C>(cx, pick, slot, w[1], c);
     return;
   }
-  int lo = w[2], hi = w[3];
-  if (series_cuts) {
-    lo = as_const(cx.cut_row)[w[2]];
-    hi = as_const(cx.cut_row)[w[3]];
-  }
-  const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
-  const int t_first = (int)cx.t0 + cx.wave * C::SPAN + cx.lane * E;  // element (h=0, e=0)
   if (kind == FR_SIEVE_PPV_K || kind == FR_SIEVE_CPV_K) {
-    // PPV / CPV (fruits/sieving/implicit.py:114-129, 169-190): the indicator v >= qlo - or with
-    // OPF_SEGMENTS qlo <= v < qhi, per element: the thresholds are not sorted - counted (PPV), or
-    // its rising edges at t >= 1 (CPV; zero-padded first difference, fruits/cache.py:8-13).  The
-    // value at t - 1 is the row's own (c): one neighbour exchange per node (FusedScratch), its
-    // chunk carry in the node's slot 3.  implicit_finalize_kernel divides the counts.
-    const bool cpv = kind == FR_SIEVE_CPV_K, seg = (w[0] & OPF_SEGMENTS) != 0;
-    if (cpv && !sc.have_cp) {
-      prev_first_differences<C>(cx, c, sc.cp, 3);
-      sc.have_cp = true;
-    }
-    int n_in = 0;
-#pragma unroll
-    for (int h = 0; h < P; ++h)
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int t = t_first + h * C::PIECE + e;
-        const double v = c[h * E + e];
-        bool in = seg ? (qlo <= v && v < qhi) : (v >= qlo);
-        if (cpv) {
-          const double u = sc.cp[h * E + e];
-          const bool before = seg ? (qlo <= u && u < qhi) : (u >= qlo);
-          in = in && !before && t >= 1;
-        }
-        n_in += __popcll(__ballot(in && t < hi));
-      }
-    if (cx.lane == 0) {
-      if constexpr (C::TEAM != 1) lds_add(cx.fl_val + slot, (double)n_in);
-      else cx.feat_row[col] = (double)n_in;
-    }
+    if constexpr (C::MODE == 1) fop_implicit<C, EPI>(cx, w, slot, c, sc);
     return;
   }
+  Band band{w[2], w[3], bits_to_double(w[4], w[5]), bits_to_double(w[6], w[7])};
+  if (series_cuts) {
+    cptr<int32_t> cut_row = series_cut_row(cx);
+    band.lo = cut_row[w[2]];
+    band.hi = cut_row[w[3]];
+  }
+  // element 0 of the series: increments are zero-padded there (fruits/cache.py:8-13)
+  const bool at0 = cx.first_chunk && cx.wave == 0 && cx.lane == 0;
   double d[EP];
   if (inc <= 0) {
 #pragma unroll
     for (int i = 0; i < EP; ++i) d[i] = c[i];
-    if constexpr (C::MULTI == 0) {
+    if constexpr (C::MULTI == 0 || C::HIGHORD) {
       // inc < 0: the row cumulated -inc times (np.cumsum, fruits/sieving/increment.py:68-70) -
-      // a plain sum whatever the semiring of the plan; one-chunk series only (the host
-      // refuses longer ones: every cumulation would need its own carry)
-      using CR = WalkCfg<C::E, C::P, C::MAXLV, 0, C::VEC, C::WEIGHTED, C::TEAM, C::MODE, 0>;
+      // a plain sum whatever the semiring of the plan, by the family's scan (EPI::cumulate).  On
+      // series of several chunks (WalkCfg::HIGHORD) the j-th cumulation carries its running sum
+      // in a slot pair of its own (walk_fused.h, WindowEpilogue).
+      using CR = WalkCfg<C::E, C::P, C::MAXLV, C::MULTI, C::VEC, C::WEIGHTED, C::TEAM, C::MODE, 0>;
       for (int k = inc; k < 0; ++k) {
-        double cs[EP], xs[EP];
-        block_scan<CR>(cx, d, cs, xs, 0);
+        double cs[EP];
+        EPI::template cumulate<CR>(cx, k - inc, d, cs);
 #pragma unroll
         for (int i = 0; i < EP; ++i) d[i] = cs[i];
       }
     }
   } else {
-    // increments are zero-padded at t = 0 (fruits/cache.py:8-13)
-#pragma unroll
-    for (int h = 0; h < P; ++h)
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const int i = h * E + e;
-        double step = c[i] - x[i];
-        if (C::SEMI == 0 && seq_steps) step = (x[i] + s[i]) - x[i];
-        d[i] = (t_first + h * C::PIECE + e == 0) ? 0.0 : step;
-      }
+    first_differences<C>(cx, c, x, s, seq_steps, d);
     if (inc >= 2) {
       if (!sc.have_dp) {
         prev_first_differences<C>(cx, d, sc.dp);
         sc.have_dp = true;
       }
 #pragma unroll
-      for (int h = 0; h < P; ++h)
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-          d[h * E + e] = (t_first + h * C::PIECE + e == 0) ? 0.0 : d[h * E + e] - sc.dp[h * E + e];
-      if constexpr (C::MULTI == 0) {
-        // third to eighth differences (IncrementSieve._pre_transform applies _increments inc
-        // times, fruits/sieving/increment.py:63-71): one more neighbour exchange per order.
-        // Single-chunk series only (the host refuses longer ones: an order needs its own
-        // carry between chunks).
+      for (int i = 0; i < EP; ++i) d[i] = d[i] - sc.dp[i];
+      d[0] = at0 ? 0.0 : d[0];
+      // third to eighth differences (IncrementSieve._pre_transform applies _increments inc times,
+      // fruits/sieving/increment.py:63-71): one more neighbour exchange per order; on series of
+      // several chunks (WalkCfg::HIGHORD; the host refuses them elsewhere) every order carries its
+      // last value of the chunk in a slot pair of its own (IssArgs::carry_per_node =
+      // 3 + 2 * (highest order - 2))
+      if constexpr (C::MULTI == 0 || C::HIGHORD) {
         for (int k = 3; k <= inc; ++k) {
           double dq[EP];
-          prev_first_differences<C>(cx, d, dq);
+          prev_first_differences<C>(cx, d, dq, 3 + 2 * (k - 3), C::MULTI != 0);
 #pragma unroll
-          for (int h = 0; h < P; ++h)
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-              d[h * E + e] = (t_first + h * C::PIECE + e == 0) ? 0.0 : d[h * E + e] - dq[h * E + e];
+          for (int i = 0; i < EP; ++i) d[i] = d[i] - dq[i];
+          d[0] = at0 ? 0.0 : d[0];
         }
       }
     }
   }
-  if (keyed) {
-    // MAX / MIN: the largest band_key (walk_types.h) of the wave, one ds_max_u64 per wave
+  // (the accumulation order inside a lane - pieces outer, elements inner - is part of the bits of
+  // the real-valued sums)
+  const int t_first = first_index<C>(cx);
+  if (kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K) {
+    // the largest band key of the wave (walk_types.h)
     uint64_t key = 0;
 #pragma unroll
     for (int h = 0; h < P; ++h)
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        const int t = t_first + h * C::PIECE + e;
         const double v = d[h * E + e];
         const uint64_t kv = band_key(v, kind == FR_SIEVE_MIN_K);
-        if (t >= lo && t < hi && qlo < v && v <= qhi && kv > key) key = kv;
+        if (band.in(t_first + h * C::PIECE + e, v) && kv > key) key = kv;
       }
-    key = wave_max_u64(key);
-    if (cx.lane == 0) {
-      if constexpr (C::TEAM != 1) lds_max_u64(cx.fl_val + slot, key);
-      else cx.feat_row[col] = __builtin_bit_cast(double, key);
-    }
+    feat_put_key<C>(cx, slot, w[1], wave_max_u64(key));
     return;
   }
   if (kind == FR_SIEVE_CUR_K) {
-    // CUR (fruits/sieving/segment.py:228-272): the sum of the squares inside the band; no
-    // population, nothing divides it - the waves' (and the chunks') partial sums add up
+    // CUR (fruits/sieving/segment.py:228-272): the sum of the squares inside the band.  No
+    // population and nothing to divide: the partial sums of the waves - and, through the flush,
+    // of the time chunks - add up like NPI's counts
     double sum = 0.0;
 #pragma unroll
     for (int h = 0; h < P; ++h)
 #pragma unroll
       for (int e = 0; e < E; ++e) {
-        const int t = t_first + h * C::PIECE + e;
         const double v = d[h * E + e];
-        const bool in = t >= lo && t < hi && qlo < v && v <= qhi;
-        sum += in ? v * v : 0.0;
+        sum += band.in(t_first + h * C::PIECE + e, v) ? v * v : 0.0;
       }
-    sum = wave_last_lane(wave_inclusive_scan<0>(sum));
-    if (cx.lane == 0) {
-      if constexpr (C::TEAM != 1) lds_add(cx.fl_val + slot, sum);
-      else cx.feat_row[col] = sum;
-    }
+    feat_put_sum<C>(cx, slot, w[1], wave_inclusive_scan<0>(sum));
     return;
   }
-  // XPI: the sum of MPI is one of positions relative to the segment start (integers: exact)
-  const bool mpi = kind == FR_SIEVE_MPI_K || kind == FR_SIEVE_XPI_K;
+  // XPI: MPI of the positions relative to the segment start (integer sums: exact in any order).
+  // Every op leaves its result, zero counts included: every feature column is written exactly
+  // once per series and the feature tensor needs no clearing.
+  const bool xpi = kind == FR_SIEVE_XPI_K;
+  const bool mpi = kind == FR_SIEVE_MPI_K || xpi;
   int cnt = 0;
   double sum = 0.0;
 #pragma unroll
@@ -735,71 +902,39 @@ __device__ __forceinline__ void fused_op(WalkCtx &cx, const int32_t *w, int slot
     for (int e = 0; e < E; ++e) {
       const int t = t_first + h * C::PIECE + e;
       const double v = d[h * E + e];
-      const bool in = t >= lo && t < hi && qlo < v && v <= qhi;
-      cnt += __popcll(__ballot(in));
-      if (kind == FR_SIEVE_MPI_K) sum += in ? v : 0.0;
-      else if (kind == FR_SIEVE_XPI_K) sum += in ? (double)(t - lo) : 0.0;
-    }
-  // every op leaves its result, zero counts included: every feature column is written exactly
-  // once per series and the feature tensor needs no clearing
-  if (mpi)
-    sum = wave_last_lane(wave_inclusive_scan<0>(sum));  // wave total by DPP (no LDS permutes)
-  if (cx.lane == 0) {
-    if constexpr (C::TEAM != 1) {
-      // one LDS add per wave (ds_add_f64, nothing returned)
       if (mpi) {
-        lds_add(cx.fl_val + slot, sum);
-        lds_add(cx.fl_cnt + slot, (double)cnt);
+        const bool in = band.in(t, v);
+        cnt += __popcll(__ballot(in));
+        sum += in ? (xpi ? (double)(t - band.lo) : v) : 0.0;
       } else {
-        lds_add(cx.fl_val + slot, (double)cnt);
-      }
-    } else {
-      // wave-per-unit kernels: the wave holds the whole (single-chunk) row
-      if (mpi) {
-        cx.feat_row[col] = sum;
-        cx.cnt_row[col] = (double)cnt;
-      } else {
-        cx.feat_row[col] = (double)cnt;
+        cnt += band.count(t, v);
       }
     }
-  }
+  if (mpi) feat_put_mean<C>(cx, slot, w[1], wave_inclusive_scan<0>(sum), cnt);
+  else feat_put_count<C>(cx, slot, w[1], cnt);
 }
 
-// (The IssArgs struct is the only kernel argument of every kernel that flushes: it starts the
-// kernel-argument segment.)
-// Flushes the LDS feature window of a cooperative kernel: slot s -> column fl_col[s] of the
-// series' feature row with plain stores (`add`: onto what earlier time chunks of the unit left
-// there - the unit owns its columns, so a plain read-modify-write by the thread that wrote them),
-// and clears the window.  The next adds come behind the next node's scan barrier.
-// TABLE (the fused walk): no columns in the window - a slot is (output row r of the unit's walk,
-// op i), its column the one the row's i-th op names (slot_rows, GroupedProgram).
-template <class C, bool TABLE = false>
+// Flushes the LDS feature window of a cooperative kernel with plain stores (`add`: onto what
+// earlier time chunks of the unit left there - the unit owns its columns, so a plain
+// read-modify-write by the thread that wrote them), and clears the window.  The next adds come
+// behind the next node's scan barrier.  No columns in the window: a slot is (output row r of the
+// unit's walk, op i), its column the one the row's i-th op names; the window's first row is
+// position cx.frow0 of IssArgs::slot_rows (GroupedProgram) or, without that table (a plan in
+// pieces numbers its output rows in walk order; a CosWISS unit has ONE row), row cx.frow0 itself.
+template <class C>
 __device__ __forceinline__ void feat_flush(WalkCtx &cx, bool add) {
   lds_barrier();   // the adds of every wave are in
-  // (the kernel arguments through a pointer the optimiser cannot look through: loaded here,
-  // where they are used, not kept in scalar registers over the whole walk)
-  cptr<IssArgs> ap = (cptr<IssArgs>)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(ap));
+  cptr<IssArgs> ap = cold_args();
   const bool mpi = ap->has_mpi != 0;
   double *feat_row = ap->feats + cx.series * ap->feat_stride;
   double *cnt_row = ap->cnt + cx.series * ap->feat_stride;
   const int n_ops = ap->n_ops;
   for (int sl = cx.tid; sl < cx.fused_used; sl += kWalkThreads) {
-    int col;
-    bool keyed;   // a MAX / MIN slot (band keys, walk_types.h)
-    if constexpr (TABLE) {
-      const int r = sl / n_ops, i = sl - r * n_ops;
-      // (a plan in pieces numbers its output rows in walk order: no table)
-      const int64_t k = ap->slot_rows != nullptr ? as_const(ap->slot_rows)[cx.frow0 + r] : cx.frow0 + r;
-      cptr<FeatOp> op = as_const(ap->ops) + k * ap->n_ops_padded + i;
-      col = op->col;
-      const int kind = op->kind_inc & 0xff;
-      keyed = kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K;
-    } else {
-      col = cx.fl_col[sl];
-      keyed = col < 0;   // (fused_op: ~col)
-      col = keyed ? ~col : col;
-    }
+    const int r = sl / n_ops, i = sl - r * n_ops;
+    const int64_t k = ap->slot_rows != nullptr ? as_const(ap->slot_rows)[cx.frow0 + r] : cx.frow0 + r;
+    cptr<FeatOp> op = as_const(ap->ops) + k * ap->n_ops_padded + i;
+    const int col = op->col, kind = op->kind_inc & 0xff;
+    const bool keyed = kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K;   // band keys, walk_types.h
     double v = cx.fl_val[sl];
     if (add) {
       const double before = feat_row[col];
@@ -818,40 +953,79 @@ __device__ __forceinline__ void feat_flush(WalkCtx &cx, bool add) {
       cx.fl_cnt[sl] = 0.0;
     }
   }
-  if constexpr (TABLE) cx.frow0 += cx.fused_used / n_ops;
+  cx.frow0 += cx.fused_used / n_ops;
   cx.fused_used = 0;
 }
 
 // Window slots of the next node (`need` = output rows x feature ops); a full window leaves first.
-template <class C, bool TABLE = false>
+template <class C>
 __device__ __forceinline__ void feat_reserve(WalkCtx &cx, int need) {
-  if (cx.fused_used + need > cx.feat_window) feat_flush<C, TABLE>(cx, !cx.first_chunk);
+  if (cx.fused_used + need > cx.feat_window) feat_flush<C>(cx, !cx.first_chunk);
   cx.fslot = cx.fused_used;
   cx.fused_used += need;
 }
 
+// Two feature ops of one output row (64 bytes, one scalar load), requested a step ahead of their
+// use in the wave-per-series kernel: without this prefetch it waits for every op (measured: 2 % on
+// its fused benchmark line).
+struct OpPair {
+  int32_t w[16];
+};
+__device__ __forceinline__ OpPair load_op_pair(const IssArgs &a, int64_t k, int first) {
+  cptr<int32_t> q = as_const(reinterpret_cast<const int32_t *>(
+      __builtin_assume_aligned(a.ops + (k * a.n_ops_padded + first), 64)));
+  OpPair o;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o.w[i] = q[i];
+  return o;
+}
+
+// The feature ops of every output row of a node of the wave-per-series kernel.  `pre`: ops 0-1 of
+// the first row, requested at the start of the node; the next pair is requested behind the
+// current one.  Window slot of (output row j, op i): fslot + j * n + i.
 template <class C>
-__device__ __forceinline__ void fused_all(WalkCtx &cx, const Rec &nd, const Ops2 &pre,
-                                          const double (&c)[C::EP], const double (&x)[C::EP],
-                                          const double (&s)[C::EP], bool seq_steps) {
+__device__ __forceinline__ void fops_rows_ahead(WalkCtx &cx, const Rec &nd, const OpPair &pre,
+                                                const double (&c)[C::EP], const double (&x)[C::EP],
+                                                const double (&s)[C::EP], bool seq_steps) {
   const IssArgs &a = *cx.a;
   const int ne = nd.emit_count(), n = a.n_ops;
   int64_t k = nd.w[7];
-  Ops2 o = pre;  // ops 0-1 of the first row were requested at the start of the node
+  OpPair o = pre;
   FusedScratch<C::EP> sc;
-  int slot = cx.fslot;   // window slot of (output row j, op i): fslot + j * n + i
+  int slot = cx.fslot;
   for (int j = 0;;) {
     for (int i = 0;;) {
-      fused_op<C>(cx, o.w, slot + i, c, x, s, seq_steps, sc);
-      if (i + 1 < n) fused_op<C>(cx, o.w + 8, slot + i + 1, c, x, s, seq_steps, sc);
+      fop<C, RowEpilogue>(cx, o.w, slot + i, c, x, s, seq_steps, sc);
+      if (i + 1 < n) fop<C, RowEpilogue>(cx, o.w + 8, slot + i + 1, c, x, s, seq_steps, sc);
       i += 2;
       if (i >= n) break;
-      o = load_ops2(a, k, i);
+      o = load_op_pair(a, k, i);
     }
     if (++j >= ne) break;
     slot += n;
     k = j == 1 ? (int64_t)nd.w[8] : (int64_t)as_const(a.emit_rows)[nd.emit_begin() + j];
-    o = load_ops2(a, k, 0);
+    o = load_op_pair(a, k, 0);
+  }
+}
+
+// The same rows without the prefetch, an op's words read where they are used: CosWISS, whose unit
+// is one node with one row - its S+1 scans leave no scalar registers for a pair held ahead (the
+// prefetch costs the multi-chunk kernels spills, and nothing in time).
+template <class C>
+__device__ __forceinline__ void fops_rows(WalkCtx &cx, const Rec &nd, const double (&c)[C::EP],
+                                          const double (&x)[C::EP], const double (&s)[C::EP],
+                                          bool seq_steps) {
+  const IssArgs &a = *cx.a;
+  const int ne = nd.emit_count(), n = a.n_ops;
+  FusedScratch<C::EP> sc;
+  int slot = cx.fslot;
+  for (int j = 0; j < ne; ++j, slot += n) {
+    const int64_t k = j == 0 ? (int64_t)nd.w[7]
+                             : (j == 1 ? (int64_t)nd.w[8] : (int64_t)as_const(a.emit_rows)[nd.emit_begin() + j]);
+    for (int i = 0; i < n; ++i) {
+      fop<C, RowEpilogue>(cx, as_const(reinterpret_cast<const int32_t *>(a.ops + (k * a.n_ops_padded + i))),
+                          slot + i, c, x, s, seq_steps, sc);
+    }
   }
 }
 
@@ -860,7 +1034,7 @@ __device__ __forceinline__ void fused_all(WalkCtx &cx, const Rec &nd, const Ops2
 // c[t] (x) w[t] - c[t-1] (x) w[t-1] - the second term formed here from the exclusive prefix
 // (x[t] = c[t-1] bit for bit) and the weight row read one element to the left (staged in LDS;
 // the element in front of the chunk from the table itself).  The result takes x's place in
-// fused_op, whose plain difference then is the increment of the stored row, rounded like it.
+// fop, whose plain difference then is the increment of the stored row, rounded like it.
 template <class C>
 __device__ __forceinline__ void previous_weighted(const WalkCtx &cx, int emit_mul,
                                                   const double (&x)[C::EP], double (&xs)[C::EP]) {
@@ -899,9 +1073,9 @@ __device__ __forceinline__ void process_node(WalkCtx &cx, const Rec &nd, int slo
   double s[EP];
 #pragma unroll
   for (int i = 0; i < EP; ++i) s[i] = pin[i];
-  Ops2 pre;  // MODE 1: the first two feature ops of the first output row, requested early
+  OpPair pre;  // MODE 1: the first two feature ops of the first output row, requested early
   if constexpr (C::MODE == 1) {
-    if (nd.emit_count() > 0) pre = load_ops2(*cx.a, nd.w[7], 0);
+    if (nd.emit_count() > 0) pre = load_op_pair(*cx.a, nd.w[7], 0);
   }
   const int nf = nd.fac_count();
   bool letter_sum = false;
@@ -954,17 +1128,11 @@ __device__ __forceinline__ void process_node(WalkCtx &cx, const Rec &nd, int slo
       // total weighting: Reals emit c * exp(-g alpha_k), Arctic emit c - g alpha_k
       if (C::WEIGHTED && emit_mul >= 0)
         mul_row<C>(cx, C::SEMI != 1 ? emit_mul : fac_arctic(emit_mul, -1), c);
-      if constexpr (C::MODE == 1 && C::TOTALINC) {
-        if (emit_mul >= 0) {
-          double xs[EP];
-          previous_weighted<C>(cx, emit_mul, x, xs);
-          fused_all<C>(cx, nd, pre, c, xs, s, false);
-        } else {
-          fused_all<C>(cx, nd, pre, c, x, s, true);
-        }
-      } else if constexpr (C::MODE == 1) {
-        fused_all<C>(cx, nd, pre, c, x, s, !(C::WEIGHTED && emit_mul >= 0));
-      } else
+      // (MODE 1 here is the wave-per-series kernel, which a totally weighted plan under a
+      // differencing sieve never takes: launch_choice.h, walk_is_packed)
+      if constexpr (C::MODE == 1)
+        fops_rows_ahead<C>(cx, nd, pre, c, x, s, !(C::WEIGHTED && emit_mul >= 0));
+      else
         emit_all<C>(cx, nd, c, more, n_more);
       STAMP(cx, 5);  // stores
     }
@@ -1290,28 +1458,8 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_static_kernel(const Iss
 #endif
 }
 
-// WALK_SPILL_LV: fused kernels with at least this many register levels are built for three
-// waves per SIMD (<= 168 VGPRs, no scratch) instead of four (128 VGPRs, the deepest frames
-// spill 20-92 bytes per lane).  Measured (fruits_amd.build --variant, one process per arm,
-// interleaved, r02h): four waves WITH the spills are faster - config 4 (6 levels) 23.9 vs
-// 27.8 ms, config 5 (8 levels, 4 chunks) 42.0 vs 49.5 ms - so the default keeps four waves.
-#ifndef WALK_SPILL_LV
-#define WALK_SPILL_LV 99
-#endif
-// The fused kernels for 1024-element chunks sit just above 128 VGPRs; at least 4 waves
-// per SIMD (<= 128 VGPRs) is worth the compiler's effort there.
-#if defined(WALK_MODE) && WALK_MODE == 1 && defined(WALK_LV) && WALK_LV >= WALK_SPILL_LV
-// deep tries: 8 VGPRs per register frame on top of the epilogue - three waves per SIMD
-// (<= 168 VGPRs) hold them without scratch
-#define WALK_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(3)))
-#elif defined(WALK_MODE) && WALK_MODE == 1
-#define WALK_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(4)))
-#else
-#define WALK_KERNEL_ATTR
-#endif
-
 template <class C>
-__global__ __launch_bounds__(kWalkThreads) WALK_KERNEL_ATTR void iss_walk_kernel(const IssArgs a) {
+__global__ __launch_bounds__(kWalkThreads) void iss_walk_kernel(const IssArgs a) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x;
   WalkCtx cx;

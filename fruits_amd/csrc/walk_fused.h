@@ -18,8 +18,9 @@
 //     total straight from the scan register (no readlane / broadcast);
 //   * feature ops carry host-resolved flags (whole series, one-sided band), the epilogue
 //     takes the short path for them;
-//   * features accumulate in the LDS window of walk_device.h (feat_flush) and leave with
-//     plain stores; a slot's column follows from the walk order (GroupedProgram::slot_rows).
+//   * the feature ops are walk_device.h's one evaluator (fop, with WindowEpilogue below): features
+//     accumulate in the LDS window (feat_flush) and leave with plain stores; a slot's column
+//     follows from the walk order (GroupedProgram::slot_rows).
 // Results are bit-identical to the interpreter's (same association everywhere).
 //
 // What a kernel of this file knows at compile time is a template parameter:
@@ -37,60 +38,10 @@
 
 namespace fr {
 
-// feature-op flags (FeatOp::kind_inc), resolved by the host (capi_pipeline.cpp, fr_pipeline_set_quantiles)
-constexpr int32_t OPF_SERIES_CUTS = 1 << 16;
-// bits 20-22: the op's SHAPE when it is one of the common ones (0: none of them)
-constexpr int OPF_SHAPE_SHIFT = 20;
-constexpr int OPF_SHAPE_END = 1;     // END at a fixed index (lo)
-constexpr int OPF_SHAPE_BAND1 = 2;   // NPI over the whole series, qlo < v (qhi = +inf); | 1: of the first differences
-constexpr int OPF_SHAPE_BAND2 = 4;   // NPI over the whole series, qlo < v <= qhi;       | 1: of the first differences
-
 // Table reads of the node loop: base pointer + unsigned 32-bit BYTE offset (one scalar load with
 // a register offset; a 64-bit index costs five scalar instructions of address arithmetic).
 __device__ __forceinline__ cptr<int32_t> at_offset(const void *base, uint32_t off) {
   return (cptr<int32_t>)((cptr<char>)(base) + off);
-}
-
-// Single-lane LDS operations of a whole wave in uniform control flow (EXEC all ones before and
-// after): the lane is selected by writing EXEC, not by a compare + saved mask + branch - two
-// scalar instructions, no mask registers kept alive.  `off` is an LDS BYTE address.
-__device__ __forceinline__ void lds_store_lane63(int off, double v) {
-  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_write_b64 %0, %1\n\ts_mov_b64 exec, -1"
-               :: "v"(off), "v"(v) : "memory", "scc");   // (s_lshl_b64 writes SCC)
-}
-__device__ __forceinline__ void lds_store_lane(int lane, int off, double v) {
-  asm volatile("s_lshl_b64 exec, 1, %2\n\tds_write_b64 %0, %1\n\ts_mov_b64 exec, -1"
-               :: "v"(off), "v"(v), "s"(__builtin_amdgcn_readfirstlane(lane)) : "memory", "scc");
-}
-__device__ __forceinline__ void lds_store_lane0_i32(int off, int v) {
-  asm volatile("s_mov_b64 exec, 1\n\tds_write_b32 %0, %1\n\ts_mov_b64 exec, -1"
-               :: "v"(off), "v"(v) : "memory");
-}
-__device__ __forceinline__ void lds_add_lane0(int off, double v) {
-  asm volatile("s_mov_b64 exec, 1\n\tds_add_f64 %0, %1\n\ts_mov_b64 exec, -1"
-               :: "v"(off), "v"(v) : "memory");
-}
-__device__ __forceinline__ void lds_add_lane63(int off, double v) {
-  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_add_f64 %0, %1\n\ts_mov_b64 exec, -1"
-               :: "v"(off), "v"(v) : "memory", "scc");
-}
-__device__ __forceinline__ void lds_add2_lane63(int off0, double v0, int off1, double v1) {
-  asm volatile("s_lshl_b64 exec, 1, 63\n\tds_add_f64 %0, %1\n\tds_add_f64 %2, %3\n\ts_mov_b64 exec, -1"
-               :: "v"(off0), "v"(v0), "v"(off1), "v"(v1) : "memory", "scc");
-}
-__device__ __forceinline__ int lds_offset(const void __attribute__((address_space(3))) *p) {
-  return (int)(unsigned)(__UINTPTR_TYPE__)p;
-}
-
-// The kernel arguments as seen from code that rarely runs (flushes, reciprocal factors, further
-// output rows, per-series cuts): read through a pointer the optimiser cannot look through, so
-// that they are loaded where they are used instead of being hoisted out of the node loop into
-// scalar registers - there are only 102 of those, and the hot path needs them.
-// (The kernel's only argument is the IssArgs struct: it starts the kernel-argument segment.)
-__device__ __forceinline__ cptr<IssArgs> cold_args() {
-  cptr<IssArgs> ap = (cptr<IssArgs>)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(ap));
-  return ap;
 }
 
 __device__ __forceinline__ const void *uniform_ptr(const void *p) {
@@ -226,7 +177,7 @@ __device__ __forceinline__ void fscan_pieces(WalkCtx &cx, const double (&s)[C::E
 // WINDOW = false: the identity slots hold another semiring's zero (the plain sums of a max-plus
 // plan's cumulated rows, inc < 0) - select instead.
 // `carry_wr`: the slot the advanced chunk carry goes to (default: the one it was read from; the
-// cumulations of the epilogue keep two buffers, see fop).
+// cumulations of the epilogue keep two buffers, see WindowEpilogue).
 template <class C, bool WINDOW = true>
 __device__ __forceinline__ void fscan(WalkCtx &cx, const double (&s)[C::EP], double (&c)[C::EP],
                                       double (&x)[C::EP], int carry_slot, int carry_wr = -1) {
@@ -277,260 +228,23 @@ __device__ __forceinline__ void fscan(WalkCtx &cx, const double (&s)[C::EP], dou
   c[E - 1] = semi_add<C::SEMI>(base, incl);
 }
 
-// c[eu] for a uniform eu: a chain of uniform branches (the empty asm keeps the arms apart: as
-// selects, or as an index, the compiler would send the whole array through scratch memory)
-template <int E, int K>
-__device__ __forceinline__ double pick_uniform(int eu, const double (&c)[E]) {
-  if constexpr (K + 1 >= E) {
-    return c[K];
-  } else {
-    double v;
-    if (eu == K) {
-      v = c[K];
-      asm volatile("" : "+v"(v));
-    } else {
-      v = pick_uniform<E, K + 1>(eu, c);
-    }
-    return v;
+// The epilogue policy of the fused walk (EPI of fop, walk_device.h): a cumulation is an fscan; on
+// series of several chunks (WalkCfg::HIGHORD) the j-th cumulation of an op carries its running sum
+// in a slot pair of its own behind the differencing orders' (kCumCarryBase + 2 j): this chunk reads
+// buffer `parity` and writes the other, so several sieves of a node read the same old value.  The
+// CPV exchange carries in the node's LAST slot (IssArgs::carry_per_node - 1).  The shapes the host
+// flags take their short paths here.
+struct WindowEpilogue {
+  template <class CR>
+  static __device__ __forceinline__ void cumulate(WalkCtx &cx, int j, const double (&d)[CR::EP],
+                                                  double (&cs)[CR::EP]) {
+    double xs[CR::EP];
+    const int at = cx.slot + kCumCarryBase + 2 * j;
+    fscan<CR, false>(cx, d, cs, xs, at + cx.parity, at + (cx.parity ^ 1));
   }
-}
-
-// END at a position the host resolved (no per-series cut): the value at series index `pick`
-template <class C>
-__device__ __forceinline__ void end_pick(WalkCtx &cx, int pick, int slot, const double (&c)[C::EP]) {
-  constexpr int E = C::E;
-  const unsigned rel = (unsigned)(pick - (int)cx.t0);
-  if (rel >= (unsigned)C::CHUNK) return;           // another time chunk's element
-  if ((int)(rel / C::SPAN) != cx.wave) return;     // another wave's
-  // the position is uniform: uniform selects of the register, ONE lane stores
-  const unsigned q = rel % C::SPAN;
-  const double v = pick_uniform<E, 0>((int)(q % E), c);
-  lds_store_lane((int)(q / E), lds_offset(cx.fl_val + slot), v);
-}
-
-// PPV / CPV (fruits/sieving/implicit.py:114-129, 169-190): the indicator is closed BELOW -
-// v >= qlo, or with OPF_SEGMENTS qlo <= v < qhi, a conjunction per element (the thresholds are
-// not sorted: a band with qlo > qhi is empty; a NaN is never in, +inf is in above a finite qlo).
-// PPV counts it; CPV counts its rising edges at t >= 1 - the first difference of the indicator
-// is zero-padded (fruits/cache.py:8-13), a component that starts at t = 0 is not counted.  The
-// indicator at t - 1 is taken from the VALUE the row holds there (c, what MODE 2 stores): the
-// lane's own register, the neighbour lane's, the wave's in front through LDS, and across time
-// chunks the node's LAST carry slot (IssArgs::carry_per_node - 1).  The exchange is made once
-// per node and chunk, whatever the number of CPV ops (FusedScratch, like the first differences
-// of the inc = 2 ops), so one slot does.  Counts are integers, one LDS add per wave like NPI's;
-// implicit_finalize_kernel divides them.
-template <class C>
-__device__ __forceinline__ void fop_implicit(WalkCtx &cx, const int32_t *w, int slot,
-                                             const double (&c)[C::EP], FusedScratch<C::EP> &sc) {
-  constexpr int E = C::E;
-  static_assert(C::P == 1, "one piece per wave");
-  const bool cpv = (w[0] & 0xff) == FR_SIEVE_CPV_K, seg = (w[0] & OPF_SEGMENTS) != 0;
-  int hi = w[3];   // T, or the slot of the series' own length
-  if ((w[0] & OPF_SERIES_CUTS) != 0) {
-    cptr<IssArgs> ca = cold_args();
-    hi = as_const(ca->series_cuts + cx.series * ca->cut_slots)[w[3]];
-  }
-  const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
-  if (cpv && !sc.have_cp) {
-    int at = 0;
-    if constexpr (C::MULTI != 0) at = cold_args()->carry_per_node - 1;
-    prev_first_differences<C>(cx, c, sc.cp, at);   // cp[t] = c[t - 1]
-    sc.have_cp = true;
-  }
-  const int t_first = (int)cx.t0 + cx.wave * C::SPAN + cx.lane * E;
-  int cnt = 0;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int t = t_first + e;
-    const double v = c[e];
-    bool in = seg ? (qlo <= v && v < qhi) : (v >= qlo);
-    if (cpv) {
-      const double u = sc.cp[e];
-      const bool before = seg ? (qlo <= u && u < qhi) : (u >= qlo);
-      in = in && !before && t >= 1;
-    }
-    cnt += __popcll(__ballot(in && t < hi));
-  }
-  lds_add_lane0(lds_offset(cx.fl_val + slot), (double)cnt);
-}
-
-template <class C>
-__device__ __forceinline__ void fop(WalkCtx &cx, const int32_t *w, int slot, const double (&c)[C::EP],
-                                    const double (&x)[C::EP], const double (&s)[C::EP],
-                                    bool seq_steps, FusedScratch<C::EP> &sc) {
-  constexpr int E = C::E;
-  // The shapes the host flags (OPF_SHAPE_*: END at a fixed index; a counting band over the whole
-  // series, of the values or of their first differences, with or without an upper threshold)
-  // are short straight-line paths; everything else takes the general one below.
-  const int shape = (w[0] >> OPF_SHAPE_SHIFT) & 7;
-  if (shape == OPF_SHAPE_END) {
-    end_pick<C>(cx, w[2], slot, c);
-    return;
-  }
-  if (shape != 0 && cx.full_chunk) {
-    const double qlo = bits_to_double(w[4], w[5]);
-    double d[E];
-    if (shape & 1) {   // first differences
-#pragma unroll
-      for (int i = 0; i < E; ++i) {
-        double step = c[i] - x[i];
-        if (C::SEMI == 0 && seq_steps) step = (x[i] + s[i]) - x[i];
-        d[i] = step;
-      }
-      // element 0 of the series: increments are zero-padded there (fruits/cache.py:8-13)
-      d[0] = (cx.first_chunk && cx.wave == 0 && cx.lane == 0) ? 0.0 : d[0];
-    } else {
-#pragma unroll
-      for (int i = 0; i < E; ++i) d[i] = c[i];
-    }
-    int cnt = 0;
-    if (shape >= OPF_SHAPE_BAND2) {
-      const double qhi = bits_to_double(w[6], w[7]);
-#pragma unroll
-      for (int e = 0; e < E; ++e) cnt += __popcll(__ballot(qlo < d[e]) & __ballot(d[e] <= qhi));
-    } else {
-#pragma unroll
-      for (int e = 0; e < E; ++e) cnt += __popcll(__ballot(qlo < d[e]));
-    }
-    lds_add_lane0(lds_offset(cx.fl_val + slot), (double)cnt);
-    return;
-  }
-  const int kind = w[0] & 0xff, inc = (int)(int8_t)((w[0] >> 8) & 0xff);   // inc: signed
-  const bool series_cuts = (w[0] & OPF_SERIES_CUTS) != 0;
-  if (kind == FR_SIEVE_END_K) {
-    int pick = w[2];                    // index of the value to pick
-    if (series_cuts) {                  // X[:, cut - 1], index -1 wrapping like numpy
-      cptr<IssArgs> ca = cold_args();
-      pick = as_const(ca->series_cuts + cx.series * ca->cut_slots)[w[2]] - 1;
-      if (pick < 0) pick += (int)ca->T;
-    }
-    end_pick<C>(cx, pick, slot, c);
-    return;
-  }
-  if (kind == FR_SIEVE_PPV_K || kind == FR_SIEVE_CPV_K) {
-    if constexpr (C::MODE == 1) fop_implicit<C>(cx, w, slot, c, sc);
-    return;
-  }
-  int lo = w[2], hi = w[3];
-  if (series_cuts) {
-    cptr<IssArgs> ca = cold_args();
-    cptr<int32_t> cut_row = as_const(ca->series_cuts + cx.series * ca->cut_slots);
-    lo = cut_row[w[2]];
-    hi = cut_row[w[3]];
-  }
-  const double qlo = bits_to_double(w[4], w[5]), qhi = bits_to_double(w[6], w[7]);
-  // element 0 of the series: increments are zero-padded there (fruits/cache.py:8-13)
-  const bool at0 = cx.first_chunk && cx.wave == 0 && cx.lane == 0;
-  double d[E];
-  if (inc <= 0) {
-#pragma unroll
-    for (int i = 0; i < E; ++i) d[i] = c[i];
-    if constexpr (C::MULTI == 0 || C::HIGHORD) {
-      // inc < 0: the row cumulated -inc times (np.cumsum, fruits/sieving/increment.py:68-70) -
-      // a plain sum whatever the semiring of the plan.  On series of several chunks
-      // (WalkCfg::HIGHORD) the j-th cumulation carries its running sum in a slot pair of its
-      // own behind the differencing orders' (kCumCarryBase + 2 (j - 1)): this chunk reads buffer
-      // `parity` and writes the other, so several sieves of a node read the same old value
-      using CR = WalkCfg<C::E, C::P, C::MAXLV, C::MULTI, C::VEC, C::WEIGHTED, C::TEAM, C::MODE, 0>;
-      for (int k = inc; k < 0; ++k) {
-        double cs[E], xs[E];
-        const int at = cx.slot + kCumCarryBase + 2 * (k - inc);
-        fscan<CR, false>(cx, d, cs, xs, at + cx.parity, at + (cx.parity ^ 1));
-#pragma unroll
-        for (int i = 0; i < E; ++i) d[i] = cs[i];
-      }
-    }
-  } else {
-    // Reals: fl(x + s) - x, the step a SEQUENTIAL cumsum takes from the same prefix (see
-    // fused_op in walk_device.h)
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-      double step = c[i] - x[i];
-      if (C::SEMI == 0 && seq_steps) step = (x[i] + s[i]) - x[i];
-      d[i] = step;
-    }
-    d[0] = at0 ? 0.0 : d[0];
-    if (inc >= 2) {
-      if (!sc.have_dp) {
-        prev_first_differences<C>(cx, d, sc.dp);
-        sc.have_dp = true;
-      }
-#pragma unroll
-      for (int e = 0; e < E; ++e) d[e] = d[e] - sc.dp[e];
-      d[0] = at0 ? 0.0 : d[0];
-      // third to eighth differences: one more neighbour exchange per order; on series of several
-      // chunks (WalkCfg::HIGHORD) every order carries its last value of the chunk in a slot pair
-      // of its own (IssArgs::carry_per_node = 3 + 2 * (highest order - 2))
-      if constexpr (C::MULTI == 0 || C::HIGHORD) {
-        for (int k = 3; k <= inc; ++k) {
-          double dq[E];
-          prev_first_differences<C>(cx, d, dq, 3 + 2 * (k - 3), C::MULTI != 0);
-#pragma unroll
-          for (int e = 0; e < E; ++e) d[e] = d[e] - dq[e];
-          d[0] = at0 ? 0.0 : d[0];
-        }
-      }
-    }
-  }
-  const int t_first = (int)cx.t0 + cx.wave * C::SPAN + cx.lane * E;
-  if (kind == FR_SIEVE_MAX_K || kind == FR_SIEVE_MIN_K) {
-    // the largest band key of the wave (walk_types.h), one ds_max_u64; the flush combines a
-    // window's keys with the row's by maximum (walk_device.h, feat_flush)
-    uint64_t key = 0;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int t = t_first + e;
-      const double v = d[e];
-      const uint64_t kv = band_key(v, kind == FR_SIEVE_MIN_K);
-      if (t >= lo && t < hi && qlo < v && v <= qhi && kv > key) key = kv;
-    }
-    key = wave_max_u64(key);
-    if (cx.lane == 0) lds_max_u64(cx.fl_val + slot, key);
-    return;
-  }
-  if (kind == FR_SIEVE_CUR_K) {
-    // CUR (fruits/sieving/segment.py:228-272): the sum of the squares inside the band.  No
-    // population and nothing to divide: the partial sums of the waves - and, through the flush,
-    // of the time chunks - add up in fl_val like NPI's counts
-    double sum = 0.0;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-      const int t = t_first + e;
-      const double v = d[e];
-      const bool in = t >= lo && t < hi && qlo < v && v <= qhi;
-      sum += in ? v * v : 0.0;
-    }
-    sum = wave_inclusive_scan<0>(sum);  // lane 63 holds the wave total
-    lds_add_lane63(lds_offset(cx.fl_val + slot), sum);
-    return;
-  }
-  // XPI: MPI of the positions relative to the segment start (integer sums: exact in any order)
-  const bool xpi = kind == FR_SIEVE_XPI_K;
-  const bool mpi = kind == FR_SIEVE_MPI_K || xpi;
-  int cnt = 0;
-  double sum = 0.0;
-#pragma unroll
-  for (int e = 0; e < E; ++e) {
-    const int t = t_first + e;
-    const double v = d[e];
-    const bool in_t = t >= lo && t < hi;
-    if (mpi) {
-      const bool in = in_t && qlo < v && v <= qhi;
-      cnt += __popcll(__ballot(in));
-      sum += in ? (xpi ? (double)(t - lo) : v) : 0.0;
-    } else {
-      // (the AND of the compare masks: as one predicate it goes through a vector register)
-      cnt += __popcll(__ballot(in_t) & __ballot(qlo < v) & __ballot(v <= qhi));
-    }
-  }
-  // one LDS add per wave (ds_add_f64, nothing returned)
-  if (mpi) {
-    sum = wave_inclusive_scan<0>(sum);  // lane 63 holds the wave total
-    lds_add2_lane63(lds_offset(cx.fl_val + slot), sum, lds_offset(cx.fl_cnt + slot), (double)cnt);
-  } else {
-    lds_add_lane0(lds_offset(cx.fl_val + slot), (double)cnt);
-  }
-}
+  static constexpr bool short_paths = true;
+  static __device__ __forceinline__ int cpv_slot() { return cold_args()->carry_per_node - 1; }
+};
 
 // one feature op (32 bytes = one s_load_dwordx8)
 struct Op1 {
@@ -583,7 +297,7 @@ __device__ __forceinline__ void freserve(WalkCtx &cx, int need) {
     cx.fslot = cx.fused_used;
     cx.fused_used += need;
   } else {
-    feat_reserve<C, true>(cx, need);
+    feat_reserve<C>(cx, need);
   }
 }
 
@@ -594,7 +308,7 @@ __device__ __forceinline__ void fops_static(WalkCtx &cx, const Hot &a, uint32_t 
   if constexpr (I < OPS::n) {
     const Op1 o = load_op1(a, op_off + 32u * (uint32_t)I);   // (column and thresholds: the row's own)
     const int32_t w[8] = {OPS::w0[I], o.w[1], OPS::lo[I], OPS::hi[I], o.w[4], o.w[5], o.w[6], o.w[7]};
-    fop<C>(cx, w, slot + I, c, x, s, SEQ, sc);
+    fop<C, WindowEpilogue, const int32_t *>(cx, w, slot + I, c, x, s, SEQ, sc);
     fops_static<C, OPS, SEQ, I + 1>(cx, a, op_off, slot, c, x, s, sc);
   }
 }
@@ -614,7 +328,7 @@ __device__ __forceinline__ void fops_all(WalkCtx &cx, const Hot &a, int ne, uint
     } else {
       for (int i = 0; i < n; ++i) {
         const Op1 o = load_op1(a, op_off + 32u * (uint32_t)i);
-        fop<C>(cx, o.w, slot + i, c, x, s, SEQ, sc);
+        fop<C, WindowEpilogue, const int32_t *>(cx, o.w, slot + i, c, x, s, SEQ, sc);
       }
     }
     if (++j >= ne) break;
@@ -1207,7 +921,7 @@ __device__ __forceinline__ void stage_chunk(const WalkCtx &cx, const IssArgs &a,
 }
 
 // LDS of the fused kernel: rows [R][CHUNK] | totals window [2][8] | tails [2][4] | carries
-// [carry_slots] (MULTI) | feature window (values, populations, columns)
+// [carry_slots] (MULTI) | feature window (values, populations)
 // (No waves-per-SIMD attribute: every instance fits 128 VGPRs - four waves - without one, and
 // with it the 8-level one-chunk instances spilled a few registers for nothing.)
 template <class C, bool TOTAL, class OPS = DynOps, class PG = NoProg>
@@ -1234,7 +948,6 @@ __global__ __launch_bounds__(kWalkThreads) void iss_fused_kernel(const IssArgs a
     double *fw = cx.carry + (C::MULTI == 1 ? a.carry_slots : 0);
     cx.fl_val = (lds_f64 *)fw;
     cx.fl_cnt = (lds_f64 *)(fw + a.feat_window);
-    cx.fl_col = nullptr;   // (columns follow from the walk order: feat_flush<C, true>)
     for (int sl = tid; sl < a.feat_window; sl += kWalkThreads) {
       cx.fl_val[sl] = 0.0;
       if (a.has_mpi) cx.fl_cnt[sl] = 0.0;
@@ -1289,7 +1002,7 @@ __global__ __launch_bounds__(kWalkThreads) void iss_fused_kernel(const IssArgs a
       }
       // a unit whose features fit the window keeps them there over its time chunks; else every
       // chunk leaves its share (added onto the earlier chunks' in global memory)
-      if (!a.feat_fits || chunk + 1 == a.nchunks) feat_flush<C, true>(cx, !a.feat_fits && chunk > 0);
+      if (!a.feat_fits || chunk + 1 == a.nchunks) feat_flush<C>(cx, !a.feat_fits && chunk > 0);
     }
   }
   if (sink == 0x7fffffff) (C::MODE == 2 ? a.out : a.feats)[0] = 0.0;   // (keeps the cache-touching loads alive)

@@ -27,23 +27,24 @@ static hipError_t inst_p(const IssArgs &a, hipStream_t st) {
   return a.nchunks > 1 ? inst_f<E, 1>(a, st) : inst_f<E, 0>(a, st);
 }
 #else
+static_assert(WALK_MODE == 0, "the materialising interpreter");
 template <int P, int MULTI, bool VEC>
 static hipError_t inst_w(const IssArgs &a, hipStream_t st) {
   constexpr int E = 2, PP = P;
   if (a.semiring == kSemiArctic)
-    return a.aux ? launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, true, 4, WALK_MODE, 1>(a, st)
-                 : launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 4, WALK_MODE, 1>(a, st);
+    return a.aux ? launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, true, 1>(a, st)
+                 : launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 1>(a, st);
   if (a.semiring == kSemiBayesian)
-    return a.aux ? launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, true, 4, WALK_MODE, 2>(a, st)
-                 : launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 4, WALK_MODE, 2>(a, st);
+    return a.aux ? launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, true, 2>(a, st)
+                 : launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 2>(a, st);
   // unweighted Reals, one aligned chunk, one group per series on a cache-sized batch: the
   // input is staged with non-temporal loads (capi_walk.cpp sets nt_input)
   if constexpr (MULTI == 0 && VEC) {
     if (a.nt_input && !a.aux)
-      return launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 4, WALK_MODE, 0, true>(a, st);
+      return launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 0, true>(a, st);
   }
-  return a.aux ? launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, true, 4, WALK_MODE>(a, st)
-               : launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false, 4, WALK_MODE>(a, st);
+  return a.aux ? launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, true>(a, st)
+               : launch_walk_cfg<E, PP, WALK_LV, MULTI, VEC, false>(a, st);
 }
 template <int P>
 static hipError_t inst_p(const IssArgs &a, hipStream_t st) {

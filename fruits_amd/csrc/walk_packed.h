@@ -6,7 +6,8 @@
 // group) unit alone - TEAM = 1 of WalkCfg: the scan is wave-local (DPP only, no
 // barrier, no LDS exchange) and a lane stages exactly the row elements it reads
 // back, so the four waves of a workgroup never synchronise.  Same records, same
-// walk / emit / fused-sieve code as the cooperative kernel.
+// walk / emit code as the interpreter, the fused walk's sieve epilogue (fop, walk_device.h) with
+// the series' feature row as its sink.
 #pragma once
 #include "walk.h"
 
@@ -35,6 +36,7 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_packed_kernel(const Iss
   cx.first_chunk = true;
   cx.full_chunk = C::CHUNK <= a.T;
   cx.slot = 0;
+  cx.fslot = 0;
   const int64_t units = a.N * a.G;
   for (int64_t u = packed_first_unit(blockIdx.x, C::TEAMS, cx.team); u < units;
        u += packed_unit_stride(gridDim.x, C::TEAMS)) {
@@ -47,7 +49,6 @@ __global__ __launch_bounds__(kWalkThreads) void iss_walk_packed_kernel(const Iss
     if constexpr (C::MODE == 1) {
       cx.feat_row = a.feats + n * a.feat_stride;
       cx.cnt_row = a.cnt + n * a.feat_stride;
-      cx.cut_row = a.series_cuts ? a.series_cuts + n * a.cut_slots : nullptr;
       cx.series = n;
     }
     // stage: lane l keeps elements [h*128 + 2l, +2) of every row - the ones read_row

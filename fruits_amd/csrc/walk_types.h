@@ -84,9 +84,9 @@ constexpr int kPieceUnitNodes = 160;
 constexpr int kWalkThreads = 256;
 
 // LDS bytes of a feature window of `slots` slots (8-byte value, 8-byte population with MPI
-// sieves, 4-byte column - not in the fused walk, whose columns follow from the walk order; slots even)
-constexpr uint64_t feat_window_bytes(int slots, bool mpi, bool cols = true) {
-  return (uint64_t)slots * ((mpi ? 16u : 8u) + (cols ? 4u : 0u));
+// sieves; a slot's column follows from the walk order)
+constexpr uint64_t feat_window_bytes(int slots, bool mpi) {
+  return (uint64_t)slots * (mpi ? 16u : 8u);
 }
 
 constexpr int FR_SIEVE_NPI_K = 0;
@@ -183,7 +183,7 @@ struct IssArgs {
   int64_t feat_stride;
   int32_t n_ops, n_ops_padded;
   // LDS feature window of the cooperative kernels (walk_device.h, feat_flush): slots of
-  // {value, population (has_mpi), column}; feat_fits: every group's features fit the window,
+  // {value, population (has_mpi)}; feat_fits: every group's features fit the window,
   // so a unit flushes once, after its last time chunk
   int32_t feat_window, feat_fits, has_mpi;
   // per-series segment boundaries (coquantile cuts, fruits/sieving/segment.py:51-64): (N,
