@@ -30,9 +30,17 @@
 //                                                  fr_pipeline_prepare): the sieves as immediates
 //   iss_fused_kernel<C, TOTAL, JitOps, JitPlan>    ... and the plan (fr_pipeline_compile_plan): a
 //                                                  small one as straight-line code (fwalk_static),
-//                                                  of a large one the node shapes (fwalk_shaped)
+//                                                  a large one in pieces (fwalk_pieces), or of a
+//                                                  large one the node shapes (fwalk_shaped)
 // and C::MODE == 2 is the same node loop with a store epilogue: the lean MATERIALISING walk of the
 // plans that have no static program of walk_device.h's kind (emit_lean, two pieces per wave).
+//
+// All of them evaluate a node in ONE function, fnode_body, over a node DESCRIPTOR that says which
+// fields of the record the kernel knows: RecNode (none: the record is loaded and decoded),
+// ShapeNode (level, flags, output-row count), StaticNode (all of it).  The four drivers differ in
+// how they step: fwalk (record loop), fwalk_shaped (shape-indexed loop), fwalk_static (template
+// recursion over the records), fwalk_pieces (the items of a piece type: a chain by the record
+// loop, a body by the recursion).
 #pragma once
 #include "walk_device.h"
 
@@ -65,8 +73,6 @@ struct Rec8 {
   __device__ __forceinline__ int level() const { return w[0] & 0xff; }
   __device__ __forceinline__ int flags() const { return w[0] >> 8; }
   __device__ __forceinline__ int fac_count() const { return w[1] & 0xffff; }
-  __device__ __forceinline__ int z_mul() const { return ((w[1] >> 16) & 0xff) - 1; }
-  __device__ __forceinline__ int emit_mul() const { return ((w[1] >> 24) & 0xff) - 1; }
   __device__ __forceinline__ int emit_count() const { return w[6]; }
 };
 
@@ -301,6 +307,13 @@ __device__ __forceinline__ void freserve(WalkCtx &cx, int need) {
   }
 }
 
+// The j-th output row of a node, j >= 1 (the first is w[7] of its record): the second is inline in
+// the record, further ones - SINGLE-mode plans with repeated words - come from the emit-row table.
+__device__ __forceinline__ int emit_row(const Hot &a, uint32_t rec_off, int j) {
+  return j == 1 ? rec_field(a.recs, rec_off, 8)
+                : as_const(cold_args()->emit_rows)[rec_field(a.recs, rec_off, 13) + j];
+}
+
 template <class C, class OPS, bool SEQ, int I>
 __device__ __forceinline__ void fops_static(WalkCtx &cx, const Hot &a, uint32_t op_off, int slot,
                                             const double (&c)[C::EP], const double (&x)[C::EP],
@@ -333,9 +346,7 @@ __device__ __forceinline__ void fops_all(WalkCtx &cx, const Hot &a, int ne, uint
     }
     if (++j >= ne) break;
     slot += n;
-    const int k = j == 1 ? rec_field(a.recs, rec_off, 8)
-                         : as_const(cold_args()->emit_rows)[rec_field(a.recs, rec_off, 13) + j];
-    op_off = a.op_base + (uint32_t)k * a.op_row_bytes;
+    op_off = a.op_base + (uint32_t)emit_row(a, rec_off, j) * a.op_row_bytes;
   }
 }
 
@@ -368,27 +379,54 @@ __device__ __forceinline__ void emit_lean(const WalkCtx &cx, const Hot &a, int n
         }
     }
     if (++j >= ne) break;
-    k = j == 1 ? rec_field(a.recs, rec_off, 8)
-               : as_const(cold_args()->emit_rows)[rec_field(a.recs, rec_off, 13) + j];
+    k = emit_row(a, rec_off, j);
   }
 }
 
 // Register frames: f[k] holds the prefix the children of the open node of level k continue
-// from.  They are only ever indexed by compile-time constants: a node's level selects a case
-// through a chain of single-bit tests of 1 << level, deepest level first (that is where most
-// nodes are; as a chain of equality tests the compiler builds a balanced switch with flag
-// variables out of it).  Case K < 0 is the semiring's one (a first letter).
+// from.  They are only ever indexed by compile-time constants (the *_at functions; K < 0 is the
+// semiring's one: a first letter).
+template <class C>
+__device__ __forceinline__ void semiring_one(double (&s)[C::EP]) {
+#pragma unroll   // (identity of the semiring's product: 1 (Reals, Bayesian), 0 (Arctic))
+  for (int i = 0; i < C::EP; ++i) s[i] = C::SEMI != 1 ? 1.0 : 0.0;
+}
+template <class C, int K>
+__device__ __forceinline__ void frame_get_at(const double (&f)[C::MAXLV][C::EP], double (&s)[C::EP]) {
+  if constexpr (K < 0) {
+    semiring_one<C>(s);
+  } else {
+#pragma unroll
+    for (int i = 0; i < C::EP; ++i) s[i] = f[K][i];
+  }
+}
+template <class C, int K>
+__device__ __forceinline__ void frame_mul_at(const WalkCtx &cx, int code, const double (&f)[C::MAXLV][C::EP],
+                                             double (&s)[C::EP]) {
+  if constexpr (K < 0) {
+    double ones[C::EP];
+    semiring_one<C>(ones);
+    mul_row_from<C>(cx, code, ones, s);
+  } else {
+    mul_row_from<C>(cx, code, f[K], s);
+  }
+}
+template <class C, int K>
+__device__ __forceinline__ void frame_put_at(double (&f)[C::MAXLV][C::EP], const double (&x)[C::EP]) {
+#pragma unroll
+  for (int i = 0; i < C::EP; ++i) f[K][i] = x[i];
+}
+// A node's level as a run-time value selects a case through a chain of single-bit tests of
+// 1 << level, deepest level first (that is where most nodes are; as a chain of equality tests the
+// compiler builds a balanced switch with flag variables out of it).
 template <class C, int K>
 __device__ __forceinline__ void frame_mul(const WalkCtx &cx, unsigned rd_bit, int code,
                                           const double (&f)[C::MAXLV][C::EP], double (&s)[C::EP]) {
   if constexpr (K < 0) {
-    double ones[C::EP];  // identity of the semiring's product: 1 (Reals, Bayesian), 0 (Arctic)
-#pragma unroll
-    for (int i = 0; i < C::EP; ++i) ones[i] = C::SEMI != 1 ? 1.0 : 0.0;
-    mul_row_from<C>(cx, code, ones, s);
+    frame_mul_at<C, -1>(cx, code, f, s);
   } else {
     if (rd_bit & (2u << K)) {
-      mul_row_from<C>(cx, code, f[K], s);
+      frame_mul_at<C, K>(cx, code, f, s);
       asm volatile("" ::: "memory");  // (keeps the cases apart: merged, they cost selects)
     } else {
       frame_mul<C, K - 1>(cx, rd_bit, code, f, s);
@@ -399,12 +437,10 @@ template <class C, int K>
 __device__ __forceinline__ void frame_get(unsigned rd_bit, const double (&f)[C::MAXLV][C::EP],
                                           double (&s)[C::EP]) {
   if constexpr (K < 0) {
-#pragma unroll
-    for (int i = 0; i < C::EP; ++i) s[i] = C::SEMI != 1 ? 1.0 : 0.0;
+    frame_get_at<C, -1>(f, s);
   } else {
     if (rd_bit & (2u << K)) {
-#pragma unroll
-      for (int i = 0; i < C::EP; ++i) s[i] = f[K][i];
+      frame_get_at<C, K>(f, s);
       asm volatile("" ::: "memory");
     } else {
       frame_get<C, K - 1>(rd_bit, f, s);
@@ -416,8 +452,7 @@ __device__ __forceinline__ void frame_put(unsigned lv_bit, double (&f)[C::MAXLV]
                                           const double (&x)[C::EP]) {
   if constexpr (K >= 0) {
     if (lv_bit & (1u << K)) {
-#pragma unroll
-      for (int i = 0; i < C::EP; ++i) f[K][i] = x[i];
+      frame_put_at<C, K>(f, x);
       asm volatile("" ::: "memory");
     } else {
       frame_put<C, K - 1>(lv_bit, f, x);
@@ -425,75 +460,172 @@ __device__ __forceinline__ void frame_put(unsigned lv_bit, double (&f)[C::MAXLV]
   }
 }
 
-// One node of the record loop: the letters into the prefix it continues (the frame of the level
-// below; its own level's for an only child, F_CHAIN), the scan, the feature ops (MODE 2: the
-// stores), the hand-over to the children.  `nd` comes in as the node's record and leaves as the
-// NEXT one (requested behind the first scan: a scalar-cache hit, in flight over the second).
-template <class C, bool TOTAL, class OPS>
-__device__ __forceinline__ void fnode(WalkCtx &cx, const Hot &a, double (&f)[C::MAXLV][C::EP],
-                                      Rec8 &nd, uint32_t me, int slot, int &sink) {
-  constexpr int EP = C::EP;
-  const uint32_t rec_off = me + 64u;
-  const int ne = nd.emit_count();
-  const uint32_t op_off = (uint32_t)nd.w[7] * a.op_row_bytes;
-  // the lines of the next record and of this node's ops, on their way to the scalar cache
+// ---------------------------------------------------------------- node descriptors
+// What the node body (fnode_body below) is told about a node: for every field of the record, its
+// value and whether the kernel knows it at compile time.  `knows_flags`: level and flags are the
+// constants klevel / kflags - the frames are indexed directly, a test of a flag folds away;
+// `knows_record`: so is everything else (knf: the factor count; the other fields are constants
+// behind the same accessors).  Where a field comes from the record the body branches on it
+// (uniform branches) and reaches the frames through the bit tests above.
+//
+// RecNode: a loaded record, nothing known - the generic instances, a pipeline's kernel with the
+// sieves as immediates, the lean materialising walk (MODE 2), the chain in front of a piece.  Only
+// here is there anything to prefetch: the lines of the next record and of the node's ops go to
+// the scalar cache at the start of the node, and `r` leaves the body as the NEXT record (requested
+// behind the first scan: a scalar-cache hit, in flight over the second).
+struct RecNode {
+  static constexpr bool knows_flags = false, knows_record = false;
+  static constexpr int klevel = 0, kflags = 0, knf = 0;
+  Rec8 &r;
+  const uint32_t me;   // byte offset of the record
+  __device__ __forceinline__ int level() const { return r.level(); }
+  __device__ __forceinline__ int flags() const { return r.flags(); }
+  __device__ __forceinline__ int fac_count() const { return r.fac_count(); }
+  __device__ __forceinline__ int fac(int i) const { return r.w[2 + i]; }
+  __device__ __forceinline__ int weights() const { return r.w[1]; }   // z_mul, emit_mul (Rec8)
+  __device__ __forceinline__ int emit_count() const { return r.emit_count(); }
+  __device__ __forceinline__ int first_row() const { return r.w[7]; }
+  __device__ __forceinline__ int fac_begin(const Hot &a) const { return rec_field(a.recs, me, 12); }
+  __device__ __forceinline__ int touch_next(const Hot &a) const { return touch(a.recs, me + 64u); }
   // (a node without output rows names row 0: a harmless touch)
-  const int t_rec = touch(a.recs, rec_off);
+  __device__ __forceinline__ int touch_ops(const Hot &a, uint32_t op_off) const { return touch(a.ops, op_off); }
+  __device__ __forceinline__ void advance(const Hot &a, int touched, int &sink) const {
+    sink += touched;
+    r = load_rec8(a.recs, me + 64u);
+  }
+};
+
+// ShapeNode: a run-time compiled kernel of a LARGE plan that is not cut into pieces knows the
+// plan's node SHAPES - level, flags, output rows (GroupedProgram::shapes, the most frequent
+// first); the rows, weights and offsets still come from the record.
+template <class SH, int I>
+struct SShape {
+  static constexpr int d = SH::desc[I];
+  static constexpr int level = d & 0xff, flags = (d >> 8) & 0xff;
+  static constexpr int ne = (d >> 20) & 0xf;   // output rows; 3: more than two (read from the record)
+};
+template <class SH, int I>
+struct ShapeNode : RecNode {
+  using S = SShape<SH, I>;
+  static constexpr bool knows_flags = true;
+  static constexpr int klevel = S::level, kflags = S::flags;
+  __device__ __forceinline__ ShapeNode(Rec8 &r, uint32_t me) : RecNode{r, me} {}
+  __device__ __forceinline__ int emit_count() const { return S::ne < 3 ? S::ne : r.emit_count(); }
+};
+
+// StaticNode: a run-time compiled kernel may also know the PLAN (jit.cpp: a pipeline of at most
+// kFusedStaticMaxNodes nodes, or one piece type of a larger one): PG::w holds the records, 16
+// words per record like NodeRec.  Record PC is then a constant in every field: nothing is loaded,
+// touched or decoded.
+struct NoProg {
+  static constexpr bool is_static = false, is_shaped = false, is_piece = false;
+};
+template <class PG, int PC>
+struct StaticNode {
+  static constexpr int w(int i) { return PG::w[PC * 16 + i]; }
+  static constexpr bool knows_flags = true, knows_record = true;
+  static constexpr int klevel = PG::w[PC * 16] & 0xff, kflags = PG::w[PC * 16] >> 8;
+  static constexpr int knf = PG::w[PC * 16 + 1] & 0xffff;
+  static constexpr uint32_t me = (uint32_t)PC * 64u;
+  static constexpr int level() { return klevel; }
+  static constexpr int flags() { return kflags; }
+  static constexpr int fac_count() { return knf; }
+  static constexpr int fac(int i) { return w(2 + i); }
+  static constexpr int weights() { return w(1); }
+  static constexpr int emit_count() { return w(6); }
+  static constexpr int first_row() { return w(7); }
+  static constexpr int fac_begin(const Hot &) { return w(12); }
+  static constexpr int touch_next(const Hot &) { return 0; }
+  static constexpr int touch_ops(const Hot &, uint32_t) { return 0; }
+  static __device__ __forceinline__ void advance(const Hot &, int, int &) {}
+};
+
+// the children's prefix into the node's own frame
+template <class C, class ND>
+__device__ __forceinline__ void hand_over(unsigned lv_bit, double (&f)[C::MAXLV][C::EP],
+                                          const double (&p)[C::EP]) {
+  if constexpr (ND::knows_flags) frame_put_at<C, ND::klevel>(f, p);
+  else frame_put<C, C::MAXLV - 1>(lv_bit, f, p);
+}
+
+// One node: the letters into the prefix it continues (the frame of the level below; its own
+// level's for an only child, F_CHAIN; the semiring's one at level 0), the scan, the hand-over to
+// the children, the feature ops (MODE 2: the stores) and, under a non-total weighting, the second
+// scan.  The ONE place where the walk's node semantics are written: what a kernel knows of the node
+// is the descriptor's (above), how it steps to the next the driver's (below).
+//
+// The tests of the node's fields are plain `if`s.  On a RecNode they are the uniform branches of
+// the record loop.  On a field the descriptor knows, the condition is an integral constant
+// expression and the compiler's front end emits no code for the arm not taken (nor does the
+// body call anything that is instantiated per node), so a straight-line kernel pays nothing for
+// the arms its nodes do not take: resources, code size and compile time of the bundled kernels
+// against the earlier `if constexpr` bodies are in DESIGN.md 4.2.  Only the frames need
+// `if constexpr`: their index is a template argument.
+template <class C, bool TOTAL, class OPS, class ND>
+__device__ __forceinline__ void fnode_body(WalkCtx &cx, const Hot &a, double (&f)[C::MAXLV][C::EP],
+                                           ND &nd, int slot, int &sink) {
+  constexpr int EP = C::EP;
+  constexpr bool KF = ND::knows_flags;
+  constexpr int kread = (ND::kflags & F_CHAIN) ? ND::klevel : ND::klevel - 1;   // the level read
+  static_assert(C::MODE == 1 || !KF, "the lean materialising walk (MODE 2) decodes its records");
+  static_assert(!KF || ND::klevel < C::MAXLV, "a node deeper than the kernel's register frames");
+  const uint32_t me = nd.me;
+  // (known fields by their static names: integral constants to the compiler's front end)
+  const int flags = KF ? ND::kflags : nd.flags(), nf = ND::knows_record ? ND::knf : nd.fac_count();
+  const int ne = nd.emit_count(), w1 = nd.weights();
+  const uint32_t op_off = a.op_base + (uint32_t)nd.first_row() * a.op_row_bytes;
+  const int t_rec = nd.touch_next(a);
   int t_ops = 0;
   if constexpr (C::MODE == 1) {
-    t_ops = touch(a.ops, op_off);
-    freserve<C, OPS>(cx, ne * (OPS::is_static ? OPS::n : a.n_ops));
+    // the op line and the window slots of the node's output rows.  The record loop does not look
+    // whether the node has any: it reserves none then.  A node KNOWN to have none skips both (the
+    // earlier straight-line body reserved 0 slots there, which only set cx.fslot - nobody reads it)
+    if (!KF || (flags & F_EMIT)) {
+      t_ops = nd.touch_ops(a, op_off);
+      freserve<C, OPS>(cx, ne * a.n_ops);
+    }
   }
   cx.slot = slot;
-  const int nf = nd.fac_count(), flags = nd.flags(), lv = nd.level();
-  const unsigned lv_bit = 1u << lv;
+  const unsigned lv_bit = 1u << (KF ? ND::klevel : nd.level());
   const unsigned rd_bit = (flags & F_CHAIN) ? (lv_bit << 1) : lv_bit;   // 2 << (level read)
   double s[EP];
   if (flags & F_SLOW) {
     // a reciprocal factor, more than four or none: the factor table, one factor at a time
-    frame_get<C, C::MAXLV - 1>(rd_bit, f, s);
-    slow_factors<C>(cx, rec_field(a.recs, me, 12), nf, s, s, false);
+    if constexpr (KF) frame_get_at<C, kread>(f, s);
+    else frame_get<C, C::MAXLV - 1>(rd_bit, f, s);
+    slow_factors<C>(cx, nd.fac_begin(a), nf, s, s, false);
   } else {
-    frame_mul<C, C::MAXLV - 1>(cx, rd_bit, nd.w[2], f, s);
+    if constexpr (KF) frame_mul_at<C, kread>(cx, nd.fac(0), f, s);
+    else frame_mul<C, C::MAXLV - 1>(cx, rd_bit, nd.fac(0), f, s);
     if (nf > 1) {
-      mul_rowp<C>(cx, nd.w[3], s);
-      if (nf > 2) mul_rowp<C>(cx, nd.w[4], s);
-      if (nf > 3) mul_rowp<C>(cx, nd.w[5], s);
+      mul_rowp<C>(cx, nd.fac(1), s);
+      if (nf > 2) mul_rowp<C>(cx, nd.fac(2), s);
+      if (nf > 3) mul_rowp<C>(cx, nd.fac(3), s);
     }
   }
-  const int w1 = nd.w[1];
   if (flags & F_NEED1) {
     double c[EP], x[EP];
     fscan<C>(cx, s, c, x, slot);
     // Reals: children start from the exclusive shift; Arctic / Bayesian: from the inclusive
     // maximum (taken before the emitted values are rescaled)
-    if ((flags & (F_CHILDREN | F_NEED2)) == F_CHILDREN) {
-      if constexpr (C::SEMI == 0) frame_put<C, C::MAXLV - 1>(lv_bit, f, x);
-      else frame_put<C, C::MAXLV - 1>(lv_bit, f, c);
-    }
+    if ((flags & (F_CHILDREN | F_NEED2)) == F_CHILDREN) hand_over<C, ND>(lv_bit, f, C::SEMI == 0 ? x : c);
     if (flags & F_EMIT) {
-      if constexpr (C::WEIGHTED && TOTAL) {
-        // total weighting: the sieves see c * exp(-g alpha_k) (Arctic: c - g alpha_k)
-        const int emit_mul = ((w1 >> 24) & 0xff) - 1;
-        mul_rowp<C>(cx, C::SEMI != 1 ? emit_mul : fac_arctic(emit_mul, -1), c);
-        if constexpr (C::MODE == 2) {
-          emit_lean<C>(cx, a, ne, nd.w[7], me, c);
-        } else if constexpr (C::TOTALINC) {
-          double xs[EP];
-          previous_weighted<C>(cx, emit_mul, x, xs);
-          fops_all<C, false, OPS>(cx, a, ne, op_off, me, c, xs, s);
-        } else {
-          fops_all<C, false, OPS>(cx, a, ne, op_off, me, c, x, s);
-        }
-      } else if constexpr (C::MODE == 2) {
-        emit_lean<C>(cx, a, ne, nd.w[7], me, c);
+      constexpr bool RESCALED = C::WEIGHTED && TOTAL;
+      [[maybe_unused]] const int emit_mul = ((w1 >> 24) & 0xff) - 1;
+      // total weighting: the sieves see c * exp(-g alpha_k) (Arctic: c - g alpha_k)
+      if constexpr (RESCALED) mul_rowp<C>(cx, C::SEMI != 1 ? emit_mul : fac_arctic(emit_mul, -1), c);
+      if constexpr (C::MODE == 2) {
+        emit_lean<C>(cx, a, ne, nd.first_row(), me, c);
+      } else if constexpr (RESCALED && C::TOTALINC) {
+        double xs[EP];
+        previous_weighted<C>(cx, emit_mul, x, xs);
+        fops_all<C, false, OPS>(cx, a, ne, op_off, me, c, xs, s);
       } else {
-        fops_all<C, true, OPS>(cx, a, ne, op_off, me, c, x, s);
+        fops_all<C, !RESCALED, OPS>(cx, a, ne, op_off, me, c, x, s);
       }
     }
   }
-  sink += t_rec + t_ops;
-  nd = load_rec8(a.recs, rec_off);   // (a scalar-cache hit; in flight over the second scan)
+  nd.advance(a, t_rec + t_ops, sink);
   if constexpr (C::WEIGHTED && !TOTAL) {
     if (flags & F_NEED2) {
       // non-total weighting: the children continue from the scan of s * exp(+g alpha_k)
@@ -501,14 +633,26 @@ __device__ __forceinline__ void fnode(WalkCtx &cx, const Hot &a, double (&f)[C::
       double c2[EP], x2[EP];
       mul_rowp<C>(cx, C::SEMI != 1 ? z_mul : fac_arctic(z_mul, 1), s);
       fscan<C>(cx, s, c2, x2, slot + 1);
-      if constexpr (C::SEMI == 0) frame_put<C, C::MAXLV - 1>(lv_bit, f, x2);
-      else frame_put<C, C::MAXLV - 1>(lv_bit, f, c2);
+      hand_over<C, ND>(lv_bit, f, C::SEMI == 0 ? x2 : c2);
     }
   }
 }
 
-// what the node loop reads of the kernel arguments (see Hot)
-template <class C>
+// ---------------------------------------------------------------- the drivers
+// Every driver begins with the same two lines: the node loop's arguments as scalars (hot_args) and
+// the register frames, zeroed.  The zeroing is a macro and not a function on purpose: the scalar
+// stores have to stand in the driver's own body.  A helper that zeroes the array (or `= {}`) is
+// one store of the whole array by the time it is inlined, and the frames then live as ONE vector
+// of MAXLV x EP doubles (48 more VGPRs in the lean kernels of six levels); frames declared once in
+// the kernel and handed to the drivers cost the piece kernels 14 VGPRs, an occupancy step.
+#define FR_ZEROED_FRAMES(f)                 \
+  double f[C::MAXLV][C::EP];                \
+  _Pragma("unroll") for (int k = 0; k < C::MAXLV; ++k) \
+  _Pragma("unroll") for (int i = 0; i < C::EP; ++i) f[k][i] = 0.0
+
+// What the node loop reads of the kernel arguments (see Hot).  A run-time compiled kernel knows the
+// number of its ops and of a node's carry slots.
+template <class C, class OPS>
 __device__ __forceinline__ Hot hot_args(const WalkCtx &cx) {
   Hot a;
   const IssArgs &ka = *cx.a;
@@ -516,9 +660,15 @@ __device__ __forceinline__ Hot hot_args(const WalkCtx &cx) {
   // that is spilled and restored as a whole)
   a.recs = reinterpret_cast<const NodeRec *>(uniform_ptr(ka.recs));
   a.ops = reinterpret_cast<const FeatOp *>(uniform_ptr(ka.ops));
-  a.n_ops = __builtin_amdgcn_readfirstlane(ka.n_ops);
-  a.op_row_bytes = __builtin_amdgcn_readfirstlane(ka.n_ops_padded * 32);
-  a.cps = C::MULTI != 0 ? __builtin_amdgcn_readfirstlane(ka.carry_per_node) : kCarrySlots;
+  if constexpr (OPS::is_static) {
+    a.n_ops = OPS::n;
+    a.op_row_bytes = (uint32_t)(OPS::n_padded * 32);
+    a.cps = C::MULTI != 0 ? OPS::cps : kCarrySlots;
+  } else {
+    a.n_ops = __builtin_amdgcn_readfirstlane(ka.n_ops);
+    a.op_row_bytes = __builtin_amdgcn_readfirstlane(ka.n_ops_padded * 32);
+    a.cps = C::MULTI != 0 ? __builtin_amdgcn_readfirstlane(ka.carry_per_node) : kCarrySlots;
+  }
   a.op_base = 0;
   a.slot_base = 0;
   if constexpr (C::MODE == 2) {
@@ -529,318 +679,118 @@ __device__ __forceinline__ Hot hot_args(const WalkCtx &cx) {
   return a;
 }
 
-// Walks the records of one group (DFS order, sentinel at the end).
+// The record loop: the records from rec_off on (DFS order) up to the sentinel; `slot`: the carry
+// slots of the node, a.cps per record.
 template <class C, bool TOTAL, class OPS>
-__device__ __forceinline__ void fwalk(WalkCtx &cx, int node_begin, int &sink) {
-  constexpr int EP = C::EP;
-  const Hot a = hot_args<C>(cx);
-  double f[C::MAXLV][EP];
-#pragma unroll
-  for (int k = 0; k < C::MAXLV; ++k)
-#pragma unroll
-    for (int i = 0; i < EP; ++i) f[k][i] = 0.0;
-  uint32_t rec_off = (uint32_t)node_begin * 64u;
-  int slot = 0;   // carry slots of the node: three per record of the group
-  Rec8 nd = load_rec8(a.recs, rec_off);
-  while (nd.level() != kRecSentinelLevel) {
-    fnode<C, TOTAL, OPS>(cx, a, f, nd, rec_off, slot, sink);
+__device__ __forceinline__ void fwalk_records(WalkCtx &cx, const Hot &a, double (&f)[C::MAXLV][C::EP],
+                                              uint32_t &rec_off, int &slot, int &sink) {
+  Rec8 r = load_rec8(a.recs, rec_off);
+  while (r.level() != kRecSentinelLevel) {
+    RecNode nd{r, rec_off};
+    fnode_body<C, TOTAL, OPS>(cx, a, f, nd, slot, sink);
     rec_off += 64u;
     slot += a.cps;
   }
 }
-
-// ---------------------------------------------------------------- node shapes as immediates
-// Between the record loop and a plan that is straight-line code (below): a run-time compiled
-// kernel of a LARGE plan knows the plan's node SHAPES - what the body of a node branches on:
-// level, flags, output rows (GroupedProgram::shapes, the most frequent first).  The loop stays a loop over records, but a node's shape index (one more dword per
-// node, IssArgs::shape_ids) selects a body compiled for that shape: frames indexed directly, no
-// level dispatch, no flag or count tests - the rows, weights and offsets still come from the
-// record.  Shapes beyond the SH::n compiled ones take the generic body.
-template <class SH, int I>
-struct SShape {
-  static constexpr int d = SH::desc[I];
-  static constexpr int level = d & 0xff, flags = (d >> 8) & 0xff;
-  static constexpr int ne = (d >> 20) & 0xf;   // output rows; 3: more than two (read from the record)
-};
-template <class C, bool TOTAL, class OPS, class SH, int I>
-__device__ __forceinline__ void fnode_shaped(WalkCtx &cx, const Hot &a, double (&f)[C::MAXLV][C::EP],
-                                             Rec8 &nd, uint32_t me, int slot, int &sink) {
-  using S = SShape<SH, I>;
-  constexpr int EP = C::EP;
-  static_assert(S::level < C::MAXLV, "a shape deeper than the kernel's register frames");
-  const uint32_t rec_off = me + 64u;
-  const int ne = S::ne < 3 ? S::ne : nd.emit_count();
-  const uint32_t op_off = (uint32_t)nd.w[7] * (uint32_t)(OPS::n_padded * 32);
-  const int t_rec = touch(a.recs, rec_off);
-  int t_ops = 0;
-  if constexpr ((S::flags & F_EMIT) != 0) {
-    t_ops = touch(a.ops, op_off);
-    freserve<C, OPS>(cx, ne * OPS::n);
-  }
-  cx.slot = slot;
-  double s[EP];
-  if constexpr ((S::flags & F_SLOW) != 0) {
-    if constexpr ((S::flags & F_CHAIN) != 0) {
-#pragma unroll
-      for (int i = 0; i < EP; ++i) s[i] = f[S::level][i];
-    } else if constexpr (S::level > 0) {
-#pragma unroll
-      for (int i = 0; i < EP; ++i) s[i] = f[S::level - 1][i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < EP; ++i) s[i] = C::SEMI != 1 ? 1.0 : 0.0;
-    }
-    slow_factors<C>(cx, rec_field(a.recs, me, 12), nd.fac_count(), s, s, false);
-  } else {
-    if constexpr ((S::flags & F_CHAIN) != 0) {
-      mul_row_from<C>(cx, nd.w[2], f[S::level], s);
-    } else if constexpr (S::level > 0) {
-      mul_row_from<C>(cx, nd.w[2], f[S::level - 1], s);
-    } else {
-      double ones[EP];
-#pragma unroll
-      for (int i = 0; i < EP; ++i) ones[i] = C::SEMI != 1 ? 1.0 : 0.0;
-      mul_row_from<C>(cx, nd.w[2], ones, s);
-    }
-    const int nf = nd.fac_count();
-    if (nf > 1) {
-      mul_rowp<C>(cx, nd.w[3], s);
-      if (nf > 2) mul_rowp<C>(cx, nd.w[4], s);
-      if (nf > 3) mul_rowp<C>(cx, nd.w[5], s);
-    }
-  }
-  const int w1 = nd.w[1];
-  if constexpr ((S::flags & F_NEED1) != 0) {
-    double c[EP], x[EP];
-    fscan<C>(cx, s, c, x, slot);
-    if constexpr ((S::flags & (F_CHILDREN | F_NEED2)) == F_CHILDREN) {
-#pragma unroll
-      for (int i = 0; i < EP; ++i) f[S::level][i] = C::SEMI == 0 ? x[i] : c[i];
-    }
-    if constexpr ((S::flags & F_EMIT) != 0) {
-      if constexpr (C::WEIGHTED && TOTAL) {
-        const int emit_mul = ((w1 >> 24) & 0xff) - 1;
-        mul_rowp<C>(cx, C::SEMI != 1 ? emit_mul : fac_arctic(emit_mul, -1), c);
-        if constexpr (C::TOTALINC) {
-          double xs[EP];
-          previous_weighted<C>(cx, emit_mul, x, xs);
-          fops_all<C, false, OPS>(cx, a, ne, op_off, me, c, xs, s);
-        } else {
-          fops_all<C, false, OPS>(cx, a, ne, op_off, me, c, x, s);
-        }
-      } else {
-        fops_all<C, true, OPS>(cx, a, ne, op_off, me, c, x, s);
-      }
-    }
-  }
-  sink += t_rec + t_ops;
-  nd = load_rec8(a.recs, rec_off);
-  if constexpr (C::WEIGHTED && !TOTAL && (S::flags & F_NEED2) != 0) {
-    const int z_mul = ((w1 >> 16) & 0xff) - 1;
-    double c2[EP], x2[EP];
-    mul_rowp<C>(cx, C::SEMI != 1 ? z_mul : fac_arctic(z_mul, 1), s);
-    fscan<C>(cx, s, c2, x2, slot + 1);
-#pragma unroll
-    for (int i = 0; i < EP; ++i) f[S::level][i] = C::SEMI == 0 ? x2[i] : c2[i];
-  }
+// the records of one group
+template <class C, bool TOTAL, class OPS>
+__device__ __forceinline__ void fwalk(WalkCtx &cx, int node_begin, int &sink) {
+  const Hot a = hot_args<C, OPS>(cx);
+  FR_ZEROED_FRAMES(f);
+  uint32_t rec_off = (uint32_t)node_begin * 64u;
+  int slot = 0;
+  fwalk_records<C, TOTAL, OPS>(cx, a, f, rec_off, slot, sink);
 }
-// a chain of uniform tests, the most frequent shape first
+
+// The shape-indexed loop: still a loop over records, but a node's shape index (one more dword per
+// node, IssArgs::shape_ids) selects a body compiled for that shape through a chain of uniform
+// tests, the most frequent shape first.  Shapes beyond the SH::n compiled ones take the record's.
 template <class C, bool TOTAL, class OPS, class SH, int I>
 __device__ __forceinline__ void fnode_by_shape(int shape, WalkCtx &cx, const Hot &a,
-                                               double (&f)[C::MAXLV][C::EP], Rec8 &nd, uint32_t me,
+                                               double (&f)[C::MAXLV][C::EP], Rec8 &r, uint32_t me,
                                                int slot, int &sink) {
   if constexpr (I < SH::n) {
     if (shape == I) {
-      fnode_shaped<C, TOTAL, OPS, SH, I>(cx, a, f, nd, me, slot, sink);
+      ShapeNode<SH, I> nd(r, me);
+      fnode_body<C, TOTAL, OPS>(cx, a, f, nd, slot, sink);
       asm volatile("" ::: "memory");  // (keeps the bodies apart)
     } else {
-      fnode_by_shape<C, TOTAL, OPS, SH, I + 1>(shape, cx, a, f, nd, me, slot, sink);
+      fnode_by_shape<C, TOTAL, OPS, SH, I + 1>(shape, cx, a, f, r, me, slot, sink);
     }
   } else {
-    fnode<C, TOTAL, OPS>(cx, a, f, nd, me, slot, sink);
+    RecNode nd{r, me};
+    fnode_body<C, TOTAL, OPS>(cx, a, f, nd, slot, sink);
   }
 }
 template <class C, bool TOTAL, class OPS, class SH>
 __device__ __forceinline__ void fwalk_shaped(WalkCtx &cx, int node_begin, int &sink) {
-  constexpr int EP = C::EP;
-  const Hot a = hot_args<C>(cx);
+  const Hot a = hot_args<C, OPS>(cx);
+  FR_ZEROED_FRAMES(f);
   const void *shape_ids = uniform_ptr(cx.a->shape_ids);
-  double f[C::MAXLV][EP];
-#pragma unroll
-  for (int k = 0; k < C::MAXLV; ++k)
-#pragma unroll
-    for (int i = 0; i < EP; ++i) f[k][i] = 0.0;
   uint32_t rec_off = (uint32_t)node_begin * 64u;
   int slot = 0;
-  Rec8 nd = load_rec8(a.recs, rec_off);
+  Rec8 r = load_rec8(a.recs, rec_off);
   int shape = at_offset(shape_ids, rec_off >> 4)[0];
   while (shape >= 0) {   // (the sentinel's shape index is -1)
     const int next_shape = at_offset(shape_ids, (rec_off + 64u) >> 4)[0];   // (in flight over the node)
-    fnode_by_shape<C, TOTAL, OPS, SH, 0>(shape, cx, a, f, nd, rec_off, slot, sink);
+    fnode_by_shape<C, TOTAL, OPS, SH, 0>(shape, cx, a, f, r, rec_off, slot, sink);
     shape = next_shape;
     rec_off += 64u;
     slot += a.cps;
   }
 }
 
-// ---------------------------------------------------------------- the plan as an immediate too
-// A run-time compiled kernel may also know the PLAN (jit.cpp: a pipeline of at most
-// kFusedStaticMaxNodes nodes): PG::w holds the records of the group program the launch will use,
-// 16 words per record like NodeRec, PG::group_begin the groups' first records.  The walk is then
-// straight-line code - a node's level, flags, factor rows, output rows, carry slot and op offsets
-// are immediates, the register frames are indexed directly, nothing of a record is loaded or
-// decoded - and what is left per node is the arithmetic, the thresholds of its ops and the feature
-// window's bookkeeping.  Same sums in the same order as fwalk (same functions).
-struct NoProg {
-  static constexpr bool is_static = false, is_shaped = false, is_piece = false;
-};
-template <class PG, int PC>
-struct SRec {
-  static constexpr int w(int i) { return PG::w[PC * 16 + i]; }
-  static constexpr int level = PG::w[PC * 16] & 0xff, flags = PG::w[PC * 16] >> 8;
-  static constexpr int nf = PG::w[PC * 16 + 1] & 0xffff;
-  static constexpr int z_mul = ((PG::w[PC * 16 + 1] >> 16) & 0xff) - 1;
-  static constexpr int emit_mul = ((PG::w[PC * 16 + 1] >> 24) & 0xff) - 1;
-  static constexpr int ne = PG::w[PC * 16 + 6];
-};
-// PC: the record; GB: the first record of its group (carry slots count from there)
+// Template recursion over the records of PG: the walk as straight-line code.  PC: the record; GB:
+// the first record of its group (carry slots count from there).
 template <class C, bool TOTAL, class OPS, class PG, int PC, int GB>
-__device__ __forceinline__ void fwalk_static(WalkCtx &cx, const Hot &a, double (&f)[C::MAXLV][C::EP]) {
-  using R = SRec<PG, PC>;
-  constexpr int EP = C::EP;
-  if constexpr (R::level != kRecSentinelLevel) {
-    static_assert(R::level < C::MAXLV, "a record deeper than the kernel's register frames");
-    const int slot = a.slot_base + (C::MULTI != 0 ? OPS::cps : kCarrySlots) * (PC - GB);
-    constexpr uint32_t me = (uint32_t)PC * 64u;
-    const uint32_t op_off = a.op_base + (uint32_t)R::w(7) * (uint32_t)(OPS::n_padded * 32);
-    freserve<C, OPS>(cx, R::ne * OPS::n);
-    cx.slot = slot;
-    double s[EP];
-    if constexpr ((R::flags & F_SLOW) != 0) {
-      if constexpr ((R::flags & F_CHAIN) != 0) {
-#pragma unroll
-        for (int i = 0; i < EP; ++i) s[i] = f[R::level][i];
-      } else if constexpr (R::level > 0) {
-#pragma unroll
-        for (int i = 0; i < EP; ++i) s[i] = f[R::level - 1][i];
-      } else {
-#pragma unroll
-        for (int i = 0; i < EP; ++i) s[i] = C::SEMI != 1 ? 1.0 : 0.0;
-      }
-      slow_factors<C>(cx, R::w(12), R::nf, s, s, false);
-    } else {
-      if constexpr ((R::flags & F_CHAIN) != 0) {
-        mul_row_from<C>(cx, R::w(2), f[R::level], s);
-      } else if constexpr (R::level > 0) {
-        mul_row_from<C>(cx, R::w(2), f[R::level - 1], s);
-      } else {
-        double ones[EP];
-#pragma unroll
-        for (int i = 0; i < EP; ++i) ones[i] = C::SEMI != 1 ? 1.0 : 0.0;
-        mul_row_from<C>(cx, R::w(2), ones, s);
-      }
-      if constexpr (R::nf > 1) mul_rowp<C>(cx, R::w(3), s);
-      if constexpr (R::nf > 2) mul_rowp<C>(cx, R::w(4), s);
-      if constexpr (R::nf > 3) mul_rowp<C>(cx, R::w(5), s);
-    }
-    if constexpr ((R::flags & F_NEED1) != 0) {
-      double c[EP], x[EP];
-      fscan<C>(cx, s, c, x, slot);
-      if constexpr ((R::flags & (F_CHILDREN | F_NEED2)) == F_CHILDREN) {
-#pragma unroll
-        for (int i = 0; i < EP; ++i) f[R::level][i] = C::SEMI == 0 ? x[i] : c[i];
-      }
-      if constexpr ((R::flags & F_EMIT) != 0) {
-        if constexpr (C::WEIGHTED && TOTAL) {
-          mul_rowp<C>(cx, C::SEMI != 1 ? R::emit_mul : fac_arctic(R::emit_mul, -1), c);
-          if constexpr (C::TOTALINC) {
-            double xs[EP];
-            previous_weighted<C>(cx, R::emit_mul, x, xs);
-            fops_all<C, false, OPS>(cx, a, R::ne, op_off, me, c, xs, s);
-          } else {
-            fops_all<C, false, OPS>(cx, a, R::ne, op_off, me, c, x, s);
-          }
-        } else {
-          fops_all<C, true, OPS>(cx, a, R::ne, op_off, me, c, x, s);
-        }
-      }
-    }
-    if constexpr (C::WEIGHTED && !TOTAL && (R::flags & F_NEED2) != 0) {
-      double c2[EP], x2[EP];
-      mul_rowp<C>(cx, C::SEMI != 1 ? R::z_mul : fac_arctic(R::z_mul, 1), s);
-      fscan<C>(cx, s, c2, x2, slot + 1);
-#pragma unroll
-      for (int i = 0; i < EP; ++i) f[R::level][i] = C::SEMI == 0 ? x2[i] : c2[i];
-    }
-    fwalk_static<C, TOTAL, OPS, PG, PC + 1, GB>(cx, a, f);
+__device__ __forceinline__ void fwalk_static(WalkCtx &cx, const Hot &a, double (&f)[C::MAXLV][C::EP],
+                                             int &sink) {
+  if constexpr (StaticNode<PG, PC>::klevel != kRecSentinelLevel) {
+    StaticNode<PG, PC> nd;
+    fnode_body<C, TOTAL, OPS>(cx, a, f, nd, a.slot_base + a.cps * (PC - GB), sink);
+    fwalk_static<C, TOTAL, OPS, PG, PC + 1, GB>(cx, a, f, sink);
   }
 }
 // the group a unit walks is a run-time value: one straight-line walk per group
 template <class C, bool TOTAL, class OPS, class PG, int G>
-__device__ __forceinline__ void fwalk_static_group(WalkCtx &cx, int g0) {
+__device__ __forceinline__ void fwalk_static_group(WalkCtx &cx, int g0, int &sink) {
   if constexpr (G < PG::groups) {
     if (g0 == G) {
-      Hot a;
-      const IssArgs &ka = *cx.a;
-      a.recs = reinterpret_cast<const NodeRec *>(uniform_ptr(ka.recs));
-      a.ops = reinterpret_cast<const FeatOp *>(uniform_ptr(ka.ops));
-      a.n_ops = OPS::n;
-      a.op_row_bytes = (uint32_t)(OPS::n_padded * 32);
-      a.cps = OPS::cps;
-      a.op_base = 0;
-      a.slot_base = 0;
-      double f[C::MAXLV][C::EP];
-#pragma unroll
-      for (int k = 0; k < C::MAXLV; ++k)
-#pragma unroll
-        for (int i = 0; i < C::EP; ++i) f[k][i] = 0.0;
-      fwalk_static<C, TOTAL, OPS, PG, PG::group_begin[G], PG::group_begin[G]>(cx, a, f);
+      const Hot a = hot_args<C, OPS>(cx);
+      FR_ZEROED_FRAMES(f);
+      fwalk_static<C, TOTAL, OPS, PG, PG::group_begin[G], PG::group_begin[G]>(cx, a, f, sink);
     } else {
-      fwalk_static_group<C, TOTAL, OPS, PG, G + 1>(cx, g0);
+      fwalk_static_group<C, TOTAL, OPS, PG, G + 1>(cx, g0, sink);
     }
   }
 }
 
-// ---------------------------------------------------------------- a large plan in pieces
-// plan.h, PiecedProgram: a kernel of this kind walks the items of ONE piece type - PG::w holds the
-// records of the type's body, a forest of whole sub-tries as straight-line code (fwalk_static
-// above, its output rows and carry slots counted from the item's) - behind a CHAIN, the path
-// from the trie's root to the node the forest hangs below, walked by the record loop in frame 0.
-// A unit = the items [unit_begin[u], unit_begin[u + 1]) on one series, one staging of its rows.
+// A large plan in pieces (plan.h, PiecedProgram): a kernel of this kind walks the items of ONE
+// piece type - PG::w holds the records of the type's body, a forest of whole sub-tries as
+// straight-line code, its output rows and carry slots counted from the item's - behind a CHAIN,
+// the path from the trie's root to the node the forest hangs below, walked by the record loop in
+// frame 0.  A unit = the items [unit_begin[u], unit_begin[u + 1]) on one series, one staging of
+// its rows.
 template <class C, bool TOTAL, class OPS, class PG>
 __device__ __forceinline__ void fwalk_pieces(WalkCtx &cx, int unit, int &sink) {
-  constexpr int EP = C::EP;
-  Hot a = hot_args<C>(cx);
-  a.n_ops = OPS::n;
-  a.op_row_bytes = (uint32_t)(OPS::n_padded * 32);
-  a.cps = C::MULTI != 0 ? OPS::cps : kCarrySlots;
+  Hot a = hot_args<C, OPS>(cx);   // (op_base and slot_base move with the items)
+  FR_ZEROED_FRAMES(f);
   const void *items = uniform_ptr(cx.a->piece_items);
   const void *unit_begin = uniform_ptr(cx.a->piece_unit_begin);
   uint32_t it = (uint32_t)at_offset(unit_begin, (uint32_t)unit * 4u)[0] * 16u;
   const uint32_t it_end = (uint32_t)at_offset(unit_begin, (uint32_t)unit * 4u)[1] * 16u;
-  double f[C::MAXLV][EP];
-#pragma unroll
-  for (int k = 1; k < C::MAXLV; ++k)
-#pragma unroll
-    for (int i = 0; i < EP; ++i) f[k][i] = 0.0;
   for (; it < it_end; it += 16u) {
     cptr<int32_t> iw = at_offset(items, it);
     uint32_t rec_off = (uint32_t)iw[0];
     const int row_base = iw[1], node_base = iw[2];
     // the chain: every node continues frame 0 (the semiring's one in front of the first)
-#pragma unroll
-    for (int i = 0; i < EP; ++i) f[0][i] = C::SEMI != 1 ? 1.0 : 0.0;
+    semiring_one<C>(f[0]);
     a.op_base = 0;
     int slot = a.cps * node_base;
-    Rec8 nd = load_rec8(a.recs, rec_off);
-    while (nd.level() != kRecSentinelLevel) {
-      fnode<C, TOTAL, OPS>(cx, a, f, nd, rec_off, slot, sink);
-      rec_off += 64u;
-      slot += a.cps;
-    }
+    fwalk_records<C, TOTAL, OPS>(cx, a, f, rec_off, slot, sink);
     a.op_base = (uint32_t)row_base * a.op_row_bytes;
     a.slot_base = slot;
-    fwalk_static<C, TOTAL, OPS, PG, 0, 0>(cx, a, f);
+    fwalk_static<C, TOTAL, OPS, PG, 0, 0>(cx, a, f, sink);
   }
 }
 
@@ -981,25 +931,17 @@ __global__ __launch_bounds__(kWalkThreads) void iss_fused_kernel(const IssArgs a
     __syncthreads();
     if constexpr (C::MODE == 2) {
       cx.out_base = a.out + n * a.out_n_stride + t0;
-      fwalk<C, TOTAL, OPS>(cx, node_begin, sink);
     } else {
       cx.fused_used = 0;  // same slots in every chunk
-      if constexpr (PG::is_piece) {
-        static_assert(OPS::is_static && C::MODE == 1, "a piece comes with static ops");
-        cx.frow0 = as_const(a.piece_unit_row0)[g0];
-        fwalk_pieces<C, TOTAL, OPS, PG>(cx, g0, sink);
-      } else {
-      cx.frow0 = as_const(a.group_row_begin)[g0];
-      if constexpr (PG::is_static) {
-        static_assert(OPS::is_static && C::MODE == 1, "a static plan comes with static ops");
-        fwalk_static_group<C, TOTAL, OPS, PG, 0>(cx, g0);
-      } else if constexpr (PG::is_shaped) {
-        static_assert(OPS::is_static && C::MODE == 1, "node shapes come with static ops");
-        fwalk_shaped<C, TOTAL, OPS, PG>(cx, node_begin, sink);
-      } else {
-        fwalk<C, TOTAL, OPS>(cx, node_begin, sink);
-      }
-      }
+      cx.frow0 = as_const(PG::is_piece ? a.piece_unit_row0 : a.group_row_begin)[g0];
+    }
+    static_assert(!(PG::is_piece || PG::is_static || PG::is_shaped) || (OPS::is_static && C::MODE == 1),
+                  "a kernel that knows its plan is a fused one and comes with static ops");
+    if constexpr (PG::is_piece) fwalk_pieces<C, TOTAL, OPS, PG>(cx, g0, sink);
+    else if constexpr (PG::is_static) fwalk_static_group<C, TOTAL, OPS, PG, 0>(cx, g0, sink);
+    else if constexpr (PG::is_shaped) fwalk_shaped<C, TOTAL, OPS, PG>(cx, node_begin, sink);
+    else fwalk<C, TOTAL, OPS>(cx, node_begin, sink);
+    if constexpr (C::MODE == 1) {
       // a unit whose features fit the window keeps them there over its time chunks; else every
       // chunk leaves its share (added onto the earlier chunks' in global memory)
       if (!a.feat_fits || chunk + 1 == a.nchunks) feat_flush<C>(cx, !a.feat_fits && chunk > 0);
@@ -1007,5 +949,7 @@ __global__ __launch_bounds__(kWalkThreads) void iss_fused_kernel(const IssArgs a
   }
   if (sink == 0x7fffffff) (C::MODE == 2 ? a.out : a.feats)[0] = 0.0;   // (keeps the cache-touching loads alive)
 }
+
+#undef FR_ZEROED_FRAMES
 
 }  // namespace fr
