@@ -1144,7 +1144,7 @@ def letter_rows(Xd, spec, ext_d=None, one_is_zero: bool = False, out=None, spec_
             raise TypeError("letter values must be a contiguous float64 (N, H, T) device tensor")
         H = int(ext_d.shape[1])
     out = _prep_out(out, (N, sp.shape[0], T), Xd)
-    sp_d = spec_d if spec_d is not None else t.from_numpy(sp).to(Xd.device)
+    sp_d = spec_d if spec_d is not None else to_device(sp, dtype=np.int32)
     if sp_d.dtype != t.int32 or tuple(sp_d.shape) != sp.shape or not sp_d.is_contiguous():
         raise TypeError("the device copy of the row specification must be (Dv, 3) int32")
     check(lib().fr_letter_rows(dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
@@ -1165,7 +1165,7 @@ def rows_unshift(Ad, shifts, out=None, shifts_d=None):
     if sh.shape != (K,):
         raise ValueError("one shift per row")
     out = _prep_out(out, (K, N, T), Ad)
-    sh_d = shifts_d if shifts_d is not None else t.from_numpy(sh).to(Ad.device)
+    sh_d = shifts_d if shifts_d is not None else to_device(sh, dtype=np.int32)
     if sh_d.dtype != t.int32 or tuple(sh_d.shape) != (K,) or not sh_d.is_contiguous():
         raise TypeError("the device copy of the shifts must be (K) int32")
     check(lib().fr_rows_unshift(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(sh_d),

@@ -694,10 +694,13 @@ int fr_pipeline_set_quantiles(fr_pipeline_t *pl, const double *h_quant) {
       HIP_TRY(hipMemcpy(pl->d_npi_pairs, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice));
     }
   }
-  // (new thresholds: the kernels compiled for the old ops go - once the launches that may still
-  // be running them are done: fr_pipeline_run returns without a synchronisation)
+  // (new thresholds: d_ops is rewritten in place and the kernels compiled for the old ops go - once
+  // the launches that may still be reading or running them are done: fr_pipeline_run returns
+  // without a synchronisation, and the hipMemcpy below does not wait for a non-blocking stream.
+  // Whatever the pipeline holds: the generic kernel reads d_ops too.  A refit is rare and has
+  // waited for a selection already.)
   std::lock_guard<std::mutex> jit_lock(pl->jit_mu);
-  if (!pl->jit.empty() || !pl->jit_static.empty() || !pl->jit_pieces.empty()) (void)hipDeviceSynchronize();
+  (void)hipDeviceSynchronize();
   ++pl->jit_gen;
   for (auto &kv : pl->jit) fr::jit_unload(kv.second);
   for (auto &kv : pl->jit_static) fr::jit_unload(kv.second);

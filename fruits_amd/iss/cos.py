@@ -256,7 +256,8 @@ class CosWISS(ISS):
             self._arm_plan(plan, idx, T)
             return plan.run(Xd, None, out=out, layout="KNT")
         plan, begin_d, coeff_d, desc_d = self._program(start, stop, D)
-        trig = t.from_numpy(self._trig(T)).to(Xd.device)              # (F, 2, T)
+        # (to_device: a copy from pageable memory on the caller's stream would wait for that stream)
+        trig = nat.to_device(self._trig(T))                           # (F, 2, T)
         Xa = t.empty((N, D + 2, T), dtype=t.float64, device=Xd.device)
         Xa[:, :D] = Xd
         terms = None

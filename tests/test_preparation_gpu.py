@@ -378,25 +378,22 @@ def test_fit_hands_over_the_prepared_shape(fr):
     assert out.shape == (9, fruit.nfeatures()) and np.isfinite(out).all()
 
 
-def test_non_default_stream(fr):
-    from fruits_amd import _native as nat
-    t = nat.torch()
+def test_non_default_stream(fr, record_property):
+    """Every preparateur on a non-blocking side stream while the producer of its input still runs
+    (tests/stream_order.py): bit for bit the default-stream result, which is held to ``np_apply``."""
+    import stream_order as so
     X = np.random.default_rng(4).standard_normal((33, 3, 700))
+    wrong = np.random.default_rng(5).standard_normal(X.shape)
     P = fr.preparation
     preps = [P.NRM(), P.LAG(), _fitted(P.MAV(7), X.shape, 1), _fitted(P.RIN(5), X.shape, 2),
              _fitted(P.JLD(2), X.shape, 3), _fitted(P.FFN(2), X.shape, 4),
              _fitted(P.DIM(P.RIN(2), 1), X.shape, 5)]
-    Xd = nat.to_device(X)
-    t.cuda.synchronize()
-    side = t.cuda.Stream()
-    with t.cuda.stream(side):
-        outs = [p._transform_device(Xd) for p in preps]
-    side.synchronize()
-    for p, o in zip(preps, outs):
+    for p in preps:
+        (got,), report = so.behind_producer(lambda b, p=p: p._transform_device(b), [X], [wrong], what=str(p))
+        so.note(record_property, report)
         ref = np_apply(p, X)
         scale = np.abs(ref).max()
-        assert np.abs(nat.to_host(o) - ref).max() <= 1e-9 * scale, str(p)
-    np.testing.assert_array_equal(nat.to_host(Xd), X)
+        assert np.abs(got - ref).max() <= 1e-9 * scale, str(p)
 
 
 def _new_prep_fruit(fr):
