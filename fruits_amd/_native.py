@@ -49,7 +49,7 @@ EXPORTS = [
     "fr_letter_rows", "fr_rows_unshift",
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
     "fr_iss_backward", "fr_iss_backward_max", "fr_iss_backward_weighted",
-    "fr_sieve_pick", "fr_iss_backward_picked",
+    "fr_sieve_pick", "fr_iss_backward_picked", "fr_plan_set_grad_lengths",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -116,6 +116,7 @@ def lib():
     L.fr_pipeline_prepare_cached.argtypes = [C.c_void_p, C.c_int64, C.c_int32]
     L.fr_pipeline_set_series_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
     L.fr_pipeline_set_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.fr_plan_set_grad_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.fr_pipeline_set_argmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.fr_select_ranks_begin.restype = C.c_void_p
     L.fr_select_ranks_end.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -1186,6 +1187,33 @@ def _backward_args(prefix_plan: Plan, Xd, G, row_prefix):
     return (N, D, T, K, prefix_plan.rows), rp, [C.c_int64(int(s)) for s in G.stride()]
 
 
+class _grad_lengths:
+    """Set, call, clear: the plan is armed with the ``(N,)`` int32 device lengths
+    (fr_plan_set_grad_lengths) for the one ABI call inside the block; None arms nothing.  The
+    entry reads the pointer once and hands it to its kernels by value, so clearing it behind the
+    call is safe; the caller keeps the tensor alive, as it keeps ``Xd``."""
+
+    def __init__(self, prefix_plan: "Plan", lengths_d, Xd) -> None:
+        self.plan, self.lengths_d = prefix_plan, lengths_d
+        if lengths_d is not None:
+            t = torch()
+            if (lengths_d.dtype != t.int32 or tuple(lengths_d.shape) != (int(Xd.shape[0]),)
+                    or not lengths_d.is_contiguous() or lengths_d.device != Xd.device):
+                raise TypeError("the lengths must be a contiguous int32 (N,) tensor on the input's device")
+
+    def __enter__(self):
+        if self.lengths_d is not None:
+            check(lib().fr_plan_set_grad_lengths(self.plan._h, C.c_void_p(self.lengths_d.data_ptr()),
+                                                 C.c_int64(int(self.lengths_d.shape[0]))),
+                  "fr_plan_set_grad_lengths")
+        return self
+
+    def __exit__(self, *exc):
+        if self.lengths_d is not None:
+            check(lib().fr_plan_set_grad_lengths(self.plan._h, None, 0), "fr_plan_set_grad_lengths")
+        return False
+
+
 def _backward_scratch(work, need: int, what: str, Xd):
     """The caller's scratch if it holds ``need`` doubles (``what``: that number in words), or a
     fresh one."""
@@ -1197,40 +1225,46 @@ def _backward_scratch(work, need: int, what: str, Xd):
     return work
 
 
-def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, entry="fr_iss_backward"):
+def iss_backward(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, entry="fr_iss_backward",
+                 lengths_d=None):
     """fr_iss_backward: the gradient ``(N, D, T)`` of unweighted Reals iterated sums with respect
     to ``Xd``.  ``prefix_plan``: the plan of the distinct prefixes, each with depth 1; ``Sd``
     ``(V, N, T)`` its output on ``Xd``; ``G`` the upstream gradient as an ``(N, K, T)`` device
     tensor of any strides; ``row_prefix`` ``(K)`` int32 host array, the row of ``Sd`` that output
     row k is; ``work``: a ``(V, N, T)`` scratch if the caller keeps one.  ``entry``: the ABI
-    entry that takes these arguments (``iss_backward_max``)."""
+    entry that takes these arguments (``iss_backward_max``).  ``lengths_d``: ``(N,)`` int32
+    device lengths in ``1..T`` - series n is its first ``lengths_d[n]`` steps, the gradient behind
+    them is +0.0 and ``G`` is not read there (fr_plan_set_grad_lengths around the call)."""
     t = torch()
     (N, D, T, K, V), rp, (sn, sk, st) = _backward_args(prefix_plan, Xd, G, row_prefix)
     if Sd.dtype != t.float64 or tuple(Sd.shape) != (V, N, T) or not Sd.is_contiguous():
         raise TypeError("the prefix sums must be a contiguous float64 (V, N, T) device tensor")
     work = _backward_scratch(work, V * N * T, "V * N * T", Xd)
     dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
-    check(getattr(lib(), entry)(prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
-                                dptr(Sd), dptr(G), C.c_int64(K), sn, sk, st, _i32p(rp), dptr(work),
-                                dptr(dX), stream_ptr()),
-          entry)
+    with _grad_lengths(prefix_plan, lengths_d, Xd):
+        check(getattr(lib(), entry)(prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T),
+                                    dptr(Sd), dptr(G), C.c_int64(K), sn, sk, st, _i32p(rp), dptr(work),
+                                    dptr(dX), stream_ptr()),
+              entry)
     return dX
 
 
-def iss_backward_max(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None):
+def iss_backward_max(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, lengths_d=None):
     """fr_iss_backward_max: the gradient ``(N, D, T)`` of unweighted Arctic or Bayesian iterated
     sums with respect to ``Xd``; the arguments of ``iss_backward``, ``prefix_plan`` created with
     ``arctic=True`` or ``bayesian=True``."""
-    return iss_backward(prefix_plan, Xd, Sd, G, row_prefix, work, entry="fr_iss_backward_max")
+    return iss_backward(prefix_plan, Xd, Sd, G, row_prefix, work, entry="fr_iss_backward_max",
+                        lengths_d=lengths_d)
 
 
-def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=None):
+def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=None, lengths_d=None):
     """fr_iss_backward_weighted: the gradient ``(N, D, T)`` of weighted Reals iterated sums with
     respect to ``Xd``, the lookup being a constant.  ``prefix_plan``: the weighted plan of the
     distinct (letters, alphas) prefixes, each with depth 1; ``lookup_d`` ``(1 | N, T)`` the
     weighting's device lookup; ``G`` and ``row_prefix`` as in ``iss_backward``.  The entry forms
     the carried sums itself: it takes no output of the plan.  ``work``: a scratch of
-    ``2 V N T + 2 alphas rows T`` doubles if the caller keeps one."""
+    ``2 V N T + 2 alphas rows T`` doubles if the caller keeps one.  ``lengths_d`` as in
+    ``iss_backward``; row n of an ``(N, T)`` lookup is then the row of a series of that length."""
     t = torch()
     (N, D, T, K, V), rp, (sn, sk, st) = _backward_args(prefix_plan, Xd, G, row_prefix)
     if (lookup_d is None or lookup_d.dtype != t.float64 or lookup_d.dim() != 2
@@ -1243,10 +1277,11 @@ def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=N
     dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
     # (the scratch in three parts; an empty part still gets a distinct address)
     parts = [C.c_void_p(work.data_ptr() + 8 * o) for o in (0, cells, 2 * cells)]
-    check(lib().fr_iss_backward_weighted(
-        prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
-        C.c_int64(rows), dptr(G), C.c_int64(K), sn, sk, st,
-        _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
+    with _grad_lengths(prefix_plan, lengths_d, Xd):
+        check(lib().fr_iss_backward_weighted(
+            prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
+            C.c_int64(rows), dptr(G), C.c_int64(K), sn, sk, st,
+            _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
     return dX
 
 
@@ -1256,7 +1291,9 @@ def sieve_pick(Ad, spec, spec_d, cuts_d, q_d, F: int):
     ``(K, N, T)`` device tensor ``Ad`` in one launch.  ``spec`` ``(n_sieves, 6)`` int32 host
     array ``{kind, cut_begin, C1, q_begin, Q1, feat_begin}`` per sieve (checked by the library),
     ``spec_d`` its device copy, ``cuts_d`` int64 and ``q_d`` float64 the flat device tables the
-    spec indexes.  Returns ``(features (N, K, F) float64, positions (N, K, F) int32)``: of every
+    spec indexes.  Per-series cuts: every kind of the spec carries ``FR_SIEVE_SERIES_CUTS`` and
+    ``cuts_d`` is the contiguous ``(N, row)`` table whose row n holds the cut rows of series n,
+    which the spec's ``cut_begin`` index.  Returns ``(features (N, K, F) float64, positions (N, K, F) int32)``: of every
     feature its value and the step of its row that it selects, -1 where it selects none."""
     t = torch()
     if Ad.dtype != t.float64 or Ad.dim() != 3 or not Ad.is_contiguous():
@@ -1267,9 +1304,11 @@ def sieve_pick(Ad, spec, spec_d, cuts_d, q_d, F: int):
         raise ValueError("the spec table is (n_sieves, 6)")
     if (spec_d.dtype != t.int32 or tuple(spec_d.shape) != sp.shape or not spec_d.is_contiguous()
             or cuts_d.dtype != t.int64 or not cuts_d.is_contiguous()
+            or (sp.shape[0] > 0 and (sp[0, 0] & FR_SIEVE_SERIES_CUTS)
+                and (cuts_d.dim() != 2 or int(cuts_d.shape[0]) != N))
             or (q_d is not None and (q_d.dtype != t.float64 or not q_d.is_contiguous()))):
         raise TypeError("the device tables must be contiguous: spec int32 like the host table, "
-                        "cuts int64, thresholds float64")
+                        "cuts int64 (per-series cuts: (N, row)), thresholds float64")
     feat = t.empty((N, K, int(F)), dtype=t.float64, device=Ad.device)
     pos = t.empty((N, K, int(F)), dtype=t.int32, device=Ad.device)
     check(lib().fr_sieve_pick(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(spec_d),
@@ -1281,13 +1320,14 @@ def sieve_pick(Ad, spec, spec_d, cuts_d, q_d, F: int):
     return feat, pos
 
 
-def iss_backward_picked(prefix_plan: Plan, Xd, pos_d, w_d, row_prefix, Sd=None, lookup_d=None):
+def iss_backward_picked(prefix_plan: Plan, Xd, pos_d, w_d, row_prefix, Sd=None, lookup_d=None,
+                        lengths_d=None):
     """fr_iss_backward_picked: the gradient ``(N, D, T)`` of picked features of iterated sums
     with respect to ``Xd`` - the adjoint the plan's kind names, with a sparse upstream.
     ``pos_d`` ``(N, K, F)`` int32 and ``w_d`` ``(N, K, F)`` float64, contiguous: the weight
     ``w_d[n, k, f]`` reaches step ``pos_d[n, k, f]`` of row k, nothing where that is negative.
     ``Sd``: an unweighted plan's output on ``Xd`` ``(V, N, T)``; ``lookup_d``: a weighted plan's
-    ``(1 | N, T)`` lookup.  ``row_prefix`` as in ``iss_backward``."""
+    ``(1 | N, T)`` lookup.  ``row_prefix`` and ``lengths_d`` as in ``iss_backward``."""
     t = torch()
     N, D, T = _rows3(Xd)
     rp = np.ascontiguousarray(row_prefix, dtype=np.int32)
@@ -1318,8 +1358,9 @@ def iss_backward_picked(prefix_plan: Plan, Xd, pos_d, w_d, row_prefix, Sd=None, 
             raise TypeError("the prefix sums must be a contiguous float64 (V, N, T) device tensor")
         work = _backward_scratch(None, cells, "V * N * T", Xd)
         Cs, A, ax, S, lk, rows = null, dptr(work), null, dptr(Sd), null, 0
-    check(lib().fr_iss_backward_picked(
-        prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), S, lk, C.c_int64(rows),
-        dptr(pos_d), dptr(w_d), C.c_int64(K), C.c_int32(F), _i32p(rp), Cs, A, ax, dptr(dX),
-        stream_ptr()), "fr_iss_backward_picked")
+    with _grad_lengths(prefix_plan, lengths_d, Xd):
+        check(lib().fr_iss_backward_picked(
+            prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), S, lk, C.c_int64(rows),
+            dptr(pos_d), dptr(w_d), C.c_int64(K), C.c_int32(F), _i32p(rp), Cs, A, ax, dptr(dX),
+            stream_ptr()), "fr_iss_backward_picked")
     return dX

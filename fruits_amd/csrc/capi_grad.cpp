@@ -4,6 +4,7 @@
 // fr_iss_backward_picked: any of the three with the sparse upstream of picked features.  The trie -
 // parents, children, letters, exp tables - is read off the plan the plan compiler built (plan.cpp);
 // the kernels are those of kernels_grad.hip.  One body (run_backward) serves the four entries.
+// fr_plan_set_grad_lengths arms a plan with per-series lengths for the backward passes that follow.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -396,6 +397,11 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   if (refused) return fail(FR_E_ARG, who + ": " + refused);
   hipStream_t st = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(p.mu);
+  // (read once: the launches below carry the pointer by value, a setter after this changes nothing)
+  const int32_t *lengths = p.grad_lengths;
+  if (lengths && p.grad_lengths_n != N)
+    return fail(FR_E_ARG, who + ": the lengths were set for " + std::to_string(p.grad_lengths_n) +
+                              " series (fr_plan_set_grad_lengths), the call brings " + std::to_string(N));
   GradTables *g = nullptr;
   int rc = ensure_tables(p, who, h_row_prefix, K, D, N == 0 || T == 0, st, g);
   if (rc != FR_OK || N == 0 || T == 0) return rc;
@@ -418,6 +424,7 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   }
   a.A = d_A;
   a.dX = d_dX;
+  a.len = lengths;
   a.g_n = g_n_stride;
   a.g_k = g_k_stride;
   a.g_t = g_t_stride;
@@ -454,6 +461,16 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
 }  // namespace
 
 extern "C" {
+
+int fr_plan_set_grad_lengths(fr_plan_t *prefix_plan, const int32_t *d_lengths, int64_t N) {
+  if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, "fr_plan_set_grad_lengths: null plan");
+  if (N < 0) return fail(FR_E_ARG, "fr_plan_set_grad_lengths: bad shape");
+  fr::Plan &p = *prefix_plan->p;
+  std::lock_guard<std::mutex> lock(p.mu);
+  p.grad_lengths = d_lengths;
+  p.grad_lengths_n = d_lengths ? N : 0;
+  return FR_OK;
+}
 
 int fr_iss_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D,
                              int64_t T, const double *d_lookup, int64_t lookup_rows,

@@ -420,16 +420,28 @@ int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int3
     return fail(FR_E_LIMIT, who + ": at most 256 features per row, not " + std::to_string(F));
   if (T > 0x7fffffffLL) return fail(FR_E_LIMIT, who + ": positions are 32-bit, T is not");
   if (!h_spec) return fail(FR_E_ARG, who + ": null host table");
+  // per-series cuts: every sieve or none; d_cuts is then (N, n_cuts / N) and a sieve's cut row
+  // lies within a series' row
+  const bool series_cuts = (h_spec[0] & FR_SIEVE_SERIES_CUTS) != 0;
+  for (int32_t s = 1; s < n_sieves; ++s)
+    if (((h_spec[6 * (int64_t)s] & FR_SIEVE_SERIES_CUTS) != 0) != series_cuts)
+      return fail(FR_E_ARG, who + ": sieve " + std::to_string(s) + " and sieve 0 differ in FR_SIEVE_SERIES_CUTS: "
+                                  "either every sieve reads per-series cuts or none does");
+  if (series_cuts && N > 0 && n_cuts % N != 0)
+    return fail(FR_E_ARG, who + ": per-series cuts are an (N, row) table, but n_cuts = " +
+                              std::to_string(n_cuts) + " is no multiple of N = " + std::to_string(N));
+  const int64_t cut_row = series_cuts && N > 0 ? n_cuts / N : n_cuts;
   // every entry of the table, before a kernel reads the device copy
   int64_t features = 0;
   for (int32_t s = 0; s < n_sieves; ++s) {
     const int32_t *sp = h_spec + 6 * (int64_t)s;
     const std::string sieve = who + ": sieve " + std::to_string(s);
-    const int32_t kind = sp[0], cut_begin = sp[1], C1 = sp[2], q_begin = sp[3], Q1 = sp[4];
+    const int32_t kind = sp[0] & ~FR_SIEVE_SERIES_CUTS, cut_begin = sp[1], C1 = sp[2], q_begin = sp[3], Q1 = sp[4];
     if (kind != FR_SIEVE_END && kind != FR_SIEVE_MAX && kind != FR_SIEVE_MIN)
       return fail(FR_E_ARG, sieve + " is no selecting sieve (END, MAX, MIN): kind " + std::to_string(kind));
-    if (C1 < 2 || cut_begin < 0 || (int64_t)cut_begin + C1 > n_cuts)
-      return fail(FR_E_ARG, sieve + " has a cut row outside the cut table");
+    if (C1 < 2 || cut_begin < 0 || (int64_t)cut_begin + C1 > cut_row)
+      return fail(FR_E_ARG, sieve + (series_cuts ? " has a cut row outside a series' row of the cut table"
+                                                 : " has a cut row outside the cut table"));
     if (kind != FR_SIEVE_END && (Q1 < 2 || q_begin < 0 || (int64_t)q_begin + Q1 > n_q))
       return fail(FR_E_ARG, sieve + " has thresholds outside the threshold table");
     if (sp[5] != features)
@@ -445,7 +457,8 @@ int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int3
   if (!d_A || !d_spec || !d_cuts || !d_feat || !d_pos || (n_q > 0 && !d_q))
     return fail(FR_E_ARG, who + ": null device pointer");
   hipError_t e = fr::launch_sieve_pick(d_A, K, N, T, reinterpret_cast<const fr::PickSieve *>(d_spec), n_sieves,
-                                       d_cuts, d_q, F, d_feat, d_pos, (hipStream_t)stream);
+                                       d_cuts, series_cuts ? cut_row : 0, d_q, F, d_feat, d_pos,
+                                       (hipStream_t)stream);
   return launched(e, "sieve pick launch", "fr_sieve_pick: grid too large (K * N)");
 }
 

@@ -142,10 +142,12 @@ struct PickSieve {
   int32_t Q1;
   int32_t feat_begin;   // its first feature among the F of a row
 };
-// feat, pos: (N, K, F), row (k, n) of A at (n * K + k) * F; hipErrorInvalidValue: a grid limit
+// feat, pos: (N, K, F), row (k, n) of A at (n * K + k) * F; hipErrorInvalidValue: a grid limit.
+// cut_stride: elements from one series' cut rows to the next (per-series cuts, every END row
+// wrapped for its series already), 0: one table for all.
 hipError_t launch_sieve_pick(const double *A, int64_t K, int64_t N, int64_t T, const PickSieve *spec,
-                             int n_sieves, const int64_t *cuts, const double *q, int F, double *feat,
-                             int32_t *pos, hipStream_t st);
+                             int n_sieves, const int64_t *cuts, int64_t cut_stride, const double *q,
+                             int F, double *feat, int32_t *pos, hipStream_t st);
 // the backward pass of the trie walk (kernels_grad.hip): which adjoint, and the
 // tables of the prefix trie, all on the device.  Node v is the plan's node v (DFS preorder); CSR
 // tables have V + 1 (D + 1) offsets.
@@ -186,6 +188,10 @@ struct GradArgs {
   int64_t aux_n;        // doubles from one series' row to the next (T; 0: one row for all)
   const int32_t *tab;   // three tables per node: its own E+, its own E-, its parent's E- (-1: unused)
   const int32_t *inner_nodes;   // the nodes that have children, by rising depth
+  // per-series lengths, or null: series n is its first len[n] steps, 1 <=
+  // len[n] <= T.  T stays the row stride of every buffer; the kernels walk, read and write A, S
+  // and C below len[n] alone, and dX behind it is +0.0.
+  const int32_t *len;           // (N)
 };
 constexpr int kPickMaxFeatures = 256;   // features of a row of fr_sieve_pick, pairs of a row of the sparse upstream
 constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)

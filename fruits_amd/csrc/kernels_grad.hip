@@ -27,6 +27,15 @@
 // Plain loads and stores only; all offsets are 64-bit; every access is guarded by t < T.  The
 // tables are wave-uniform and read through the constant address space (scalar loads).
 //
+// PER-SERIES LENGTHS (a.len).  T stays the row stride; the extent of series n is
+// T_n = len[n] (series_extent: workgroup-uniform, one scalar load; T without lengths).  The adjoint
+// is anti-causal - A_v[t] sums over s >= t - so the scans START at the series' own last chunk,
+// grad_chunks(T_n) - 1, and every guard on a time step is t < T_n: the chunks are aligned at t = 0
+// and the steps past the extent hold exact zeros, so the lane sums, wave totals and carries - and
+// the bits - are those of the call on the truncated series.  Nothing of A, S, C or G is read at
+// t >= T_n (A and C are never written there), and grad_input_kernel stores +0.0 there.  The guards
+// select; nothing is masked by a multiplication.
+//
 // WHAT EACH ADJOINT ADDS.
 // Reals, unweighted (fruits/iss/semiring.py:98-125): S_v = cumsum(m_v * shift(S_p)),
 // m_v[t] = prod_d x_d[t]^e_vd.
@@ -116,6 +125,9 @@ __device__ __forceinline__ double exp_factor(const double *__restrict__ aux_n, i
 
 // ------------------------------------------------------------------ the shared frame
 // The chunks of a time axis and the first of the four steps of this lane in chunk c.
+__device__ __forceinline__ int64_t series_extent(const GradArgs &a, int64_t n) {
+  return a.len ? (int64_t)as_const(a.len)[n] : a.T;
+}
 __device__ __forceinline__ int64_t grad_chunks(int64_t T) { return (T + kGradChunk - 1) / kGradChunk; }
 __device__ __forceinline__ int64_t forward_t0(int64_t c) { return c * kGradChunk + 4 * (int64_t)threadIdx.x; }
 __device__ __forceinline__ int64_t reversed_t0(int64_t c) {
@@ -153,14 +165,15 @@ __device__ __forceinline__ void lane_suffix(double (&b)[4]) {
   b[0] += b[1];
 }
 
-// b[j] += the rows [gb, ge) of the upstream gradient of the series at `gn`, at the steps t0 + j.
+// b[j] += the rows [gb, ge) of the upstream gradient of the series at `gn`, at the steps t0 + j
+// below the series' extent Tn.
 __device__ __forceinline__ void gather_upstream(const GradArgs &a, const double *__restrict__ gn, int gb,
-                                                int ge, int64_t t0, double (&b)[4]) {
+                                                int ge, int64_t t0, int64_t Tn, double (&b)[4]) {
   for (int g = gb; g < ge; ++g) {
     const double *__restrict__ gk = gn + (int64_t)as_const(a.g_row)[g] * a.g_k;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (t0 + j < a.T) b[j] += gk[(t0 + j) * a.g_t];
+      if (t0 + j < Tn) b[j] += gk[(t0 + j) * a.g_t];
   }
 }
 
@@ -170,7 +183,7 @@ __device__ __forceinline__ void gather_upstream(const GradArgs &a, const double 
 // each added in turn - and so are the bits.  A position < 0 (an empty band) matches no step.
 // n and the node are workgroup-uniform: the pairs are scalar loads, every lane sees every pair.
 __device__ __forceinline__ void gather_picked(const GradArgs &a, int64_t n, int gb, int ge, int64_t t0,
-                                              double (&b)[4]) {
+                                              int64_t Tn, double (&b)[4]) {
   for (int g = gb; g < ge; ++g) {
     const int64_t at = n * a.g_n + (int64_t)as_const(a.g_row)[g] * a.g_k;
     for (int f = 0; f < a.F; ++f) {
@@ -178,7 +191,7 @@ __device__ __forceinline__ void gather_picked(const GradArgs &a, int64_t n, int 
       const double w = as_const(a.w)[at + f];
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (p == t0 + j && t0 + j < a.T) b[j] += w;
+        if (p == t0 + j && t0 + j < Tn) b[j] += w;
     }
   }
 }
@@ -208,7 +221,7 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
   __shared__ double wave_total[2][KIND == kGradNonTotal ? 2 : 1][4];
   const int64_t n = blockIdx.x;
   const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
-  const int64_t N = a.N, T = a.T;
+  const int64_t N = a.N, T = a.T, Tn = series_extent(a, n);
   const double *__restrict__ xn = a.X + n * a.D * T;
   const double *__restrict__ gn = SPARSE ? nullptr : a.G + n * a.g_n;
   const double *__restrict__ en = WEIGHTED ? a.aux + n * a.aux_n : nullptr;
@@ -225,18 +238,18 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
   const bool scan1 = KIND == kGradNonTotal && has_c;
 
   double carry0 = 0.0, carry1 = 0.0;   // the sums over the chunks to the right
-  for (int64_t c = grad_chunks(T) - 1; c >= 0; --c) {
+  for (int64_t c = grad_chunks(Tn) - 1; c >= 0; --c) {
     const int64_t t0 = reversed_t0(c);
     double b[4] = {0.0, 0.0, 0.0, 0.0};   // B_v; non-total: G_v
     double q[4] = {0.0, 0.0, 0.0, 0.0};   // non-total: Q_v
     if constexpr (SPARSE)
-      gather_picked(a, n, gb, ge, t0, b);
+      gather_picked(a, n, gb, ge, t0, Tn, b);
     else
-      gather_upstream(a, gn, gb, ge, t0, b);
+      gather_upstream(a, gn, gb, ge, t0, Tn, b);
     if (TOTAL && has_g) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (t0 + j < T) b[j] *= exp_factor(en, a.aux_tab, t_minus, t0 + j);
+        if (t0 + j < Tn) b[j] *= exp_factor(en, a.aux_tab, t_minus, t0 + j);
     }
     for (int ci = cb; ci < ce; ++ci) {
       const int ch = as_const(a.child)[ci];
@@ -247,7 +260,7 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int64_t s = t0 + j + 1;
-        if (s >= T) continue;
+        if (s >= Tn) continue;
         double term = letter_value(a, xn, fb, fe, s, -1);
         if constexpr (WEIGHTED) term *= exp_factor(en, a.aux_tab, t_minus, s);
         if constexpr (TOTAL) term *= exp_factor(en, a.aux_tab, c_plus, s);
@@ -257,7 +270,7 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
           b[j] += term * ac[s];
       }
     }
-    // the lane's own suffix sums (steps past T hold exact zeros), then the lanes from the right
+    // the lane's own suffix sums (steps past the extent hold exact zeros), then the lanes from the right
     double excl0 = 0.0, excl1 = 0.0;
     if (scan0) {
       lane_suffix(b);
@@ -277,7 +290,7 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if (t0 + j >= T) continue;
+      if (t0 + j >= Tn) continue;
       double out = scan0 ? off0 + b[j] : 0.0;
       if (scan1) {
         const double sq = (off1 + q[j]) * exp_factor(en, a.aux_tab, t_plus, t0 + j);
@@ -319,7 +332,7 @@ __global__ __launch_bounds__(256) void grad_prefix_kernel(GradArgs a, int first)
   __shared__ double wave_total[2][4];
   const int64_t n = blockIdx.x;
   const int v = as_const(a.inner_nodes)[first + (int)blockIdx.y];
-  const int64_t N = a.N, T = a.T;
+  const int64_t N = a.N, T = a.T, Tn = series_extent(a, n);
   const double *__restrict__ xn = a.X + n * a.D * T;
   const double *__restrict__ en = a.aux + n * a.aux_n;
   const int fb = as_const(a.fac_begin)[v], fe = as_const(a.fac_begin)[v + 1];
@@ -329,19 +342,19 @@ __global__ __launch_bounds__(256) void grad_prefix_kernel(GradArgs a, int first)
   double *__restrict__ cv = a.C + ((int64_t)as_const(a.self_srow)[v] * N + n) * T;
 
   double carry = 0.0;   // sum of y_v over the chunks to the left
-  const int64_t chunks = grad_chunks(T);
+  const int64_t chunks = grad_chunks(Tn);
   for (int64_t c = 0; c < chunks; ++c) {
     const int64_t t0 = forward_t0(c);
     double y[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t t = t0 + j;
-      if (t >= T) continue;
+      if (t >= Tn) continue;
       double val = letter_value(a, xn, fb, fe, t, -1);
       if (ps >= 0) val = t > 0 ? val * cp[t - 1] * exp_factor(en, a.aux_tab, t_pminus, t) : 0.0;
       y[j] = val * exp_factor(en, a.aux_tab, t_plus, t);
     }
-    // the lane's own prefix sums (steps past T hold exact zeros), then the lanes from the left
+    // the lane's own prefix sums (steps past the extent hold exact zeros), then the lanes from the left
     y[1] += y[0];
     y[2] += y[1];
     y[3] += y[2];
@@ -350,7 +363,7 @@ __global__ __launch_bounds__(256) void grad_prefix_kernel(GradArgs a, int first)
     const double off = scan_offset(wave_total[c & 1], excl, carry);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (t0 + j < T) cv[t0 + j] = off + y[j];
+      if (t0 + j < Tn) cv[t0 + j] = off + y[j];
   }
 }
 
@@ -391,7 +404,7 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
   __shared__ int wave_head[2][4];
   const int64_t n = blockIdx.x;
   const int v = as_const(a.level_nodes)[first + (int)blockIdx.y];
-  const int64_t N = a.N, T = a.T;
+  const int64_t N = a.N, T = a.T, Tn = series_extent(a, n);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double *__restrict__ xn = a.X + n * a.D * T;
   const double *__restrict__ gn = SPARSE ? nullptr : a.G + n * a.g_n;
@@ -401,32 +414,32 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
   const int cb = as_const(a.child_begin)[v], ce = as_const(a.child_begin)[v + 1];
 
   double carry = 0.0;   // the open sum that enters the chunk from the right
-  for (int64_t c = grad_chunks(T) - 1; c >= 0; --c) {
+  for (int64_t c = grad_chunks(Tn) - 1; c >= 0; --c) {
     const int64_t t0 = reversed_t0(c);
-    // the heads, read off the recomputed S_v alone (steps past T hold none)
+    // the heads, read off the recomputed S_v alone (steps past the extent hold none)
     double s[5];
 #pragma unroll
-    for (int j = 0; j < 5; ++j) s[j] = (t0 + j >= 1 && t0 + j - 1 < T) ? sv[t0 + j - 1] : 0.0;
+    for (int j = 0; j < 5; ++j) s[j] = (t0 + j >= 1 && t0 + j - 1 < Tn) ? sv[t0 + j - 1] : 0.0;
     bool h[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = t0 + j < T && (t0 + j == 0 || s[j + 1] > s[j]);
+    for (int j = 0; j < 4; ++j) h[j] = t0 + j < Tn && (t0 + j == 0 || s[j + 1] > s[j]);
     double b[4] = {0.0, 0.0, 0.0, 0.0};
     if constexpr (SPARSE)
-      gather_picked(a, n, gb, ge, t0, b);
+      gather_picked(a, n, gb, ge, t0, Tn, b);
     else
-      gather_upstream(a, gn, gb, ge, t0, b);
+      gather_upstream(a, gn, gb, ge, t0, Tn, b);
     for (int ci = cb; ci < ce; ++ci) {
       const int ch = as_const(a.child)[ci];
       const double *__restrict__ ac = a.A + ((int64_t)ch * N + n) * T;
       if constexpr (KIND == kGradArctic) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (t0 + j < T) b[j] += ac[t0 + j];
+          if (t0 + j < Tn) b[j] += ac[t0 + j];
       } else {
         const int fb = as_const(a.fac_begin)[ch], fe = as_const(a.fac_begin)[ch + 1];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (t0 + j < T) b[j] += letter_value(a, xn, fb, fe, t0 + j, -1) * ac[t0 + j];
+          if (t0 + j < Tn) b[j] += letter_value(a, xn, fb, fe, t0 + j, -1) * ac[t0 + j];
       }
     }
     // the lane's own run, from its last step to its first
@@ -457,7 +470,7 @@ __global__ __launch_bounds__(256) void grad_max_suffix_kernel(GradArgs a, int fi
 #pragma unroll
     for (int j = 3; j >= 0; --j) {
       const double r = b[j] + in;
-      if (t0 + j < T) av[t0 + j] = h[j] ? r : 0.0;
+      if (t0 + j < Tn) av[t0 + j] = h[j] ? r : 0.0;
       in = h[j] ? 0.0 : r;
     }
   }
@@ -510,6 +523,7 @@ __global__ __launch_bounds__(256) void grad_input_kernel(GradArgs a) {
   const int64_t row = blockIdx.x;   // (series, dimension)
   const int64_t N = a.N, D = a.D, T = a.T;
   const int64_t n = row / D, d = row - n * D;
+  const int64_t Tn = series_extent(a, n);
   const double *__restrict__ xn = a.X + n * D * T;
   const double *__restrict__ en = grad_weighted(KIND) ? a.aux + n * a.aux_n : nullptr;
   const int ib = as_const(a.dim_begin)[d], ie = as_const(a.dim_begin)[d + 1];
@@ -517,6 +531,11 @@ __global__ __launch_bounds__(256) void grad_input_kernel(GradArgs a) {
   for (int e = 0; e < kGradTile / 256; ++e) {
     const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
     if (t >= T) continue;
+    if (t >= Tn) {
+      // behind the series' end: nothing was written there, nothing is read
+      a.dX[row * T + t] = 0.0;
+      continue;
+    }
     double acc = 0.0;
     if constexpr (KIND == kGradArctic) {
       // the letter is linear: its coefficient times A_v

@@ -12,6 +12,9 @@
 // written by the walk just before: both passes read it from the cache.
 // Plain loads and stores; all offsets are 64-bit; every access is guarded by 0 <= t < T.  The
 // spec table is workgroup-uniform and read through the constant address space (scalar loads).
+// PER-SERIES CUTS (FR_SIEVE_SERIES_CUTS on every kind): series n reads the cut
+// rows at cuts + n * cut_stride - resolved on the host for its own length, END's wrap included -,
+// so a band ends at the series' end and no position lies behind it; cut_stride 0: one table.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -24,6 +27,7 @@ __global__ __launch_bounds__(256) void sieve_pick_kernel(const double *__restric
                                                          const PickSieve *__restrict__ spec,
                                                          int n_sieves,
                                                          const int64_t *__restrict__ cuts,
+                                                         int64_t cut_stride,
                                                          const double *__restrict__ q, int F,
                                                          double *__restrict__ feat,
                                                          int32_t *__restrict__ pos) {
@@ -36,10 +40,10 @@ __global__ __launch_bounds__(256) void sieve_pick_kernel(const double *__restric
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int32_t *__restrict__ sp = reinterpret_cast<const int32_t *>(spec);
   for (int s = 0; s < n_sieves; ++s) {
-    const int kind = as_const(sp)[6 * s], cut_begin = as_const(sp)[6 * s + 1], C1 = as_const(sp)[6 * s + 2];
+    const int kind = as_const(sp)[6 * s] & 0xff, cut_begin = as_const(sp)[6 * s + 1], C1 = as_const(sp)[6 * s + 2];
     const int q_begin = as_const(sp)[6 * s + 3], Q = as_const(sp)[6 * s + 4] - 1;
     const int64_t f0 = out + as_const(sp)[6 * s + 5];
-    const int64_t *__restrict__ cut = cuts + cut_begin;
+    const int64_t *__restrict__ cut = cuts + n * cut_stride + cut_begin;
     if (kind == FR_SIEVE_END_K) {
       for (int j = tid; j < C1 - 1; j += 256) {
         int64_t idx = cut[j + 1] - 1;
@@ -104,13 +108,13 @@ __global__ __launch_bounds__(256) void sieve_pick_kernel(const double *__restric
 }
 
 hipError_t launch_sieve_pick(const double *A, int64_t K, int64_t N, int64_t T, const PickSieve *spec,
-                             int n_sieves, const int64_t *cuts, const double *q, int F, double *feat,
-                             int32_t *pos, hipStream_t st) {
+                             int n_sieves, const int64_t *cuts, int64_t cut_stride, const double *q,
+                             int F, double *feat, int32_t *pos, hipStream_t st) {
   if (K <= 0 || N <= 0 || n_sieves <= 0) return hipSuccess;
-  if (K * N > 0x7fffffffLL || T < 1 || T > 0x7fffffffLL || F < 1 || F > kPickMaxFeatures)
+  if (K * N > 0x7fffffffLL || T < 1 || T > 0x7fffffffLL || F < 1 || F > kPickMaxFeatures || cut_stride < 0)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(sieve_pick_kernel, dim3((unsigned)(K * N)), dim3(256), 0, st, A, K, N, T, spec,
-                     n_sieves, cuts, q, F, feat, pos);
+                     n_sieves, cuts, cut_stride, q, F, feat, pos);
   return hipGetLastError();
 }
 

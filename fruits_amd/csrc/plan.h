@@ -183,6 +183,10 @@ struct Plan {
   LastLaunch last_launch;         // FR_INFO_LAST_LAUNCH: the most recent run_walk, fused ones too (under mu)
   void *jit = nullptr;   // run-time compiled static programs (capi_plan.h: JitState), or nullptr
   void *grad = nullptr;  // tables of the backward pass (capi_grad.cpp: GradTables), or nullptr (under mu)
+  // per-series lengths of the following backward passes (fr_plan_set_grad_lengths), the caller's
+  // device table, or nullptr (under mu)
+  const int32_t *grad_lengths = nullptr;
+  int64_t grad_lengths_n = 0;
   int device = -1;     // HIP device the uploaded tables live on (-1: nothing uploaded yet)
   std::mutex mu;       // guards `programs`, `cos->d_blob` and `device` (uploads at run time)
 

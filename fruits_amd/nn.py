@@ -27,6 +27,19 @@ iterated sum, ``(N, K * F)`` in ``Fruit``'s column order, for any of the three c
 above.  Each such feature is one element of one row, so the backward pass is handed the position
 of that element and the feature's gradient - a sparse upstream (DESIGN.md 4.14.4,
 ``fr_sieve_pick``, ``fr_iss_backward_picked``) - and no ``(N, K, T)`` tensor outlives the call.
+
+PER-SERIES LENGTHS.  The three dense entries and the four layers' ``forward``
+take ``lengths=``, an integer array or tensor ``(N,)`` with ``1 <= lengths[n] <= T``
+(``fruits_amd.lengths.check_lengths``): series ``n`` is ``X[n, :, :lengths[n]]``, and the tail
+behind it has to be finite and influences nothing.  ``Y[n, :, :L_n]`` and ``X.grad[n, :, :L_n]``
+are those of the call on the truncated series, a weighted call with the ``Indices`` / ``Plateaus``
+row of length ``L_n``; ``Y[n, :, L_n:]`` is unspecified finite data that carries no gradient - the
+upstream gradient there is never read - and ``X.grad[n, :, L_n:]`` is ``+0.0``.  The features of
+series ``n`` are those of the truncated series (``END`` wraps by ``L_n``, ``MAX`` / ``MIN``
+segments end at ``L_n``); their functional form is ``iss_features_ragged``, their layer takes
+the lengths in ``forward`` - lengths belong to a batch, not to a module.  The lengths are
+validated on the host: a device tensor costs one download (and a synchronisation) per call.
+Lengths that all equal ``T`` take the dense path, ``lengths=None`` is untouched.
 """
 from __future__ import annotations
 
@@ -41,10 +54,11 @@ from .iss.cos import CosWISS
 from .iss.iss import ISS, ISSMode
 from .iss.semiring import Arctic, Bayesian, Reals
 from .iss.words.word import SimpleWord
+from .lengths import check_lengths
 from .sieving import END, MAX, MIN
 
 __all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "weighted_iss", "WeightedISSLayer",
-           "iss_features", "FeatureLayer", "backward_calls"]
+           "iss_features", "iss_features_ragged", "FeatureLayer", "backward_calls"]
 
 _calls = {"backward": 0}
 _OPS: dict = {}      # the functional form's ISS objects by (word strings, mode, device), oldest first
@@ -140,6 +154,18 @@ def _check_input(op: ISS, X) -> None:
                         "through the host")
 
 
+def _ragged_lengths(lengths, N: int, T: int) -> Optional[np.ndarray]:
+    """``lengths`` of a batch ``(N, D, T)`` validated on the host (``check_lengths``: its errors)
+    as an int64 array - or None where the batch is dense: no lengths, or all equal to ``T``.  A
+    torch tensor is brought to the host first: one download for a device tensor."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.detach().cpu().numpy()
+    L = check_lengths(lengths, N, T)
+    return None if N == 0 or bool((L == T).all()) else L
+
+
 def _prefix_program(op: ISS):
     """(plan, row_prefix): the plan whose words are the distinct prefixes of the words, each with
     depth 1 (row j = the iterated sum of prefix j; the construction CosWISS._program uses for
@@ -198,40 +224,49 @@ _weighted_prefix_program = _prefix_program      # (the name the weighted sums' c
 
 class _ISSFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, X, op):
+    def forward(ctx, X, op, lengths=None):
         Xc = X.contiguous()
-        Y = op.transform_device(Xc)          # (K, N, T)
+        if lengths is not None and op.weighting is not None:
+            # (row n of the lookup: the weighting's row for a series of lengths[n] steps)
+            Y = op.transform_device(Xc, lookup_d=op.lookup_device(Xc, lengths))
+        else:
+            # (the iterated sums are causal: the padded walk is the ragged one below each end)
+            Y = op.transform_device(Xc)          # (K, N, T)
         ctx.op = op
-        ctx.save_for_backward(Xc)
+        ctx.lengths = lengths                # (host; None: dense)
+        # (a ragged batch keeps its (N,) int32 device lengths beside X; a dense one X alone)
+        ctx.save_for_backward(Xc, *(() if lengths is None else (nat.to_device(lengths, dtype=np.int32),)))
         return Y.permute(1, 0, 2)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, G):
-        Xc, = ctx.saved_tensors
+        Xc, len_d = (*ctx.saved_tensors, None)[:2]
         op = ctx.op
         plan, row_prefix = _prefix_program(op)
         with torch.cuda.device(Xc.device):
             if op.weighting is not None:
-                # (the lookup is a function of T alone: formed again, not kept; the prefix plan
-                # itself never runs - the entry forms the carried sums - so it need not fit the LDS)
-                lookup = op.lookup_device(Xc)
+                # (the lookup is a function of T - and the lengths - alone: formed again, not kept;
+                # the prefix plan itself never runs - the entry forms the carried sums - so it need
+                # not fit the LDS)
+                lookup = op.lookup_device(Xc, ctx.lengths)
                 _calls["backward"] += 1
-                return nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix), None
+                return nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix, lengths_d=len_d), None, None
             S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
             _calls["backward"] += 1
             # (a max semiring: the rises of the recomputed running maxima are the segments' heads)
             entry = nat.iss_backward if isinstance(op.semiring, Reals) else nat.iss_backward_max
-            return entry(plan, Xc, S, G, row_prefix), None
+            return entry(plan, Xc, S, G, row_prefix, lengths_d=len_d), None, None
 
 
-def _apply(op: ISS, X):
+def _apply(op: ISS, X, lengths=None):
     _check_input(op, X)
     # (an unweighted backward pass runs the prefix plan: it has to fit a workgroup's LDS)
     if op.weighting is None and len(op.words) > 0 and not _prefix_program(op)[0].fits(int(X.shape[2])):
         raise NotImplementedError("the words name more input dimensions than a workgroup stages")
+    lengths = _ragged_lengths(lengths, int(X.shape[0]), int(X.shape[2]))
     with torch.cuda.device(X.device):
-        return _ISSFunction.apply(X, op)
+        return _ISSFunction.apply(X, op, lengths)
 
 
 def _cached_op(key, make) -> ISS:
@@ -264,8 +299,8 @@ class _Layer(torch.nn.Module):
     def mode(self) -> ISSMode:
         return self.op.mode
 
-    def forward(self, X):
-        return _apply(self.op, X)
+    def forward(self, X, lengths=None):
+        return _apply(self.op, X, lengths)
 
     def extra_repr(self) -> str:
         return f"{len(self.op.words)} words, {self.op.mode.name}"
@@ -284,13 +319,15 @@ def _reals_op(X, words, mode, semiring, weighting) -> ISS:
     return _cached_op(key, lambda: ISS(words, mode=mode, semiring=semiring, weighting=weighting))
 
 
-def iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, weighting=None):
+def iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, weighting=None, lengths=None):
     """Iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the row order of
     ``ISS(words, mode).transform(X)`` and with its bits; differentiable with respect to ``X``.
-    ``words`` may also be an ``ISS`` that carries the configuration."""
+    ``words`` may also be an ``ISS`` that carries the configuration.  ``lengths``: per-series
+    lengths ``(N,)`` (the module's docstring): ``Y[n, :, :L_n]`` and ``X.grad[n, :, :L_n]`` are
+    those of the truncated series, ``X.grad[n, :, L_n:]`` is ``+0.0``."""
     op = _reals_op(X, words, mode, semiring, weighting)
     _check_config(op)
-    return _apply(op, X)
+    return _apply(op, X, lengths)
 
 
 class ISSLayer(_Layer):
@@ -327,7 +364,7 @@ def _cached_max_op(X, words, mode, semiring) -> ISS:
     return _cached_op(key, lambda: _max_op(words, mode, semiring))
 
 
-def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
+def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None, lengths=None):
     """Arctic (max, +) or Bayesian (max, x) iterated sums ``(N, K, T)`` of the device tensor ``X``
     ``(N, D, T)``, in the row order of ``ISS(words, mode, semiring=semiring).transform(X)`` and
     with its bits; differentiable with respect to ``X``.  ``semiring``: an ``Arctic()`` or a
@@ -339,10 +376,11 @@ def max_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, semiring=None):
     ``(i_p, ..., i_1)`` is lexicographically smallest, the rule of ``Arctic(argmax=True)`` - which
     is a valid subgradient at a tie.  For Bayesian this holds on positive inputs; where ``X`` has
     negative values the reference's recursion (a running maximum per letter) is not the maximum
-    over index tuples, and the gradient is that of the recursion as the reference defines it."""
+    over index tuples, and the gradient is that of the recursion as the reference defines it.
+    ``lengths``: per-series lengths ``(N,)``, as ``iss`` takes them."""
     op = _cached_max_op(X, words, mode, semiring)
     _check_max_config(op)
-    return _apply(op, X)
+    return _apply(op, X, lengths)
 
 
 class MaxISSLayer(_Layer):
@@ -381,7 +419,7 @@ def _cached_weighted_op(X, words, mode, weighting) -> ISS:
     return _cached_op(key, lambda: _weighted_op(words, mode, weighting))
 
 
-def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
+def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None, lengths=None):
     """Weighted Reals iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)``, in the
     row order of ``ISS(words, mode, weighting=weighting).transform(X)`` and with its bits;
     differentiable with respect to ``X``.  ``weighting``: an ``Indices`` or a ``Plateaus``, total or
@@ -390,10 +428,12 @@ def weighted_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None):
 
     The backward pass is ``fr_iss_backward_weighted``: it forms the sums the
     forward pass carries from letter to letter with a prefix scan per inner trie node, then the
-    adjoint with suffix scans, the exp factors ``exp(+-g alpha)`` as constants."""
+    adjoint with suffix scans, the exp factors ``exp(+-g alpha)`` as constants.
+    ``lengths``: per-series lengths ``(N,)``, as ``iss`` takes them; series ``n`` is weighted with
+    the ``Indices`` / ``Plateaus`` row of a series of ``L_n`` steps, forward and backward."""
     op = _cached_weighted_op(X, words, mode, weighting)
     _check_weighted_config(op)
-    return _apply(op, X)
+    return _apply(op, X, lengths)
 
 
 class WeightedISSLayer(_Layer):
@@ -501,38 +541,80 @@ class _Head:
                                            nat.to_device(q) if len(q) else None)
         return hit
 
+    def host_series_tables(self, lengths):
+        """``host_tables`` for series of these lengths: every kind carries
+        ``FR_SIEVE_SERIES_CUTS`` and the cuts are an ``(N, row)`` table - series n's row holds
+        every sieve's cut row as the sieve itself resolves it for a series of ``lengths[n]``
+        steps (``_series_cut_rows``: lengths.resolve_cuts, and resolve_end_cuts with END's wrap
+        and its IndexError for a cut outside a series)."""
+        spec, cuts, qs, feat, at = [], [], [], 0, 0
+        for sieve in self.sieves:
+            rows = sieve._series_cut_rows(lengths)
+            q = np.zeros(0) if isinstance(sieve, END) else _thresholds(sieve)
+            spec.append([sieve._kind | nat.FR_SIEVE_SERIES_CUTS, at, rows.shape[1],
+                         sum(len(v) for v in qs), len(q), feat])
+            cuts.append(rows)
+            qs.append(q)
+            at += rows.shape[1]
+            feat += sieve.nfeatures()
+        return (np.asarray(spec, dtype=np.int32), np.ascontiguousarray(np.concatenate(cuts, axis=1), dtype=np.int64),
+                np.concatenate(qs).astype(np.float64))
+
+    def series_tables(self, lengths, device):
+        """The device tables of ``host_series_tables``.  Spec and thresholds are kept like the
+        dense ones; the cut table is the batch's and dies with the call."""
+        spec, cuts, q = self.host_series_tables(lengths)
+        key = ("series", str(device), q.tobytes())
+        with torch.cuda.device(device):
+            hit = self._tables.get(key)
+            if hit is None:
+                if len(self._tables) >= _OPS_KEPT:
+                    self._tables.pop(next(iter(self._tables)))
+                hit = self._tables[key] = (spec, nat.to_device(spec, dtype=np.int32),
+                                           nat.to_device(q) if len(q) else None)
+            return hit[0], hit[1], nat.to_device(cuts, dtype=np.int64), hit[2]
+
     def __getstate__(self):
         return {"sieves": self.sieves, "F": self.F, "_tables": {}}
 
 
 class _FeatureFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, X, op, head):
+    def forward(ctx, X, op, head, lengths=None):
         Xc = X.contiguous()
         N, T = int(Xc.shape[0]), int(Xc.shape[2])
-        spec, spec_d, cuts_d, q_d = head.tables(T, Xc.device)
-        Y = op.transform_device(Xc)          # (K, N, T): dies with this call
+        if lengths is None:
+            spec, spec_d, cuts_d, q_d = head.tables(T, Xc.device)
+        else:
+            # (an END cut outside a series: IndexError here, before any launch)
+            spec, spec_d, cuts_d, q_d = head.series_tables(lengths, Xc.device)
+        if lengths is not None and op.weighting is not None:
+            Y = op.transform_device(Xc, lookup_d=op.lookup_device(Xc, lengths))
+        else:
+            Y = op.transform_device(Xc)          # (K, N, T): dies with this call
         feat, pos = nat.sieve_pick(Y, spec, spec_d, cuts_d, q_d, head.F)
         ctx.op = op
-        ctx.save_for_backward(Xc, pos)
+        ctx.lengths = lengths                # (host; None: dense)
+        ctx.save_for_backward(Xc, pos, *(() if lengths is None else (nat.to_device(lengths, dtype=np.int32),)))
         return feat.view(N, -1)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        Xc, pos = ctx.saved_tensors
+        Xc, pos, len_d = (*ctx.saved_tensors, None)[:3]
         op = ctx.op
         plan, row_prefix = _prefix_program(op)
         # (N, K * F), tiny: an expanded scalar or a slice is made contiguous, never dense in T
         w = g.to(device=Xc.device, dtype=torch.float64).contiguous().view(pos.shape)
         with torch.cuda.device(Xc.device):
             if op.weighting is not None:
-                lookup = op.lookup_device(Xc)
+                lookup = op.lookup_device(Xc, ctx.lengths)
                 _calls["backward"] += 1
-                return nat.iss_backward_picked(plan, Xc, pos, w, row_prefix, lookup_d=lookup), None, None
+                return (nat.iss_backward_picked(plan, Xc, pos, w, row_prefix, lookup_d=lookup, lengths_d=len_d),
+                        None, None, None)
             S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
             _calls["backward"] += 1
-            return nat.iss_backward_picked(plan, Xc, pos, w, row_prefix, Sd=S), None, None
+            return nat.iss_backward_picked(plan, Xc, pos, w, row_prefix, Sd=S, lengths_d=len_d), None, None, None
 
 
 def _feature_op(X, words, mode, semiring, weighting):
@@ -552,10 +634,11 @@ def _feature_op(X, words, mode, semiring, weighting):
     return _reals_op(X, words, mode, semiring, None), _check_config
 
 
+_LENGTHS_ELSEWHERE = ("lengths= is not taken here: lengths belong to a batch - pass them to the layer's call, "
+                      "FeatureLayer(...)(X, lengths=...), or to nn.iss_features_ragged(X, lengths, ...)")
+
+
 def _apply_features(op: ISS, head: _Head, X, lengths=None):
-    if lengths is not None:
-        raise NotImplementedError("lengths= has no backward pass: the differentiable features "
-                                  "take series of one length")
     for sieve in head.sieves:
         if not isinstance(sieve, END):
             _thresholds(sieve)           # (an unfitted sieve: before the input is looked at)
@@ -564,8 +647,9 @@ def _apply_features(op: ISS, head: _Head, X, lengths=None):
         raise NotImplementedError("the words name more input dimensions than a workgroup stages")
     if int(X.shape[2]) < 1:
         raise ValueError("the features of series without a time step are undefined")
+    lengths = _ragged_lengths(lengths, int(X.shape[0]), int(X.shape[2]))
     with torch.cuda.device(X.device):
-        return _FeatureFunction.apply(X, op, head)
+        return _FeatureFunction.apply(X, op, head, lengths)
 
 
 def iss_features(X, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
@@ -586,7 +670,26 @@ def iss_features(X, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semirin
     inside the band ``q_k < v <= q_(k+1)`` (``np.argmax``'s rule, the tie rule of ``max_iss``).
     An empty segment or band is the feature 0 and carries no gradient.  Only ``X`` and the
     ``(N, K, F)`` int32 positions are kept for the backward pass, whose upstream is those
-    positions with the feature gradients."""
+    positions with the feature gradients.
+
+    Series of unequal lengths: ``iss_features_ragged``, or ``FeatureLayer(...)(X, lengths=...)``;
+    ``lengths=`` here raises NotImplementedError."""
+    if lengths is not None:
+        raise NotImplementedError(_LENGTHS_ELSEWHERE)
+    head = _Head(sieves)
+    op, check = _feature_op(X, words, mode, semiring, weighting)
+    check(op)
+    return _apply_features(op, head, X)
+
+
+def iss_features_ragged(X, lengths, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
+                        weighting=None):
+    """``iss_features`` of series of unequal lengths: ``lengths`` ``(N,)`` integers in ``1..T``,
+    series ``n`` is ``X[n, :, :lengths[n]]`` and row ``n`` of the result is ``iss_features`` of that
+    truncated series - ``END`` cuts wrap by ``L_n`` (one outside a series: IndexError, before any
+    launch), ``MAX`` / ``MIN`` segments are clipped to ``[0, L_n]``, every selected position is
+    ``< L_n``, and ``X.grad[n, :, L_n:]`` is ``+0.0``.  Lengths that all equal ``T`` take the
+    dense path."""
     head = _Head(sieves)
     op, check = _feature_op(X, words, mode, semiring, weighting)
     check(op)
@@ -599,8 +702,7 @@ class FeatureLayer(_Layer):
     def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
                  weighting=None, lengths=None) -> None:
         if lengths is not None:
-            raise NotImplementedError("lengths= has no backward pass: the differentiable features "
-                                      "take series of one length")
+            raise NotImplementedError(_LENGTHS_ELSEWHERE)
         head = _Head(sieves)
         # (no X: the layer's ISS is its own, as every layer's)
         op, check = _feature_op(None, words, mode, semiring, weighting)
@@ -611,8 +713,8 @@ class FeatureLayer(_Layer):
     def sieves(self):
         return self.head.sieves
 
-    def forward(self, X):
-        return _apply_features(self.op, self.head, X)
+    def forward(self, X, lengths=None):
+        return _apply_features(self.op, self.head, X, lengths)
 
     def extra_repr(self) -> str:
         return f"{super().extra_repr()}, {self.head.F} features per iterated sum"

@@ -697,7 +697,11 @@ int fr_rows_unshift(const double *d_A, int64_t K, int64_t N, int64_t T, const in
  * the result is bit-identical from run to run.  The first call for a plan (or for another
  * h_row_prefix / D) uploads tables - it allocates and synchronises, so it cannot be captured
  * into a hipGraph; later calls only enqueue one launch per trie depth and one more.
- * FR_E_DIM: a word names a dimension beyond D.  FR_E_LIMIT: N, N * D or T beyond the grid. */
+ * FR_E_DIM: a word names a dimension beyond D.  FR_E_LIMIT: N, N * D or T beyond the grid.
+ * A plan armed with fr_plan_set_grad_lengths: series n is its first L_n steps, T the row stride -
+ * d_dX[n, :, :L_n] is the gradient of the call on the truncated series (its bits), d_dX[n, :, L_n:]
+ * is +0.0, and d_G, d_S and d_X are not read at t >= L_n.  FR_E_ARG when N is not the N the
+ * lengths were set for. */
 int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
                     const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
                     int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
@@ -727,7 +731,8 @@ int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_
  * max over i_1 <= ... <= i_p <= t of sum_k m_k[i_k] (at ties: the maximiser with the smallest
  * reversed index tuple); for Bayesian the same on positive inputs, and the gradient of the
  * reference's recursion as it stands elsewhere.  Bit-identical from run to run and whatever the
- * batch split; the tables are kept with the plan as fr_iss_backward keeps them. */
+ * batch split; the tables are kept with the plan as fr_iss_backward keeps them.  Per-series
+ * lengths (fr_plan_set_grad_lengths) as in fr_iss_backward: no head lies behind a series' end. */
 int fr_iss_backward_max(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
                         const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
                         int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
@@ -758,7 +763,9 @@ int fr_iss_backward_max(fr_plan_t *prefix_plan, const double *d_X, int64_t N, in
  * from run to run and whatever the batch split.  The plan need not fit a workgroup's LDS
  * (fr_plan_fits): the exp tables are read from d_aux.  Tables are kept with the plan as
  * fr_iss_backward keeps them; later calls enqueue the exp tables, two launches per trie depth
- * at most and one more.  FR_E_DIM / FR_E_LIMIT as fr_iss_backward. */
+ * at most and one more.  FR_E_DIM / FR_E_LIMIT as fr_iss_backward.  Per-series lengths
+ * (fr_plan_set_grad_lengths) as in fr_iss_backward; row n of an (N, T) d_lookup is then the
+ * weighting's row for a series of L_n steps, and is not read behind them. */
 int fr_iss_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D,
                              int64_t T, const double *d_lookup, int64_t lookup_rows,
                              const double *d_G, int64_t K, int64_t g_n_stride, int64_t g_k_stride,
@@ -787,7 +794,13 @@ int fr_iss_backward_weighted(fr_plan_t *prefix_plan, const double *d_X, int64_t 
  * MAX / MIN: of the elements t of the segment [cut_j, cut_(j+1)) with q_k < v <= q_(k+1) the
  * largest / smallest, and the FIRST t whose value equals it (np.argmax's rule; -0.0 equals +0.0);
  * an empty segment or band: 0.0 and position -1.  FR_E_ARG for a bad table, on the host and before
- * the launch. */
+ * the launch.
+ * PER-SERIES CUTS: a kind may carry FR_SIEVE_SERIES_CUTS - every sieve of the spec or none (a mix
+ * is FR_E_ARG).  d_cuts is then an (N, n_cuts / N) table (FR_E_ARG when n_cuts is no multiple of
+ * N), series n reads its own row, and cut_begin / C1 index into that row (the cut-row check is
+ * made against the row's length).  Rows ascend in [0, T] behind their leading 0; an END row holds
+ * the index plus one, wrapped for the series' own length already.  With cuts resolved for lengths
+ * L_n every position is < L_n. */
 int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_spec,
                   const int32_t *h_spec, int32_t n_sieves, const int64_t *d_cuts, int64_t n_cuts,
                   const double *d_q, int64_t n_q, int32_t F, double *d_feat, int32_t *d_pos,
@@ -810,12 +823,26 @@ int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int3
  *   d_pos, d_w, K, F   the pairs; 1 <= F <= 256 (FR_E_LIMIT beyond); positions < T
  *   the rest      as in fr_iss_backward
  * FR_E_ARG, on the host and before any launch, for what the plan's own entry refuses and for a
- * null d_pos / d_w. */
+ * null d_pos / d_w.  Per-series lengths (fr_plan_set_grad_lengths) as in fr_iss_backward: a pair
+ * whose position is not below L_n reaches nothing. */
 int fr_iss_backward_picked(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
                            const double *d_S, const double *d_lookup, int64_t lookup_rows,
                            const int32_t *d_pos, const double *d_w, int64_t K, int32_t F,
                            const int32_t *h_row_prefix, double *d_C, double *d_A, double *d_aux,
                            double *d_dX, void *stream);
+
+/* fr_plan_set_grad_lengths: per-series lengths for the backward passes that follow on this plan
+ * - fr_iss_backward, fr_iss_backward_max, fr_iss_backward_weighted, fr_iss_backward_picked - with
+ * exactly N series.  d_lengths: device (N) int32, 1 <= d_lengths[n] <= T (not checked); NULL
+ * clears it.  A plan that was never armed, or is cleared, behaves exactly as before.
+ * It takes no stream: it is state of the plan, delivered like fr_pipeline_set_lengths delivers a
+ * pipeline's.  The pointer is stored under the plan's mutex; a backward entry reads it once, under
+ * the same mutex, and hands it to its kernels by value - so replacing or clearing the lengths
+ * while an earlier backward pass is still queued or running changes nothing of that pass.  The
+ * table belongs to the caller and must stay valid, and unchanged, until the kernels that read it
+ * have run.  FR_E_ARG, on the host: a null plan, N < 0; and from a backward entry, before any
+ * launch, when its N is not the N the lengths were set for (the text names both). */
+int fr_plan_set_grad_lengths(fr_plan_t *prefix_plan, const int32_t *d_lengths, int64_t N);
 
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the

@@ -1,5 +1,5 @@
 """`python tools/grad_bench.py [reps] [launches] [--semiring=reals|arctic|bayesian]
-[--weighting=indices[,total]]` from the root of the tree: what the backward pass of the
+[--weighting=indices[,total]] [--lengths]` from the root of the tree: what the backward pass of the
 differentiable ISS costs (fruits_amd.nn).  `of_weight(2, 3)` EXTENDED on a (2048, 3, 1024) batch that lives on the device - standard
 normal, uniform in [0.25, 1] for Bayesian -: the forward pass alone (under `torch.no_grad()`) and
 forward plus backward (`layer(X).backward(G)` with a dense upstream gradient), `launches`
@@ -17,10 +17,17 @@ upstream gradient.  `picked` is `nn.FeatureLayer` with `[END([-1]), MAX([-1])]`;
 same loss through the rows - `nn.ISSLayer`, then `Y[..., -1]` and `Y.amax(-1)` by torch - which
 needs nothing of this option's own code and so also runs on a tree without `nn.FeatureLayer`.
 Without a value both run interleaved.  The JSON line carries the medians, the smallest and largest
-round and `torch.cuda.max_memory_allocated()` of each route, measured over a step of its own."""
+round and `torch.cuda.max_memory_allocated()` of each route, measured over a step of its own.
+
+`--lengths` makes the batch ragged: per-series lengths uniform on [T / 2, T]
+(seeded), passed as `lengths=` to every layer call - the same padded batch, so the line compares
+with the dense call of a run without the option.  `picked` takes them too; the `dense` feature
+route has no ragged form and stays dense."""
 import json
 import statistics
 import sys
+
+import numpy as np
 
 import fruits_amd as fr
 from fruits_amd import _native as nat
@@ -48,6 +55,9 @@ nat.require_device()
 N, D, T = 2048, 3, 1024
 words = fr.words.of_weight(2, dim=3)
 K = fr.ISS(words, mode=fr.ISSMode.EXTENDED).n_iterated_sums()
+ragged = "--lengths" in sys.argv[1:]
+lengths = np.random.default_rng(0).integers(T // 2, T + 1, N) if ragged else None
+kw = {"lengths": lengths} if ragged else {}
 
 
 def timed(fn):
@@ -77,7 +87,7 @@ def feature_routes():
 
         def picked():
             X.grad = None
-            layer(X).backward(g)
+            layer(X, **kw).backward(g)
 
         routes["picked"] = picked
     return {k: routes[k] for k in features}
@@ -100,6 +110,8 @@ if features is not None:
         peak[k] = [t.cuda.max_memory_allocated() - base, t.cuda.max_memory_allocated()]
     out = {"shape": [N, D, T], "words": "of_weight(2, 3) EXTENDED", "rows": K, "reps": reps,
            "launches": launches, "features": "END([-1]), MAX([-1])"}
+    if ragged:
+        out["lengths"] = [T // 2, T, round(float(lengths.mean()), 1)]
     for k in routes:
         out.update({k + "_step_ms": round(statistics.median(times[k]), 4),
                     k + "_step_minmax_ms": [round(min(times[k]), 4), round(max(times[k]), 4)],
@@ -115,11 +127,11 @@ G = t.randn((N, K, T), dtype=t.float64, device="cuda")
 def pair(layer, X):
     def forward():
         with t.no_grad():
-            layer(X)
+            layer(X, **kw)
 
     def both():
         X.grad = None
-        layer(X).backward(G)
+        layer(X, **kw).backward(G)
 
     return forward, both
 
@@ -149,6 +161,8 @@ for r in range(reps + 1):
                 times[k, i].append(ms)
 out = {"shape": [N, D, T], "words": "of_weight(2, 3) EXTENDED", "rows": K, "reps": reps,
        "launches": launches, "semiring": semiring, "weighting": weighting or None}
+if ragged:
+    out["lengths"] = [T // 2, T, round(float(lengths.mean()), 1)]      # [low, high, mean]
 for k in fns:
     f, b = statistics.median(times[k, 0]), statistics.median(times[k, 1])
     out.update({k + "forward_ms": round(f, 4), k + "forward_backward_ms": round(b, 4),
