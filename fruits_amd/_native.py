@@ -546,6 +546,7 @@ class Pipeline:
             raise (IndexError if "out of bounds" in msg else ValueError)(msg)
         self._h = C.c_void_p(h)
         self.raw_dims = 0    # > 0: fused preparation, run() takes the raw input
+        self._preparation = None     # the arguments of the last set_preparation (ensure_preparation)
         self.rows = plan.rows
         if argmax_lengths is not None:
             lens = np.ascontiguousarray(argmax_lengths, dtype=np.int32)
@@ -607,13 +608,33 @@ class Pipeline:
         """fr_pipeline_set_preparation: ``run`` then takes the RAW (N, D, T) input and forms
         INC / NEW(INC) / STD rows while staging.  False when this plan's kernel has no fused
         staging (the caller keeps materialising the prepared input)."""
-        rc = lib().fr_pipeline_set_preparation(self._h, int(D), int(inc_lag), 1 if as_new else 0,
-                                               int(standardize), float(std_eps))
+        asked = (int(D), int(inc_lag), bool(as_new), int(standardize), float(std_eps))
+        self._preparation = None     # (a call that raises leaves nothing remembered)
+        rc = lib().fr_pipeline_set_preparation(self._h, asked[0], asked[1], 1 if as_new else 0,
+                                               asked[3], asked[4])
         if rc == FR_E_LIMIT:
             self.raw_dims = 0
+            self._preparation = asked     # (remembered as "nothing fused": asking again changes nothing)
             return False
         check(rc, "fr_pipeline_set_preparation")
+        self._preparation = asked
         self.raw_dims = int(D) if (inc_lag or standardize) else 0
+        return self.raw_dims > 0
+
+    def ensure_preparation(self, D: int, inc_lag: int = 0, as_new: bool = False,
+                           standardize: int = 0, std_eps: float = 1e-5) -> bool:
+        """``set_preparation`` unless the pipeline is configured for these arguments already (the
+        library call frees and uploads the preparation table and waits for the device: not per
+        call for a table that has not changed).  The pipeline remembers the arguments of the last
+        ``set_preparation`` it accepted or refused with FR_E_LIMIT.  Without a chain
+        (``inc_lag == 0 and standardize == 0``) nothing is done while nothing is fused, whatever
+        ``D``.  Returns ``raw_dims > 0``."""
+        if inc_lag or standardize:
+            stale = self._preparation != (D, inc_lag, as_new, standardize, std_eps)
+        else:
+            stale = self.raw_dims > 0
+        if stale:
+            self.set_preparation(D, inc_lag, as_new, standardize, std_eps)
         return self.raw_dims > 0
 
     # plans up to this size are compiled as straight-line code by a prepare nobody waits for, and

@@ -17,10 +17,12 @@ from typing import Callable, Generator, Literal, Optional, Union
 import numpy as np
 
 from . import _native as nat
+from . import preparation as _prep
 from .cache import SharedSeedCache
 from .callback import AbstractCallback
 from .iss.iss import ISS
-from .lengths import check_lengths, require_support
+from .iss.weighting import _PathLength, _SeriesIndependent
+from .lengths import check_lengths, require_support, with_lengths
 from .preparation.abstract import Preparateur
 from .seed import Seed
 from .sieving.abstract import FeatureSieve
@@ -444,17 +446,17 @@ class FruitSlice:
                     prep.fit(np.broadcast_to(0.0, tuple(int(v) for v in Xd.shape)))
                 else:
                     prep.fit(fit_on)
-            Xd = (prep._transform_device(Xd) if lengths_d is None
-                  else prep._transform_device(Xd, lengths_d=lengths_d))
+            Xd = with_lengths(prep._transform_device, Xd, lengths_d=lengths_d)
             for cb in callbacks:
                 cb.on_preparateur(nat.to_host(Xd))
         return Xd
 
     def _iterate_iss_device(self, Xd, iss_index: int = 0, upto: Optional[int] = None,
-                            lengths=None) -> Generator:
+                            lengths=None, indices=None) -> Generator:
         """Yields every iterated sum as an (N, T) device tensor, in the order of
         fruits/fruit.py:440-454 (chained ISS feed each row to the next ISS).  ``upto``: stop in
-        front of that ISS of the chain and yield its (N, 1, T) INPUTS instead."""
+        front of that ISS of the chain and yield its (N, 1, T) INPUTS instead.  ``indices``
+        (single ISS): the iterated sums of these words only, formed by ONE launch."""
         if upto is not None and iss_index == upto:
             yield Xd
             return
@@ -462,8 +464,11 @@ class FruitSlice:
             yield Xd[:, 0, :]
             return
         iss = self._iss[iss_index]
+        if indices is not None:
+            yield from iss.transform_device(Xd, indices=indices)
+            return
         # (``lengths``: a single ISS - the gate of a ragged batch has seen to that)
-        lookup = iss.lookup_device(Xd) if lengths is None else iss.lookup_device(Xd, lengths=lengths)
+        lookup = with_lengths(iss.lookup_device, Xd, lengths=lengths)
         for s, e in iss.word_batches(int(Xd.shape[0]), int(Xd.shape[2])):
             block = iss.transform_device(Xd, s, e, lookup)
             for k in range(block.shape[0]):
@@ -635,81 +640,80 @@ class FruitSlice:
         # everything else - Bayesian, whose rows come out time-shifted, chains that end in
         # generic words, generic next to weighted simple words - materialises through
         # ISS.transform_device.
-        generic = bool(self._iss) and getattr(self._iss[-1], "_has_generic", False)
+        iss = self._iss[-1] if self._iss else None
+        generic = getattr(iss, "_has_generic", False)
         if generic:
-            iss = self._iss[-1]
             used = range(len(iss.words)) if indices is None else indices
             if (D is None or len(self._iss) != 1 or iss.needs_unshift() or getattr(iss, "_argmax", False)
                     or (iss.weighting is not None and len(iss._class_runs(used)) > 1)):
                 return None
             key = (key, "D", int(D))
-        if key in self._fused_cache:
-            return self._fused_cache[key]
-        entry = None
-        if self._fusable():
-            iss = self._iss[-1]
-            iss._check_supported()
-            if hasattr(iss, "_arm_plan"):     # CosWISS dropout: the plan carries the mask
-                iss._check_supported()
-            argmax = None
-            if getattr(iss, "_argmax", False):   # (the pipeline's rows are the argmax rows, not the plan's)
-                argmax = [len(iss.words[i]) for i in (range(len(iss.words)) if indices is None else indices)]
-            if indices is None:
-                plan = (iss._plan_indices(range(len(iss.words)), D=D) if generic
-                        else iss._plan(0, len(iss.words)))
-                rows = range(plan.rows if argmax is None else iss._rows_of(0, len(iss.words)))
-                if hasattr(iss, "_arm_plan"):
-                    iss._arm_plan(plan, tuple(range(len(iss.words))), T)
+        if key not in self._fused_cache:
+            self._fused_cache[key] = self._build_fused(T, indices, chain_row, D if generic else None, ragged)
+        return self._fused_cache[key]
+
+    def _build_fused(self, T: int, indices, chain_row: int, D: Optional[int], ragged: bool):
+        """``_fused`` behind its cache: the pipeline of the iterated sums of the words ``indices``
+        (None: all) of the last ISS, or None.  ``D``: the dimensions a plan of generic words is
+        lowered for."""
+        if not self._fusable():
+            return None
+        iss = self._iss[-1]
+        iss._check_supported()
+        words = tuple(range(len(iss.words)) if indices is None else indices)
+        # (argmax: the pipeline's rows are the argmax rows, not the plan's)
+        argmax = [len(iss.words[i]) for i in words] if getattr(iss, "_argmax", False) else None
+        plan = iss._plan_indices(words) if D is None else iss._plan_indices(words, D=D)
+        if hasattr(iss, "_arm_plan"):     # CosWISS dropout: the plan carries the mask
+            iss._arm_plan(plan, words, T)
+        rows = [chain_row * iss.n_iterated_sums() + r for r in self._rows_of_words(iss, words)]
+        acting = self._sieves_extended[rows[0]] if self._sieves_extended and rows else self._sieves
+        specs, cut_columns, n_slots = self._pipeline_specs(acting, T, ragged)
+        if not rows or not plan.fits(T):
+            return None
+        try:
+            pipe = nat.Pipeline(plan, specs, T, argmax_lengths=argmax)
+        except ValueError:
+            return None
+        assert pipe.rows == len(rows)
+        pipe.set_quantiles(self._threshold_table(rows, pipe.q_stride))
+        pipe._cut_columns = [(slot0, sv) for slot0, sv in cut_columns.values()]
+        pipe._cut_slots = n_slots
+        return pipe
+
+    @staticmethod
+    def _rows_of_words(iss, words) -> list:
+        """The iterated sums (rows of the whole word list, reference order) of ``words``."""
+        first = [0, *np.cumsum([iss._depth(i) for i in range(len(iss.words))]).tolist()]
+        return [r for i in words for r in range(first[i], first[i + 1])]
+
+    def _threshold_table(self, rows, q_stride: int) -> np.ndarray:
+        """The pipeline's ``(len(rows), q_stride)`` thresholds: per iterated sum in ``rows`` those
+        of its fitted sieve copies, in sieve order (END has none) - read from the arrays of
+        ``_FittedRows`` or from the copy objects, whichever ``_sieves_extended`` holds."""
+        fitted = self._sieves_extended
+        quant = np.zeros((len(rows), q_stride))
+        off = 0
+        for i, sv in enumerate(self._sieves):
+            leaf, kind, _, _ = _reduced(sv)
+            if kind == nat.FR_SIEVE_END:
+                continue
+            n = _n_thresholds(leaf)
+            if isinstance(fitted, _FittedRows):     # (the thresholds of all rows are arrays already)
+                th = fitted.thresholds(i, rows)
+                if th is None:
+                    leaf._get_unfitted_quantiles()
+                    th = leaf._quantiles
             else:
-                plan = iss._plan_indices(indices, D=D) if generic else iss._plan_indices(indices)
-                if hasattr(iss, "_arm_plan"):
-                    iss._arm_plan(plan, tuple(indices), T)
-                first = np.concatenate([[0], np.cumsum(
-                    [iss._depth(i) for i in range(len(iss.words))])]).astype(int)
-                rows = [r for i in indices for r in range(first[i], first[i + 1])]
-            if chain_row:
-                rows = [chain_row * iss.n_iterated_sums() + r for r in rows]
-            acting = (self._sieves_extended[rows[0]] if self._sieves_extended and len(rows)
-                      else self._sieves)
-            specs, cut_columns, n_slots = self._pipeline_specs(acting, T, ragged)
-            try:
-                pipe = (nat.Pipeline(plan, specs, T, argmax_lengths=argmax)
-                        if len(rows) and plan.fits(T) else None)
-            except ValueError:
-                pipe = None
-            if pipe is not None:
-                assert pipe.rows == len(rows)
-                quant = np.zeros((len(rows), pipe.q_stride))
-                lazy = isinstance(self._sieves_extended, _FittedRows)
-                if lazy:     # (the thresholds of all rows are arrays already)
-                    off = 0
-                    for i, sv in enumerate(self._sieves):
-                        sv, kind, _, _ = _reduced(sv)
-                        if kind == nat.FR_SIEVE_END:
-                            continue
-                        th = self._sieves_extended.thresholds(i, rows)
-                        if th is None:
-                            sv._get_unfitted_quantiles()
-                            th = sv._quantiles
-                        quant[:, off:off + _n_thresholds(sv)] = th
-                        off += _n_thresholds(sv)
-                for k, row in enumerate(() if lazy else rows):
-                    sieves = self._sieves_extended[row] if self._sieves_extended else self._sieves
-                    off = 0
-                    for sv in sieves:
-                        sv, kind, _, _ = _reduced(sv)
-                        if kind == nat.FR_SIEVE_END:
-                            continue
-                        if not sv.requires_fitting:
-                            sv._get_unfitted_quantiles()
-                        quant[k, off:off + _n_thresholds(sv)] = sv._quantiles
-                        off += _n_thresholds(sv)
-                pipe.set_quantiles(quant)
-                pipe._cut_columns = [(slot0, sv) for slot0, sv in cut_columns.values()]
-                pipe._cut_slots = n_slots
-                entry = pipe
-        self._fused_cache[key] = entry
-        return entry
+                th = []
+                for row in rows:
+                    copy = _reduced(fitted[row][i])[0] if fitted else leaf
+                    if not copy.requires_fitting:
+                        copy._get_unfitted_quantiles()
+                    th.append(copy._quantiles)
+            quant[:, off:off + n] = th
+            off += n
+        return quant
 
     @staticmethod
     def _pipeline_specs(acting, T: int, ragged: bool = False):
@@ -823,8 +827,7 @@ class FruitSlice:
         """(inc_lag, as_new, standardize, eps) when the preparateur chain is one the fused
         launch forms while staging the raw input - [INC | NEW(INC)] [STD], the chains of the
         experiment fruits - else None (the prepared input is then materialised)."""
-        from .preparation.transform import INC, STD
-        from .preparation.wrapper import NEW
+        INC, STD = _prep.INC, _prep.STD     # (the preparateurs, not the sieves of the same names)
         level = os.environ.get("FRUITS_AMD_FUSED_PREP", "1")
         if level == "0":
             return None
@@ -842,7 +845,7 @@ class FruitSlice:
                     and isinstance(p._lag(T), int) and 1 <= p._lag(T) < T)
         if preps and plain_inc(preps[0]):
             lag = preps.pop(0)._lag(T)
-        elif preps and type(preps[0]) is NEW and preps[0]._preparateur is not None \
+        elif preps and type(preps[0]) is _prep.NEW and preps[0]._preparateur is not None \
                 and plain_inc(preps[0]._preparateur):
             lag, as_new = preps.pop(0)._preparateur._lag(T), True
         if preps and type(preps[0]) is STD and preps[0]._separately:
@@ -855,7 +858,6 @@ class FruitSlice:
         # writes.  Safe are only weightings that do not look at the data (Indices, Plateaus) and
         # path lengths of the cache's RAW input; a Custom function, or any user subclass, gets
         # the materialised preparation.
-        from .iss.weighting import _PathLength, _SeriesIndependent
         for iss in self._iss:
             w = getattr(iss, "weighting", None)
             if w is None or isinstance(w, _SeriesIndependent):
@@ -969,46 +971,6 @@ class FruitSlice:
                   cache: Optional[SharedSeedCache] = None, lengths=None) -> np.ndarray:
         return nat.to_host(self.transform_device(X, callbacks, cache, lengths=lengths))
 
-    def _transform_ragged(self, X: np.ndarray, lengths: np.ndarray, cache):
-        """``transform_device`` for a batch with per-series lengths: the launches of the dense
-        call - one fused launch where the slice fuses, on the ragged entry of ``_fused_cache``
-        (generic kernel instances: a pipeline with per-series cuts has no compiled one) - with
-        every extent, statistic and divisor taken per series."""
-        t = nat.torch()
-        iss = self._iss[0]
-        Xd = cache.input_device(X) if cache._input is X else nat.to_device(X)
-        N, T = int(Xd.shape[0]), int(Xd.shape[2])
-        lengths_d = nat.to_device(lengths.astype(np.int32), dtype=np.int32)
-        chain = self._fusable_preparation(T)
-        fused = self._fused(T, ragged=True) if chain is not None else None
-        if fused is not None:
-            if getattr(fused, "_prep_chain", None) != (chain, int(Xd.shape[1])):
-                fused.set_preparation(int(Xd.shape[1]), chain[0], chain[1], chain[2], chain[3])
-                fused._prep_chain = (chain, int(Xd.shape[1]))
-            if fused.raw_dims > 0:
-                self._attach(cache)
-                self._arm_lengths(fused, lengths, lengths_d)
-                return fused.run(Xd, iss.lookup_device(Xd, lengths=lengths))
-        Pd = self._prepare_device(Xd, cache, lengths_d=lengths_d)
-        self._attach(cache)
-        fused = self._fused(T, D=int(Pd.shape[1]), ragged=True)
-        if fused is not None:
-            if fused.raw_dims > 0:       # (was configured for raw input by another call)
-                fused.set_preparation(int(Pd.shape[1]))
-                fused._prep_chain = None
-            self._arm_lengths(fused, lengths, lengths_d)
-            weighted = fused.plan.weighting != nat.FR_W_NONE
-            return fused.run(Pd, iss.lookup_device(Pd, lengths=lengths) if weighted else None)
-        feats = t.zeros((N, self.nfeatures()), dtype=t.float64, device=Pd.device)
-        col = 0
-        for i, itsum in enumerate(self._iterate_iss_device(Pd, lengths=lengths)):
-            sieves = self._sieves_extended[i] if self._sieves_extended else self._sieves
-            for sieve in sieves:
-                sieve._cache = cache
-                sieve.transform_device(itsum, feats, col, lengths=lengths)
-                col += sieve.nfeatures()
-        return feats
-
     def transform_device(self, X: np.ndarray,
                          callbacks: Optional[list[AbstractCallback]] = None,
                          cache: Optional[SharedSeedCache] = None, lengths=None):
@@ -1020,71 +982,108 @@ class FruitSlice:
         lengths = self._ragged_lengths(X, lengths)
         if cache is None:
             cache = SharedSeedCache(X)
-        # (lengths that all equal T: the dense call itself, bit for bit)
-        if lengths is not None and not (lengths == X.shape[2]).all():
-            if callbacks:
-                raise NotImplementedError("callbacks do not support per-series lengths")
-            return self._transform_ragged(X, lengths, cache)
-        t = nat.torch()
+        if lengths is not None and (lengths == X.shape[2]).all():
+            lengths = None      # (lengths that all equal T: the dense call itself, bit for bit)
+        if lengths is not None and callbacks:
+            raise NotImplementedError("callbacks do not support per-series lengths")
         Xd = cache.input_device(X) if cache._input is X else nat.to_device(X)
-        ffn = getattr(self._iss[-1], "_ffn_size", None) is not None
-        if not callbacks and len(self._iss) == 1 and not ffn:
-            # INC / NEW(INC) / STD formed while the fused launch stages the RAW rows: no
-            # prepared tensor is written (one launch [+ the STD statistics pre-pass])
-            T = int(Xd.shape[2])
-            chain = self._fusable_preparation(T)
-            fused = self._fused(T) if chain is not None else None
-            if fused is not None:
-                if getattr(fused, "_prep_chain", None) != (chain, int(Xd.shape[1])):
-                    fused.set_preparation(int(Xd.shape[1]), chain[0], chain[1], chain[2], chain[3])
-                    fused._prep_chain = (chain, int(Xd.shape[1]))
-                if fused.raw_dims > 0:
-                    self._attach(cache)
-                    self._arm_series_cuts(fused, int(Xd.shape[0]), T, cache)
-                    self._auto_prepare(fused, int(Xd.shape[0]), T)
-                    return fused.run(Xd, self._iss[0].lookup_device(Xd))
-        Pd = self._prepare_device(Xd, cache, callbacks)
-        for cb in callbacks:
-            cb.on_preparation_end(nat.to_host(Pd))
-        self._attach(cache)
-        if ffn and not callbacks and self._fusable():
-            return self._transform_ffn_fused(Pd, cache)
-        fused = None if callbacks else self._fused(int(Pd.shape[2]), D=int(Pd.shape[1]))
-        if fused is not None and len(self._iss) > 1:
-            return self._transform_chain_fused(Pd, cache)
-        if fused is not None:
-            Vd, iss = Pd, self._iss[0]
-            if getattr(iss, "_has_generic", False):
-                # generic words over Reals / Arctic: still ONE walk + sieve launch, on the virtual rows
-                # formed from the prepared input (no in-launch preparation)
-                low, _ = iss._lowered(range(len(iss.words)), int(Pd.shape[1]))
-                Vd = iss.virtual_rows(Pd, low)
-            if fused.raw_dims > 0:       # (was configured for raw input by another call)
-                fused.set_preparation(int(Vd.shape[1]))
-                fused._prep_chain = None
-            self._arm_series_cuts(fused, int(Pd.shape[0]), int(Pd.shape[2]), cache)
-            self._auto_prepare(fused, int(Pd.shape[0]), int(Pd.shape[2]))
-            # (an unweighted plan - every lowered one - takes no lookup: none is computed)
-            weighted = fused.plan.weighting != nat.FR_W_NONE
-            return fused.run(Vd, iss.lookup_device(Pd) if weighted else None)
-        feats = t.zeros((X.shape[0], self.nfeatures()), dtype=t.float64, device=Pd.device)
-        col = 0
-        for i, itsum in enumerate(self._iterate_iss_device(Pd)):
-            for cb in callbacks:
-                cb.on_iterated_sum(nat.to_host(itsum))
-            sieves = self._sieves_extended[i] if self._sieves_extended else self._sieves
-            for sieve in sieves:
-                sieve._cache = cache
-                nf = sieve.nfeatures()
-                sieve.transform_device(itsum, feats, col)
-                for cb in callbacks:
-                    cb.on_sieve(nat.to_host(feats[col:col + nf]))
-                col += nf
+        feats = self._run(Xd, cache, lengths=lengths, callbacks=callbacks)
         if callbacks:
             out = nat.to_host(feats)
             for cb in callbacks:
                 cb.on_sieving_end(out)
         return feats
+
+    def _run(self, Xd, cache, *, indices=None, lengths=None, callbacks=()):
+        """The route ladder from the device batch ``Xd`` to the features of a fitted slice
+         - of the whole slice, of a ragged batch (``lengths``: validated, not all
+        T) or of the words ``indices`` alone (a rank's share, fruits_amd.parallel):
+
+        1. one fused launch on the RAW batch when the preparateur chain fuses into the staging;
+        2. else the prepared input is materialised, and then, the first that applies:
+           a. a CosWISS with the randomised ffn runs word by word (``_transform_ffn_fused``);
+           b. a chain of ISS runs one fused launch per row of the chain (``_transform_chain_fused``);
+           c. one fused launch on the prepared input - on the virtual rows for generic words;
+           d. every iterated sum is materialised and every sieve copy runs over it.
+
+        Callbacks see every intermediate result, so they take 2d."""
+        ffn = getattr(self._iss[-1], "_ffn_size", None) is not None
+        # What cannot come with lengths or with a share of the words: the gate refuses chains, ffn
+        # and generic words for a ragged batch (_ragged_lengths, ISS._supports_lengths) and
+        # transform_device callbacks; slice_transform_sharded shards a single ISS only.
+        assert lengths is None or not (len(self._iss) > 1 or ffn or self._iss[0]._has_generic
+                                       or callbacks or indices is not None)
+        assert indices is None or (len(self._iss) == 1 and not callbacks)
+        iss = self._iss[0]
+        ragged = None if lengths is None else (
+            lengths, nat.to_device(lengths.astype(np.int32), dtype=np.int32))
+        self._attach(cache)
+        if not callbacks and len(self._iss) == 1 and not ffn:
+            # INC / NEW(INC) / STD formed while the fused launch stages the RAW rows: no
+            # prepared tensor is written (one launch [+ the STD statistics pre-pass])
+            D, T = int(Xd.shape[1]), int(Xd.shape[2])
+            chain = self._fusable_preparation(T)
+            fused = (self._fused(T, indices=indices, ragged=ragged is not None)
+                     if chain is not None else None)
+            if fused is not None and fused.ensure_preparation(D, *chain):
+                return self._launch(fused, Xd, with_lengths(iss.lookup_device, Xd, lengths=lengths),
+                                    cache, ragged)
+        Pd = self._prepare_device(Xd, cache, callbacks, lengths_d=None if ragged is None else ragged[1])
+        for cb in callbacks:
+            cb.on_preparation_end(nat.to_host(Pd))
+        if ffn and not callbacks and self._fusable():
+            return self._transform_ffn_fused(Pd, cache, words=indices)
+        D, T = int(Pd.shape[1]), int(Pd.shape[2])
+        # (a share of generic words materialises: the pipeline of generic words is asked for with
+        # the D its virtual rows are formed for, and they are formed for the whole word list)
+        fused = None if callbacks or ffn else self._fused(
+            T, indices=indices, D=D if indices is None else None, ragged=ragged is not None)
+        if fused is not None and len(self._iss) > 1:
+            return self._transform_chain_fused(Pd, cache)
+        if fused is not None:
+            Vd = Pd
+            if getattr(iss, "_has_generic", False):
+                # generic words over Reals / Arctic: still ONE walk + sieve launch, on the virtual rows
+                # formed from the prepared input (no in-launch preparation)
+                low, _ = iss._lowered(range(len(iss.words)), D)
+                Vd = iss.virtual_rows(Pd, low)
+            fused.ensure_preparation(int(Vd.shape[1]))     # (prepared input: nothing to fuse)
+            # (an unweighted plan - every lowered one - takes no lookup: none is computed)
+            weighted = fused.plan.weighting != nat.FR_W_NONE
+            lookup = with_lengths(iss.lookup_device, Pd, lengths=lengths) if weighted else None
+            return self._launch(fused, Vd, lookup, cache, ragged)
+        rows = (range(self.niteratedsums()) if indices is None
+                else self._rows_of_words(iss, indices))
+        t = nat.torch()
+        per_sum = sum(sieve.nfeatures() for sieve in self._sieves)
+        feats = t.zeros((int(Pd.shape[0]), len(rows) * per_sum), dtype=t.float64, device=Pd.device)
+        col = 0
+        for row, itsum in zip(rows, self._iterate_iss_device(Pd, lengths=lengths, indices=indices)):
+            for cb in callbacks:
+                cb.on_iterated_sum(nat.to_host(itsum))
+            sieves = self._sieves_extended[row] if self._sieves_extended else self._sieves
+            for sieve in sieves:
+                sieve._cache = cache
+                nf = sieve.nfeatures()
+                with_lengths(sieve.transform_device, itsum, feats, col, lengths=lengths)
+                for cb in callbacks:
+                    cb.on_sieve(nat.to_host(feats[col:col + nf]))
+                col += nf
+        return feats
+
+    def _launch(self, pipe, Xin, lookup, cache, ragged=None, auto_prepare: bool = True):
+        """One fused launch of ``pipe`` on ``Xin`` - the raw batch, the prepared input, a row of a
+        chain, the copies of an ffn word - behind its per-call set-up: the per-batch tables and
+        the pipeline's own kernels.  ``ragged``: (lengths, their int32 device copy)."""
+        N, T = int(Xin.shape[0]), int(Xin.shape[2])
+        if ragged is not None:
+            # (never _auto_prepare: a pipeline with per-series cuts has no compiled instance)
+            self._arm_lengths(pipe, *ragged)
+        else:
+            self._arm_series_cuts(pipe, N, T, cache)
+            if auto_prepare:
+                self._auto_prepare(pipe, N, T)
+        return pipe.run(Xin, lookup)
 
     def _transform_chain_fused(self, Pd, cache):
         """Chained ISS (fruits/fruit.py:440-454): the rows of the chain in front of the last ISS
@@ -1098,10 +1097,9 @@ class FruitSlice:
         feats = t.empty((N, self.nfeatures()), dtype=t.float64, device=Pd.device)
         for r, Xin in enumerate(self._iterate_iss_device(Pd, 0, upto=len(self._iss) - 1)):
             pipe = self._fused(T, chain_row=r)
-            if pipe.raw_dims > 0:
-                pipe.set_preparation(1)
-            self._arm_series_cuts(pipe, N, T, cache)
-            feats[:, r * width:(r + 1) * width] = pipe.run(Xin, last.lookup_device(Xin))
+            pipe.ensure_preparation(1)
+            feats[:, r * width:(r + 1) * width] = self._launch(
+                pipe, Xin, last.lookup_device(Xin), cache, auto_prepare=False)
         return feats
 
     def _transform_ffn_fused(self, Pd, cache, words=None):
@@ -1127,8 +1125,8 @@ class FruitSlice:
             for f in range(F):
                 nat.coswiss_ffn(Pd, iss._A[w, f], iss._b[w, f], iss._C[w, f], Z[f])
             nat.check(nat.lib().fr_coswiss_set_input_stride(pipe.plan._h, N * D * T))
-            self._arm_series_cuts(pipe, N, T, cache)
-            feats[:, slot * width:(slot + 1) * width] = pipe.run(Z[0], None)
+            feats[:, slot * width:(slot + 1) * width] = self._launch(pipe, Z[0], None, cache,
+                                                                     auto_prepare=False)
         return feats
 
     def fit_transform(self, X: np.ndarray, lengths=None) -> np.ndarray:

@@ -46,6 +46,18 @@ def require_support(seeds) -> None:
                 f"{type(seed).__name__} ({seed}) does not support per-series lengths")
 
 
+def with_lengths(method, *args, **lengths):
+    """``method(*args)`` for a dense batch, ``method(*args, lengths=...)`` for a ragged one
+    (``lengths``: the one keyword the method takes them by, None for a dense batch).
+
+    The rule: lengths are handed only to seeds that said yes (``require_support``).  A dense call
+    never names the parameter, so a user's subclass written without it keeps working."""
+    for value in lengths.values():
+        if value is None:
+            return method(*args)
+    return method(*args, **lengths)
+
+
 def resolve_cuts(cut, lengths) -> np.ndarray:
     """``(N, len(cut) + 1)`` int64 segment boundaries of integer cuts, resolved per series as the
     reference resolves them for a series of that length (SegmentSieve._get_transformed_cuts,

@@ -244,50 +244,13 @@ def slice_transform_sharded(slc, Xb, cache, rank: int, world: int, group=None,
 
 
 def _device_block(slc, iss, Xd, cache, indices, depths, per_sum):
-    """The feature columns of the words ``indices`` of a slice on the device batch ``Xd``."""
-    from . import _native as nat
-    t = nat.torch()
-    N = int(Xd.shape[0])
-    rr = row_ranges(depths)
-    n_rows = sum(depths[i] for i in indices)
+    """The feature columns of the words ``indices`` of a slice on the device batch ``Xd``: the
+    slice's own route ladder (``FruitSlice._run``) over the rank's share - one fused launch where
+    the whole slice takes one, word by word for a CosWISS with the randomised ffn."""
     if not indices:
-        return t.zeros((N, 0), dtype=t.float64, device=Xd.device)
-    # the rank's share in ONE launch on the RAW batch where the slice's preparation fuses into
-    # the staging (INC / NEW(INC) / STD): as in FruitSlice.transform_device
-    T = int(Xd.shape[2])
-    # (a CosWISS with the randomised ffn reads a transformed copy of the input per (word,
-    # frequency) - fruits/iss/cos.py:93-137: its pipelines must not be run on the plain batch;
-    # the rank's words go through FruitSlice._transform_ffn_fused's word-by-word launches)
-    ffn = getattr(iss, "_ffn_size", None) is not None
-    chain = None if ffn else slc._fusable_preparation(T)
-    fused = slc._fused(T, indices=indices) if chain is not None else None
-    if fused is not None and fused.set_preparation(int(Xd.shape[1]), *chain):
-        slc._attach(cache)
-        slc._arm_series_cuts(fused, N, T, cache)
-        slc._auto_prepare(fused, N, T)
-        return fused.run(Xd, iss.lookup_device(Xd))
-    Pd = slc._prepare_device(Xd, cache)
-    slc._attach(cache)
-    if ffn and slc._fusable():
-        return slc._transform_ffn_fused(Pd, cache, words=indices)
-    fused = None if ffn else slc._fused(int(Pd.shape[2]), indices=indices)
-    if fused is not None:      # the rank's share in ONE launch, no (K_r, N, T) tensor
-        fused.set_preparation(int(Pd.shape[1]))     # (prepared input: nothing to fuse)
-        slc._arm_series_cuts(fused, int(Pd.shape[0]), int(Pd.shape[2]), cache)
-        slc._auto_prepare(fused, int(Pd.shape[0]), int(Pd.shape[2]))
-        return fused.run(Pd, iss.lookup_device(Pd))
-    feats = t.zeros((N, n_rows * per_sum), dtype=t.float64, device=Pd.device)
-    block = iss.transform_device(Pd, indices=indices)
-    col = k = 0
-    for i in indices:
-        for row in range(*rr[i]):
-            sieves = slc._sieves_extended[row] if slc._sieves_extended else slc._sieves
-            for sieve in sieves:
-                sieve._cache = cache
-                sieve.transform_device(block[k], feats, col)
-                col += sieve.nfeatures()
-            k += 1
-    return feats
+        import torch
+        return torch.zeros((int(Xd.shape[0]), 0), dtype=torch.float64, device=Xd.device)
+    return slc._run(Xd, cache, indices=indices)
 
 
 def transform_sharded(fruit, X=None, rank: Optional[int] = None, world: Optional[int] = None,

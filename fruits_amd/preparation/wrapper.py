@@ -7,6 +7,7 @@ from typing import Optional, Union
 import numpy as np
 
 from .. import _native as nat
+from ..lengths import with_lengths
 from .abstract import Preparateur
 
 __all__ = ["DIM", "NEW"]
@@ -51,8 +52,7 @@ class DIM(Preparateur):
         dim = np.arange(D)[self._dim]      # (numpy's index rules: negative entries, range errors)
         idx = nat.to_device(np.ascontiguousarray(dim, dtype=np.int64), dtype=np.int64)
         sub = t.index_select(Xd, 1, idx).contiguous()
-        transformed = (self._preparateur._transform_device(sub) if lengths_d is None
-                       else self._preparateur._transform_device(sub, lengths_d=lengths_d))
+        transformed = with_lengths(self._preparateur._transform_device, sub, lengths_d=lengths_d)
         rest = np.delete(np.arange(D), self._dim)
         if rest.size == 0:
             return transformed
@@ -98,12 +98,8 @@ class NEW(Preparateur):
 
     def _transform_device(self, Xd, lengths_d=None):
         t = nat.torch()
-        if self._preparateur is None:
-            extra = Xd
-        elif lengths_d is None:
-            extra = self._preparateur._transform_device(Xd)
-        else:
-            extra = self._preparateur._transform_device(Xd, lengths_d=lengths_d)
+        extra = Xd if self._preparateur is None else with_lengths(
+            self._preparateur._transform_device, Xd, lengths_d=lengths_d)
         return t.cat((Xd, extra), dim=1).contiguous()
 
     def _copy(self) -> "NEW":

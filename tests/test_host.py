@@ -1157,6 +1157,48 @@ def test_bundle_compiles_without_a_device(tmp_path, monkeypatch):
         assert all(os.path.getsize(out / f) > 4096 for f in files)
 
 
+def test_pipeline_remembers_its_preparation(monkeypatch):
+    """``Pipeline.ensure_preparation`` calls the library only when the pipeline is configured for
+    something else; ``set_preparation`` always calls and records what it set, a refusal
+    (FR_E_LIMIT: remembered as "nothing fused") included.  The ABI entry is replaced with a
+    counting stub: creating a pipeline needs no device, uploading the table does."""
+    from fruits_amd.fruit import FruitSlice
+    words = fr.words.of_weight(2, 2)
+    plan = fr.ISS(words, mode=fr.ISSMode.EXTENDED)._plan(0, len(words))
+    specs, _, _ = FruitSlice._pipeline_specs([fr.sieving.NPI(q=(0.5, 1.0)), fr.sieving.END()], 256)
+    pipe = nat.Pipeline(plan, specs, 256)
+    calls, answer = [], [0]
+
+    def stub(handle, *args):
+        calls.append(args)
+        return answer[0]
+    monkeypatch.setattr(nat.lib(), "fr_pipeline_set_preparation", stub)
+
+    assert pipe.ensure_preparation(2) is False and calls == []       # nothing fused, no chain: nothing to do
+    assert pipe.set_preparation(2, 1) is True and pipe.raw_dims == 2 and len(calls) == 1
+    assert pipe.ensure_preparation(2, 1) is True and len(calls) == 1           # equal arguments: no call
+    assert pipe.ensure_preparation(2, 1, False, 0, 1e-5) is True and len(calls) == 1
+    assert pipe.set_preparation(2, 1) is True and len(calls) == 2              # the setter always calls
+    assert pipe.set_preparation(3, 1, True, 2, 1e-3) is True and len(calls) == 3
+    assert pipe.ensure_preparation(2, 1) is True and len(calls) == 4           # other arguments: one call
+    assert calls[-1] == (2, 1, 0, 0, 1e-5) and pipe.raw_dims == 2
+    assert pipe.ensure_preparation(2, 1) is True and len(calls) == 4
+    assert pipe.ensure_preparation(5) is False and len(calls) == 5             # no chain while fused: unfuse
+    assert pipe.raw_dims == 0
+    assert pipe.ensure_preparation(7) is False and len(calls) == 5             # ... whatever D
+    answer[0] = nat.FR_E_LIMIT
+    assert pipe.ensure_preparation(2, 1) is False and len(calls) == 6          # refused ...
+    assert pipe.ensure_preparation(2, 1) is False and len(calls) == 6          # ... and remembered
+    assert pipe.set_preparation(2, 1) is False and len(calls) == 7
+    answer[0] = 0
+    assert pipe.ensure_preparation(2, 0, False, 1) is True and len(calls) == 8
+    answer[0] = nat.FR_E_HIP                                                   # any other failure raises
+    with pytest.raises(nat.NativeError):
+        pipe.set_preparation(2, 1)
+    answer[0] = 0
+    assert pipe.ensure_preparation(2, 0, False, 1) is True and len(calls) == 10   # nothing remembered of it
+
+
 def test_fitted_rows_table():
     """What a device-side fit leaves in FruitSlice._sieves_extended (fruit.py, _FittedRows): the
     thresholds of all rows as arrays, formed like SegmentSieve._set_quantiles_from_stats forms one
