@@ -26,7 +26,8 @@ FR_SIEVE_SEGMENTS = 0x200   # OR-ed into PPV / CPV at fr_pipeline_create: bands 
 FR_SIEVE_SERIES_CUTS = 0x100   # OR-ed into a kind: the sieve's cuts are slots of a per-series table
 (FR_INFO_ROWS, FR_INFO_NODES, FR_INFO_LEVELS, FR_INFO_DIMS_USED, FR_INFO_MAX_DIM,
  FR_INFO_ALPHAS, FR_INFO_GROUPS, FR_INFO_SHARED, FR_INFO_STAGED_ROWS, FR_INFO_JIT_PROGRAMS,
- FR_INFO_AOT_PROGRAM, FR_INFO_STATIC_TAIL, FR_INFO_LAST_LAUNCH, FR_INFO_LAST_WHOLE) = range(14)
+ FR_INFO_AOT_PROGRAM, FR_INFO_STATIC_TAIL, FR_INFO_LAST_LAUNCH, FR_INFO_LAST_WHOLE,
+ FR_INFO_GRAD_ROWS) = range(15)
 # kernel families of FR_INFO_LAST_LAUNCH (csrc/plan.h, WalkFamily)
 WALK_FAMILIES = (None, "interpreter", "static_aot", "static_jit", "lean", "packed", "fused",
                  "fused_packed", "fused_jit", "fused_pieces")
@@ -1303,6 +1304,34 @@ def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=N
             prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
             C.c_int64(rows), dptr(G), C.c_int64(K), sn, sk, st,
             _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
+    return dX
+
+
+def coswiss_grad_rows(plan: "CosPlan"):
+    """(rows of d_S, rows of d_A): the scratch ``fr_iss_backward`` needs for a CosWISS plan, in
+    rows of ``N * T`` doubles (fr_plan_info, FR_INFO_GRAD_ROWS)."""
+    word = int(plan.info(FR_INFO_GRAD_ROWS))
+    return word >> 32, word & 0xffffffff
+
+
+def iss_backward_cos(plan: "CosPlan", Xd, G, row_unit, work=None):
+    """fr_iss_backward with a CosWISS plan: the gradient ``(N, D, T)`` of the plan's rows with
+    respect to ``Xd``.  ``plan``: the CosWISS plan itself; ``G`` the upstream gradient as an
+    ``(N, K, T)`` device tensor of any strides; ``row_unit`` ``(K)`` int32 host array, the row of
+    the plan (word-major, F rows per word) that row k of ``G`` belongs to - several k may name one
+    row, a row none.  ``work``: a scratch of ``(rows of d_S + rows of d_A) * N * T`` doubles
+    (``coswiss_grad_rows``) if the caller keeps one."""
+    t = torch()
+    (N, D, T, K, _), rp, (sn, sk, st) = _backward_args(plan, Xd, G, row_unit)
+    rows_s, rows_a = coswiss_grad_rows(plan)
+    cells = N * T
+    work = _backward_scratch(work, (rows_s + rows_a) * cells, "(rows of d_S + rows of d_A) * N * T", Xd).view(-1)
+    dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
+    # (the scratch in two parts; an empty part still gets a distinct address)
+    parts = [C.c_void_p(work.data_ptr() + 8 * o) for o in (rows_a * cells, 0)]
+    check(lib().fr_iss_backward(plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), parts[0],
+                                dptr(G), C.c_int64(K), sn, sk, st, _i32p(rp), parts[1], dptr(dX),
+                                stream_ptr()), "fr_iss_backward")
     return dX
 
 

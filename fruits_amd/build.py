@@ -28,7 +28,8 @@ CAPI = ("capi_core", "capi_plan", "capi_walk", "capi_pipeline", "capi_select", "
 LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep"),
                  "select_partition.h": ("kernels_select",),
                  "capi_common.h": CAPI,
-                 "capi_plan.h": ("capi_plan", "capi_walk", "capi_pipeline"),
+                 "capi_plan.h": ("capi_plan", "capi_walk", "capi_pipeline", "capi_grad"),
+                 "grad_frame.h": ("kernels_grad", "kernels_grad_cos"),
                  "capi_pipeline.h": ("capi_walk", "capi_pipeline")}
 
 
@@ -45,6 +46,8 @@ def units():
            ("kernels_letters", "kernels_letters.hip", ["-ffp-contract=off"]), ("plan", "plan.cpp", []),
            # the backward pass: every product rounded, as the derived bound of its tests counts them
            ("kernels_grad", "kernels_grad.hip", ["-ffp-contract=off"]),
+           # ... and the adjoint of the factorised CosWISS kernels, counted the same way
+           ("kernels_grad_cos", "kernels_grad_cos.hip", ["-ffp-contract=off"]),
            # the selecting sieves of the differentiable features: comparisons and moves alone
            ("kernels_pick", "kernels_pick.hip", []),
            ("jit", "jit.cpp", []),

@@ -5,12 +5,15 @@
 // parents, children, letters, exp tables - is read off the plan the plan compiler built (plan.cpp);
 // the kernels are those of kernels_grad.hip.  One body (run_backward) serves the four entries.
 // fr_plan_set_grad_lengths arms a plan with per-series lengths for the backward passes that follow.
+// fr_iss_backward handed a CosWISS plan runs the adjoint of the factorised CosWISS kernels
+// (run_backward_cos, kernels_grad_cos.hip): the plan itself, no prefix plan and no trie.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <vector>
 
 #include "capi_common.h"
+#include "capi_plan.h"
 #include "kernels.h"
 
 using namespace fr::capi;
@@ -244,6 +247,65 @@ std::string build_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K
   return "";
 }
 
+// The backward tables of a CosWISS plan (kernels.h, CosGradArgs): the letters as {dimension,
+// exponent} pairs, the rows of G of every unit, the units some row names (level_nodes) and per
+// input dimension the {row of DZ, factor} pairs of those units' letters - a unit no row names
+// is neither launched nor gathered.
+std::string build_cos_tables(const fr::Plan &p, const int32_t *row_prefix, int64_t K, int64_t D,
+                             GradTables &g) {
+  const fr::CosProgram &c = *p.cos;
+  const int units = c.W * c.F;
+  std::vector<std::vector<int32_t>> grows((size_t)units);
+  for (int64_t k = 0; k < K; ++k) {
+    if (row_prefix[k] < 0 || row_prefix[k] >= units)
+      return "row " + std::to_string(k) + " of the gradient names row " + std::to_string(row_prefix[k]) +
+             " of " + std::to_string(units);
+    grows[(size_t)row_prefix[k]].push_back((int32_t)k);
+  }
+  g.row_prefix.assign(row_prefix, row_prefix + K);
+  g.fac_begin.h.assign(1, 0);
+  g.fac.h.clear();
+  const int letters = (int)c.fac_begin.size() - 1;
+  for (int l = 0; l < letters; ++l) {
+    const size_t begin = g.fac.h.size();
+    for (int j = c.fac_begin[l]; j < c.fac_begin[l + 1]; ++j) {
+      const int32_t dim = c.factors[j] & fr::FAC_ROW_MASK, sign = (c.factors[j] & fr::FAC_DIV) ? -1 : 1;
+      if (dim >= D) return "a factor beyond the input's dimensions";
+      if (g.fac.h.size() > begin && g.fac.h[g.fac.h.size() - 2] == dim) {
+        g.fac.h.back() += sign;
+      } else {
+        g.fac.h.push_back(dim);
+        g.fac.h.push_back(sign);
+      }
+    }
+    g.fac_begin.h.push_back((int32_t)(g.fac.h.size() / 2));
+  }
+  g.g_begin.h.assign(1, 0);
+  g.g_row.h.clear();
+  g.level_nodes.h.clear();
+  std::vector<std::vector<int32_t>> items((size_t)D);
+  for (int u = 0; u < units; ++u) {
+    g.g_row.h.insert(g.g_row.h.end(), grows[(size_t)u].begin(), grows[(size_t)u].end());
+    g.g_begin.h.push_back((int32_t)g.g_row.h.size());
+    if (grows[(size_t)u].empty()) continue;
+    g.level_nodes.h.push_back(u);
+    const int w = u / c.F, f = u % c.F;
+    for (int l = c.letter_begin[w]; l < c.letter_begin[w + 1]; ++l)
+      for (int32_t j = g.fac_begin.h[l]; j < g.fac_begin.h[l + 1]; ++j) {
+        items[(size_t)g.fac.h[2 * j]].push_back(l * c.F + f);
+        items[(size_t)g.fac.h[2 * j]].push_back(j);
+      }
+  }
+  g.dim_begin.h.assign(1, 0);
+  g.dim_item.h.clear();
+  for (int64_t d = 0; d < D; ++d) {
+    g.dim_item.h.insert(g.dim_item.h.end(), items[(size_t)d].begin(), items[(size_t)d].end());
+    g.dim_begin.h.push_back((int32_t)(g.dim_item.h.size() / 2));
+  }
+  g.dims = D;
+  return "";
+}
+
 int upload_tables(GradTables &g) {
   size_t size = 0;
   for (const TableSlot &s : kDeviceTables)
@@ -291,7 +353,8 @@ int ensure_tables(fr::Plan &p, const std::string &who, const int32_t *h_row_pref
                     (K == 0 || std::memcmp(g->row_prefix.data(), h_row_prefix, (size_t)K * 4) == 0);
   if (same) return FR_OK;
   GradTables fresh;
-  const std::string why = build_tables(p, h_row_prefix, K, D, fresh);
+  const std::string why = p.cos ? build_cos_tables(p, h_row_prefix, K, D, fresh)
+                                : build_tables(p, h_row_prefix, K, D, fresh);
   if (!why.empty()) return fail(FR_E_ARG, who + ": " + why);
   if (nothing_to_do) return FR_OK;
   if (stream_is_capturing(st))
@@ -458,6 +521,82 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   return launched(fr::launch_grad_input(a, kind, st), "backward input launch", limit);
 }
 
+// fr_iss_backward with a CosWISS plan: the checks in run_backward's order, the
+// tables, the trig rows behind the rows of DZ in d_A, the unit kernel, dX.  d_S takes the
+// recomputed u rows: it is written, never read before that.
+int run_backward_cos(fr_plan_t *plan, const double *d_X, int64_t N, int64_t D, int64_t T, double *d_S,
+                     const double *d_G, int64_t K, int64_t g_n_stride, int64_t g_k_stride, int64_t g_t_stride,
+                     const int32_t *h_row_prefix, double *d_A, double *d_dX, void *stream) {
+  const std::string who = "fr_iss_backward";
+  if (N < 0 || D < 1 || T < 0 || K < 0 || g_n_stride < 0 || g_k_stride < 0 || g_t_stride < 0)
+    return fail(FR_E_ARG, who + ": bad shape");
+  if (K > 0 && !h_row_prefix) return fail(FR_E_ARG, who + ": null host table");
+  fr::Plan &p = *plan->p;
+  fr::CosProgram &cp = *p.cos;
+  if (p.max_dim > D)
+    return fail(FR_E_DIM, who + ": a word references dimension " + std::to_string(p.max_dim) +
+                              " but the input has only " + std::to_string(D));
+  const int64_t letters = (int64_t)cp.fac_begin.size() - 1;
+  const int64_t u_rows = (letters - cp.W) * cp.F, dz_rows = letters * cp.F;
+  if (N > 0 && T > 0) {
+    if (!d_X || !d_dX || (K > 0 && !d_G) || (u_rows > 0 && !d_S) || (cp.F > 0 && !d_A))
+      return fail(FR_E_ARG, who + ": null device pointer");
+    if (d_X == d_dX) return fail(FR_E_ARG, who + ": the gradient must not alias the input");
+    if (u_rows > 0 && d_S == d_A) return fail(FR_E_ARG, who + ": the scratches must be distinct buffers");
+  }
+  if (cp.exponent > fr::kCosMaxExponent || p.levels > fr::kCosGradLetters)
+    return fail(FR_E_LIMIT, who + ": the CosWISS backward kernels cover exponents <= 8 and words of <= 16 "
+                                  "letters");
+  if (N > 0x7fffffffLL || N * D > 0x7fffffffLL || (T + 1023) / 1024 > 65535)
+    return fail(FR_E_LIMIT, who + ": grid too large (N, N * D or T)");
+  if (cp.d_mask)
+    return fail(FR_E_ARG, who + ": the CosWISS plan has a dropout mask set - the backward pass has no dropout");
+  if (cp.x_unit_stride != 0)
+    return fail(FR_E_ARG, who + ": the CosWISS plan has a per-unit input stride (ffn) - the backward pass "
+                                "differentiates the plain input alone");
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(p.mu);
+  if (p.grad_lengths)
+    return fail(FR_E_ARG, who + ": the plan is armed with per-series lengths (fr_plan_set_grad_lengths) - "
+                                "a CosWISS has none: its angle is a function of T");
+  GradTables *g = nullptr;
+  int rc = ensure_tables(p, who, h_row_prefix, K, D, N == 0 || T == 0, st, g);
+  if (rc != FR_OK || N == 0 || T == 0) return rc;
+  rc = ensure_cos_program(p, cp, st, who.c_str());
+  if (rc != FR_OK) return rc;
+  double *trig = d_A + dz_rows * N * T;
+  rc = launched(fr::launch_trig_tables(cp.d_freqs, cp.F, T, trig, st), "trig_tables launch");
+  if (rc != FR_OK) return rc;
+  fr::CosGradArgs a{};
+  a.X = d_X;
+  a.G = d_G;
+  a.trig = trig;
+  a.U = d_S;
+  a.DZ = d_A;
+  a.dX = d_dX;
+  a.N = N;
+  a.D = D;
+  a.T = T;
+  a.g_n = g_n_stride;
+  a.g_k = g_k_stride;
+  a.g_t = g_t_stride;
+  a.F = cp.F;
+  a.total = cp.total ? 1 : 0;
+  a.letter_begin = cp.d_letter_begin;
+  a.fac_begin = g->fac_begin.d;
+  a.fac = g->fac.d;
+  a.g_begin = g->g_begin.d;
+  a.g_row = g->g_row.d;
+  a.units = g->level_nodes.d;
+  a.dim_begin = g->dim_begin.d;
+  a.dim_item = g->dim_item.d;
+  const std::string limit_text = who + ": grid too large (N, N * D or T)";
+  rc = launched(fr::launch_grad_cos_units(a, cp.exponent, 0, (int)g->level_nodes.h.size(), st),
+                "backward CosWISS unit launch", limit_text.c_str());
+  if (rc != FR_OK) return rc;
+  return launched(fr::launch_grad_cos_input(a, st), "backward CosWISS input launch", limit_text.c_str());
+}
+
 }  // namespace
 
 extern "C" {
@@ -490,6 +629,10 @@ int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_
                     const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
                     int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,
                     double *d_A, double *d_dX, void *stream) {
+  // (a CosWISS plan: its own adjoint; d_S is scratch the entry writes)
+  if (prefix_plan && prefix_plan->p && prefix_plan->p->cos)
+    return run_backward_cos(prefix_plan, d_X, N, D, T, const_cast<double *>(d_S), d_G, K, g_n_stride,
+                            g_k_stride, g_t_stride, h_row_prefix, d_A, d_dX, stream);
   return run_backward({"fr_iss_backward", Entry::kReals, d_S}, prefix_plan, d_X, N, D, T, d_G, K,
                       g_n_stride, g_k_stride, g_t_stride, h_row_prefix, d_A, d_dX, stream);
 }

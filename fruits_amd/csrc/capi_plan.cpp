@@ -333,6 +333,14 @@ int64_t fr_plan_info(const fr_plan_t *plan, int32_t what) {
       return what == FR_INFO_LAST_WHOLE ? (int64_t)q.last_launch.choice.n_whole
                                         : fr::pack_last_launch(q.last_launch);
     }
+    case FR_INFO_GRAD_ROWS: {
+      // a CosWISS plan's backward scratch in (N, T) rows: d_S holds u of the letters behind a
+      // word's first, d_A dz of every letter and the (F, 2, T) trig rows behind them (2 F rows
+      // are reserved whatever N)
+      if (!p.cos) return 0;
+      const int64_t letters = (int64_t)p.cos->fac_begin.size() - 1, F = p.cos->F;
+      return (((letters - p.cos->W) * F) << 32) | (letters * F + 2 * F);
+    }
     default: return fail(FR_E_ARG, "fr_plan_info: unknown selector");
   }
 }

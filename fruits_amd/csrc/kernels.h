@@ -208,4 +208,30 @@ hipError_t launch_grad_prefix(const GradArgs &a, int kind, int first, int count,
 // dX from the finished A (every kind)
 hipError_t launch_grad_input(const GradArgs &a, int kind, hipStream_t st);
 
+// The backward pass of the factorised CosWISS kernels (kernels_grad_cos.hip).
+// Unit j = w * F + f is (word w, frequency f); letter g is a letter of the whole program,
+// letter_begin[w] <= g < letter_begin[w + 1].  Row g * F + f of DZ holds dL/dz of letter g in
+// unit (w, f); row (g - w - 1) * F + f of U the recomputed u of a word's letters behind its first.
+struct CosGradArgs {
+  const double *X;      // (N, D, T)
+  const double *G;      // upstream gradient, element (n, k, t) at n * g_n + k * g_k + t * g_t
+  const double *trig;   // (F, 2, T): sin and cos rows of launch_trig_tables
+  double *U;            // ((letters - W) * F, N, T) scratch
+  double *DZ;           // (letters * F, N, T) scratch
+  double *dX;           // (N, D, T), every element written
+  int64_t N, D, T;
+  int64_t g_n, g_k, g_t;
+  int F, total;
+  const int32_t *letter_begin;           // W + 1
+  const int32_t *fac_begin, *fac;        // a letter: pairs {dimension, exponent != 0}
+  const int32_t *g_begin, *g_row;        // per unit: the rows k of G that name it
+  const int32_t *units;                  // the units some row of G names, ascending
+  const int32_t *dim_begin, *dim_item;   // per input dimension: pairs {row of DZ, index into fac}
+};
+constexpr int kCosGradLetters = 16;   // letters of a word the unit kernel keeps carries for
+// U and DZ of `count` units, units[first ...], for every series; exponent 1 ... kCosMaxExponent
+hipError_t launch_grad_cos_units(const CosGradArgs &a, int exponent, int first, int count, hipStream_t st);
+// dX from the finished DZ
+hipError_t launch_grad_cos_input(const CosGradArgs &a, hipStream_t st);
+
 }  // namespace fr

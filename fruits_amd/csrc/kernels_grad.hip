@@ -81,26 +81,13 @@
 // applied to it gives a value).
 #include <hip/hip_runtime.h>
 
+#include "grad_frame.h"
 #include "kernels.h"
 #include "walk_scan.h"
 
 namespace fr {
 
 constexpr bool grad_weighted(int kind) { return kind == kGradTotal || kind == kGradNonTotal; }
-
-// x^e for e >= 0 by multiplication (e - 1 roundings; x^0 = 1 for every x, a zero included)
-__device__ __forceinline__ double ipow(double x, int e) {
-  if (e == 0) return 1.0;
-  double p = x;
-  for (int i = 1; i < e; ++i) p *= x;
-  return p;
-}
-
-// d/dx x^e = e x^(e-1), the power by multiplication (never m / x: a zero input is an ordinary
-// one); e < 0: e / x^(|e|+1)
-__device__ __forceinline__ double dpow(double x, int e) {
-  return e > 0 ? (double)e * ipow(x, e - 1) : (double)e * (1.0 / ipow(x, 1 - e));
-}
 
 // The letter prod_d x_d[t]^e_d of the factors [fb, fe) at time t of the series whose rows start
 // at `xn`, without factor `skip` (-1: the whole letter): |e_d| roundings per dimension at most.
@@ -124,45 +111,10 @@ __device__ __forceinline__ double exp_factor(const double *__restrict__ aux_n, i
 }
 
 // ------------------------------------------------------------------ the shared frame
-// The chunks of a time axis and the first of the four steps of this lane in chunk c.
+// (the powers, the chunks, the lane maps and the block scan: grad_frame.h)
+// The extent of series n.
 __device__ __forceinline__ int64_t series_extent(const GradArgs &a, int64_t n) {
   return a.len ? (int64_t)as_const(a.len)[n] : a.T;
-}
-__device__ __forceinline__ int64_t grad_chunks(int64_t T) { return (T + kGradChunk - 1) / kGradChunk; }
-__device__ __forceinline__ int64_t forward_t0(int64_t c) { return c * kGradChunk + 4 * (int64_t)threadIdx.x; }
-__device__ __forceinline__ int64_t reversed_t0(int64_t c) {
-  return c * kGradChunk + (kGradChunk - 4) - 4 * (int64_t)threadIdx.x;
-}
-
-// The additive block scan over the lanes' totals, lane 0 first.  Publish: the wave scan; lane 63
-// leaves the wave's total in slot[wave]; returns the sum of the lanes in front within the wave.
-__device__ __forceinline__ double scan_publish(double total, double *slot) {
-  const double incl = wave_inclusive_scan<0>(total);
-  const double excl = wave_shift_right1<0>(incl);
-  if ((threadIdx.x & 63) == 63) slot[threadIdx.x >> 6] = incl;
-  return excl;
-}
-
-// Offset, after the barrier: the wave totals join `carry` in wave order; returns the sum of
-// everything in front of this lane - the chunks before, the waves before, `excl` - and leaves
-// the carry of the next chunk.
-__device__ __forceinline__ double scan_offset(const double *slot, double excl, double &carry) {
-  const int wave = threadIdx.x >> 6;
-  double run = carry, off = carry;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    if (w == wave) off = run;
-    run += slot[w];
-  }
-  carry = run;
-  return off + excl;
-}
-
-// The lane's own inclusive sums, towards its first step (the reversed map: suffix sums over time).
-__device__ __forceinline__ void lane_suffix(double (&b)[4]) {
-  b[2] += b[3];
-  b[1] += b[2];
-  b[0] += b[1];
 }
 
 // b[j] += the rows [gb, ge) of the upstream gradient of the series at `gn`, at the steps t0 + j

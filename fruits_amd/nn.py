@@ -28,6 +28,13 @@ above.  Each such feature is one element of one row, so the backward pass is han
 of that element and the feature's gradient - a sparse upstream (DESIGN.md 4.14.4,
 ``fr_sieve_pick``, ``fr_iss_backward_picked``) - and no ``(N, K, T)`` tensor outlives the call.
 
+``cos_iss(X, words, freqs, exponent, total_weighting)`` and ``CosWISSLayer`` are the cosine
+weighted sums of ``CosWISS``, ``(N, W * F, T)`` with the bits of ``CosWISS.transform_device``.
+Their backward pass hands the CosWISS plan itself to ``fr_iss_backward`` (DESIGN.md 4.14.7,
+csrc/kernels_grad_cos.hip): per (series, word, frequency) a workgroup recomputes the factorised
+forward recursion and runs its adjoint, ``exponent + 1`` suffix scans per letter; a large batch
+runs in blocks of series, which changes no bit.  No ``lengths=``: the angle is a function of ``T``.
+
 PER-SERIES LENGTHS.  The three dense entries and the four layers' ``forward``
 take ``lengths=``, an integer array or tensor ``(N,)`` with ``1 <= lengths[n] <= T``
 (``fruits_amd.lengths.check_lengths``): series ``n`` is ``X[n, :, :lengths[n]]``, and the tail
@@ -51,14 +58,15 @@ from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .iss.cos import CosWISS
-from .iss.iss import ISS, ISSMode
+from .iss.iss import ISS, ISSMode, _device_budget_bytes
 from .iss.semiring import Arctic, Bayesian, Reals
 from .iss.words.word import SimpleWord
 from .lengths import check_lengths
 from .sieving import END, MAX, MIN
 
 __all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "weighted_iss", "WeightedISSLayer",
-           "iss_features", "iss_features_ragged", "FeatureLayer", "backward_calls"]
+           "cos_iss", "CosWISSLayer", "iss_features", "iss_features_ragged", "FeatureLayer",
+           "backward_calls"]
 
 _calls = {"backward": 0}
 _OPS: dict = {}      # the functional form's ISS objects by (word strings, mode, device), oldest first
@@ -67,7 +75,8 @@ _OPS_KEPT = 8
 
 def backward_calls() -> int:
     """Backward passes launched by this process so far (one ``fr_iss_backward``,
-    ``fr_iss_backward_max``, ``fr_iss_backward_weighted`` or ``fr_iss_backward_picked`` each)."""
+    ``fr_iss_backward_max``, ``fr_iss_backward_weighted`` or ``fr_iss_backward_picked`` each; a
+    ``cos_iss`` backward pass counts once however many series blocks it ran in)."""
     return _calls["backward"]
 
 
@@ -82,7 +91,8 @@ def _check_words(op: ISS) -> None:
 def _check_config(op: ISS) -> None:
     """The refusals that depend on the configuration alone: raised before any launch."""
     if isinstance(op, CosWISS):
-        raise NotImplementedError("CosWISS has no backward pass: only the unweighted Reals ISS has")
+        raise NotImplementedError("CosWISS has no backward pass here: only the unweighted Reals ISS has "
+                                  "(the cosine weighted sums are nn.cos_iss / nn.CosWISSLayer)")
     if op.weighting is not None:
         raise NotImplementedError(
             f"a weighting ({type(op.weighting).__name__}) has no backward pass here: the weighted "
@@ -96,7 +106,8 @@ def _check_config(op: ISS) -> None:
 def _check_max_config(op: ISS) -> None:
     """``_check_config`` for ``max_iss``: raised before any launch."""
     if isinstance(op, CosWISS):
-        raise NotImplementedError("CosWISS has no backward pass: only the unweighted ISS has")
+        raise NotImplementedError("CosWISS has no backward pass here: only the unweighted ISS has "
+                                  "(the cosine weighted sums are nn.cos_iss / nn.CosWISSLayer)")
     if isinstance(op.semiring, Reals):
         raise NotImplementedError(
             "max_iss differentiates the max semirings Arctic and Bayesian: the Reals iterated "
@@ -119,7 +130,8 @@ def _check_max_config(op: ISS) -> None:
 def _check_weighted_config(op: ISS) -> None:
     """``_check_config`` for ``weighted_iss``: raised before any launch."""
     if isinstance(op, CosWISS):
-        raise NotImplementedError("CosWISS has no backward pass: only the trie walk's ISS has")
+        raise NotImplementedError("CosWISS has no backward pass here: only the trie walk's ISS has "
+                                  "(the cosine weighted sums are nn.cos_iss / nn.CosWISSLayer)")
     if op.weighting is None:
         raise NotImplementedError(
             "weighted_iss differentiates a weighted ISS: the unweighted iterated sums are "
@@ -449,6 +461,131 @@ class WeightedISSLayer(_Layer):
     def extra_repr(self) -> str:
         return (f"{super().extra_repr()}, "
                 f"{type(self.op.weighting).__name__}{' total' if self.op.weighting.total else ''}")
+
+
+# ----------------------------------------------------------------------- cosine weighted
+_COS_NO_LENGTHS = ("lengths= is not taken here: the forward CosWISS takes no lengths, and its angle "
+                   "pi (i - j) / (f (T - 1)) is a function of T - a series of another length is another "
+                   "weighting, not a truncation")
+
+
+def _check_cos_config(op: CosWISS) -> None:
+    """The refusals of ``cos_iss`` that depend on the configuration alone: raised before any launch."""
+    if not isinstance(op, CosWISS):
+        raise TypeError(f"cos_iss differentiates a CosWISS, not {type(op).__name__}")
+    if op._ffn_size is not None:
+        raise NotImplementedError("a CosWISS with ffn_size has no backward pass: the randomised input "
+                                  "transform is not differentiated")
+    if op._dropout is not None:
+        raise NotImplementedError("a CosWISS with dropout has no backward pass yet")
+    if not op._native():
+        raise NotImplementedError(
+            "this CosWISS has no backward pass: the factorised kernels cover exponents 1 ... "
+            f"{nat.CosPlan.MAX_EXPONENT} and words of at most {nat.CosPlan.MAX_LETTERS} letters "
+            "(and FRUITS_AMD_COSWISS_TERMS=1 switches them off)")
+
+
+def _cos_series_block(plan, N: int, T: int) -> int:
+    """Series per backward call: what the scratch of the call (coswiss_grad_rows) may take of the
+    device budget that ``word_batches`` sizes the forward pass by."""
+    rows = sum(nat.coswiss_grad_rows(plan))
+    return max(1, min(N, _device_budget_bytes() // max(8 * rows * T, 1)))
+
+
+class _CosFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, op):
+        Xc = X.contiguous()
+        Y = op.transform_device(Xc)              # (W * F, N, T)
+        ctx.op = op
+        ctx.save_for_backward(Xc)
+        return Y.permute(1, 0, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        (Xc,) = ctx.saved_tensors
+        op = ctx.op
+        plan = op._plan(0, len(op.words))
+        N, T = int(Xc.shape[0]), int(Xc.shape[2])
+        rows = np.arange(plan.rows, dtype=np.int32)
+        _calls["backward"] += 1
+        with torch.cuda.device(Xc.device):
+            block = _cos_series_block(plan, N, T)
+            if block >= N:
+                return nat.iss_backward_cos(plan, Xc, G, rows), None
+            # (series are independent and every sum has one association: a split changes no bit)
+            dX, work = torch.empty_like(Xc), None
+            for s in range(0, N, block):
+                e = min(s + block, N)
+                if work is None:
+                    work = torch.empty((sum(nat.coswiss_grad_rows(plan)) * (e - s) * T,), dtype=torch.float64,
+                                       device=Xc.device)
+                dX[s:e] = nat.iss_backward_cos(plan, Xc[s:e], G[s:e], rows, work=work)
+            return dX, None
+
+
+def _apply_cos(op: CosWISS, X):
+    _check_input(op, X)
+    with torch.cuda.device(X.device):
+        return _CosFunction.apply(X, op)
+
+
+def _cos_op(X, words, freqs, exponent, total_weighting, ffn_size, dropout) -> CosWISS:
+    if isinstance(words, CosWISS):
+        return words
+    words = list(words)
+    key = None
+    if X is not None and ffn_size is None and dropout is None and all(isinstance(w, SimpleWord) for w in words):
+        key = ("cos", tuple(str(w) for w in words),
+               np.asarray(freqs, dtype=np.float32).tobytes(), int(exponent), bool(total_weighting),
+               str(getattr(X, "device", None)))
+    return _cached_op(key, lambda: CosWISS(words, freqs, exponent=exponent, total_weighting=total_weighting,
+                                           ffn_size=ffn_size, dropout=dropout))
+
+
+def cos_iss(X, words, freqs=None, exponent: int = 2, total_weighting: bool = False, *, ffn_size=None,
+            dropout=None, lengths=None):
+    """Cosine weighted iterated sums ``(N, W * F, T)`` of the device tensor ``X`` ``(N, D, T)``, in
+    the row order of ``CosWISS(words, freqs, exponent, total_weighting).transform(X)`` - word-major,
+    ``F = len(freqs)`` rows per word - and with its bits; differentiable with respect to ``X``.
+    ``words`` may also be a ``CosWISS`` that carries the configuration.
+
+    The backward pass is ``fr_iss_backward`` handed the CosWISS plan: per
+    (series, word, frequency) one workgroup recomputes the forward recursion and runs its adjoint,
+    ``exponent + 1`` suffix scans per letter; the sin / cos tables are constants.  Its scratch is
+    ``2 L - 1`` rows ``(N, T)`` per row of the result, so a large batch runs in blocks of series
+    sized by the device budget (``FRUITS_AMD_ISS_GIB``) - the bits do not depend on the split.
+    Exponents 1 ... 8 and words of at most 16 letters; ``ffn_size``, ``dropout`` and ``lengths=``
+    raise NotImplementedError."""
+    if lengths is not None:
+        raise NotImplementedError(_COS_NO_LENGTHS)
+    if not isinstance(words, CosWISS) and freqs is None:
+        raise TypeError("cos_iss needs freqs, or a CosWISS that carries them")
+    op = _cos_op(X, words, freqs, exponent, total_weighting, ffn_size, dropout)
+    _check_cos_config(op)
+    return _apply_cos(op, X)
+
+
+class CosWISSLayer(_Layer):
+    """``cos_iss`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, freqs=None, exponent: int = 2, total_weighting: bool = False, *,
+                 ffn_size=None, dropout=None) -> None:
+        if not isinstance(words, CosWISS) and freqs is None:
+            raise TypeError("CosWISSLayer needs freqs, or a CosWISS that carries them")
+        super().__init__(_cos_op(None, words, freqs, exponent, total_weighting, ffn_size, dropout),
+                         _check_cos_config)
+
+    def forward(self, X, lengths=None):
+        if lengths is not None:
+            raise NotImplementedError(_COS_NO_LENGTHS)
+        return _apply_cos(self.op, X)
+
+    def extra_repr(self) -> str:
+        op = self.op
+        return (f"{len(op.words)} words, {len(op._freqs)} frequencies, exponent {op._exponent}"
+                f"{', total' if op._total_weighting else ''}")
 
 
 # ----------------------------------------------------------------------- features of the rows

@@ -95,6 +95,10 @@ extern "C" {
                                   static instance (20 bits each, 0: not asked) */
 #define FR_INFO_LAST_WHOLE 13  /* ... and the series it ran as whole-series units (all of them unless
                                   FR_INFO_STATIC_TAIL reports finer ones behind them) */
+#define FR_INFO_GRAD_ROWS 14   /* a CosWISS plan: the scratch fr_iss_backward needs, in rows of N * T
+                                  doubles - bits 0 ... 31 the rows of d_A (F * (letters + 2): dL/dz of
+                                  every letter of every word, then the trig tables), bits 32 and up
+                                  the rows of d_S (F * (letters - W)); 0 for any other plan */
 
 /* sieve kinds of fr_sieve_* and the fused pipeline */
 #define FR_SIEVE_NPI 0 /* fruits/sieving/increment.py:101-129 */
@@ -701,7 +705,30 @@ int fr_rows_unshift(const double *d_A, int64_t K, int64_t N, int64_t T, const in
  * A plan armed with fr_plan_set_grad_lengths: series n is its first L_n steps, T the row stride -
  * d_dX[n, :, :L_n] is the gradient of the call on the truncated series (its bits), d_dX[n, :, L_n:]
  * is +0.0, and d_G, d_S and d_X are not read at t >= L_n.  FR_E_ARG when N is not the N the
- * lengths were set for. */
+ * lengths were set for.
+ *
+ * THE SECOND CONTRACT: a CosWISS plan.  Handed a plan of fr_plan_create_coswiss - the plan itself,
+ * no prefix plan - the entry runs the adjoint of the factorised CosWISS kernels: the gradient of
+ * the plan's W * F rows (word-major, F rows per word) with respect to d_X, the sin / cos tables
+ * being constants.  The arguments then mean:
+ * d_G, its strides and d_dX: as above.  h_row_prefix (K, host): the row of the PLAN, 0 ... W * F - 1,
+ *   that row k of d_G is the gradient of; several k may name one row, a row may have none - such a
+ *   (word, frequency) unit is neither launched nor gathered.
+ * d_S and d_A: scratch of the sizes FR_INFO_GRAD_ROWS reports, in rows of N * T doubles - d_S
+ *   (bits 32 and up of the word) takes the recomputed forward rows u of every letter behind a
+ *   word's first, d_A (bits 0 ... 31) dL/dz of every letter and the trig tables.  d_S is WRITTEN by
+ *   the entry, despite its type, and not read before; the two must be distinct buffers.
+ * Per (series, word, frequency) unit one workgroup recomputes the forward recursion in an
+ * ascending sweep over the time chunks, then runs the adjoint in a descending one, S + 1 suffix
+ * scans per letter behind one barrier; a second launch gathers d_dX.  One association per sum:
+ * the same bits from run to run and however a batch is split into calls.  The first call for a
+ * plan (or another h_row_prefix / D) uploads tables, as above; later calls enqueue three launches.
+ * FR_E_DIM: a word names a dimension beyond D.  FR_E_LIMIT: N, N * D or T beyond the grid, an
+ * exponent above 8 or a word of more than 16 letters.  FR_E_ARG: a row name outside the plan; a
+ * plan with a dropout mask (fr_coswiss_set_dropout), with a per-unit input stride
+ * (fr_coswiss_set_input_stride) or armed with fr_plan_set_grad_lengths - the CosWISS angle is a
+ * function of T, per-series lengths have no meaning for it.  N == 0 or T == 0: FR_OK after the
+ * same checks.  Every other plan that is not an unweighted Reals trie plan is refused (FR_E_ARG). */
 int fr_iss_backward(fr_plan_t *prefix_plan, const double *d_X, int64_t N, int64_t D, int64_t T,
                     const double *d_S, const double *d_G, int64_t K, int64_t g_n_stride,
                     int64_t g_k_stride, int64_t g_t_stride, const int32_t *h_row_prefix,

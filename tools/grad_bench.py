@@ -1,5 +1,5 @@
 """`python tools/grad_bench.py [reps] [launches] [--semiring=reals|arctic|bayesian]
-[--weighting=indices[,total]] [--lengths]` from the root of the tree: what the backward pass of the
+[--weighting=indices[,total]] [--lengths] [--coswiss]` from the root of the tree: what the backward pass of the
 differentiable ISS costs (fruits_amd.nn).  `of_weight(2, 3)` EXTENDED on a (2048, 3, 1024) batch that lives on the device - standard
 normal, uniform in [0.25, 1] for Bayesian -: the forward pass alone (under `torch.no_grad()`) and
 forward plus backward (`layer(X).backward(G)` with a dense upstream gradient), `launches`
@@ -22,7 +22,13 @@ round and `torch.cuda.max_memory_allocated()` of each route, measured over a ste
 `--lengths` makes the batch ragged: per-series lengths uniform on [T / 2, T]
 (seeded), passed as `lengths=` to every layer call - the same padded batch, so the line compares
 with the dense call of a run without the option.  `picked` takes them too; the `dense` feature
-route has no ragged form and stays dense."""
+route has no ragged form and stays dense.
+
+`--coswiss` measures the cosine weighted sums instead (`nn.CosWISSLayer`): the
+first CosWISS of the reference's experiments/fruit_reduced.py - `of_weight(1 ... 3, 2)`, the
+frequencies 0.05 ... 0.45, exponent 1, total weighting - on a (2048, 2, 1024) batch, forward alone
+and forward plus backward as above, and the number of series blocks the device budget
+(`FRUITS_AMD_ISS_GIB`) forced on a backward call."""
 import json
 import statistics
 import sys
@@ -48,6 +54,9 @@ if weighting not in ("", "indices", "indices,total") or (weighting and semiring 
     sys.exit("--weighting: indices or indices,total, with the Reals semiring")
 if features is not None and (semiring != "reals" or weighting or set(features) - {"dense", "picked"}):
     sys.exit("--features: dense, picked or both, with the unweighted Reals semiring")
+coswiss = "--coswiss" in sys.argv[1:]
+if coswiss and (semiring != "reals" or weighting or features is not None or "--lengths" in sys.argv[1:]):
+    sys.exit("--coswiss: on its own")
 reps = int(args[0]) if len(args) > 0 else 15
 launches = int(args[1]) if len(args) > 1 else 10
 t = nat.torch()
@@ -119,6 +128,40 @@ if features is not None:
     if len(routes) == 2:
         out["picked_over_dense"] = round(out["picked_step_ms"] / out["dense_step_ms"], 3)
     print(json.dumps(out))
+    sys.exit(0)
+
+if coswiss:
+    D = 2
+    words = fr.words.of_weight(1, 2) + fr.words.of_weight(2, 2) + fr.words.of_weight(3, 2)
+    freqs = [i / 20 for i in range(1, 11, 2)]
+    layer = nn.CosWISSLayer(words, freqs, exponent=1, total_weighting=True)
+    K = layer.op.n_iterated_sums()
+    X = t.randn((N, D, T), dtype=t.float64, device="cuda").requires_grad_(True)
+    G = t.randn((N, K, T), dtype=t.float64, device="cuda")
+
+    def forward():
+        with t.no_grad():
+            layer(X)
+
+    def both():
+        X.grad = None
+        layer(X).backward(G)
+
+    times = {0: [], 1: []}
+    for r in range(reps + 1):
+        for i, fn in enumerate((forward, both)):
+            ms = timed(fn)
+            if r:                      # (round 0 uploads the tables and warms everything up)
+                times[i].append(ms)
+    plan = layer.op._plan(0, len(words))
+    block = nn._cos_series_block(plan, N, T)
+    f, b = statistics.median(times[0]), statistics.median(times[1])
+    print(json.dumps({"shape": [N, D, T], "words": "of_weight(1 ... 3, 2)", "freqs": freqs, "exponent": 1,
+                      "total_weighting": True, "rows": K, "reps": reps, "launches": launches,
+                      "scratch_rows": list(nat.coswiss_grad_rows(plan)), "series_blocks": -(-N // block),
+                      "forward_ms": round(f, 4), "forward_backward_ms": round(b, 4),
+                      "forward_backward_minmax_ms": [round(min(times[1]), 4), round(max(times[1]), 4)],
+                      "ratio": round(b / f, 3)}))
     sys.exit(0)
 
 G = t.randn((N, K, T), dtype=t.float64, device="cuda")
