@@ -51,6 +51,7 @@ EXPORTS = [
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
     "fr_iss_backward", "fr_iss_backward_max", "fr_iss_backward_weighted",
     "fr_sieve_pick", "fr_iss_backward_picked", "fr_plan_set_grad_lengths",
+    "fr_plan_set_grad_pathlen",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -118,6 +119,8 @@ def lib():
     L.fr_pipeline_set_series_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
     L.fr_pipeline_set_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
     L.fr_plan_set_grad_lengths.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.fr_plan_set_grad_pathlen.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_double, C.c_void_p,
+                                           C.c_void_p]
     L.fr_pipeline_set_argmax.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.fr_select_ranks_begin.restype = C.c_void_p
     L.fr_select_ranks_end.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -1279,14 +1282,47 @@ def iss_backward_max(prefix_plan: Plan, Xd, Sd, G, row_prefix, work=None, length
                         lengths_d=lengths_d)
 
 
-def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=None, lengths_d=None):
+class _grad_pathlen:
+    """Set, call, clear, as ``_grad_lengths``: the plan is armed with the path-length lookup's
+    ``(norm, scale)`` and its scratches (fr_plan_set_grad_pathlen) for the one ABI call inside
+    the block; ``pathlen=None`` arms nothing."""
+
+    def __init__(self, prefix_plan: "Plan", pathlen, N: int, dg, R) -> None:
+        self.plan, self.pathlen, self.N, self.dg, self.R = prefix_plan, pathlen, N, dg, R
+
+    def __enter__(self):
+        if self.pathlen is not None:
+            norm, scale = self.pathlen
+            check(lib().fr_plan_set_grad_pathlen(self.plan._h, C.c_int64(self.N), C.c_int32(int(norm)),
+                                                 C.c_double(float(scale)), dptr(self.dg),
+                                                 dptr(self.R) if self.R is not None else None),
+                  "fr_plan_set_grad_pathlen")
+        return self
+
+    def __exit__(self, *exc):
+        if self.pathlen is not None:
+            rc = lib().fr_plan_set_grad_pathlen(self.plan._h, C.c_int64(0), C.c_int32(0), C.c_double(0.0),
+                                                None, None)
+            if exc[0] is None:          # (an error of the armed call is the one to report)
+                check(rc, "fr_plan_set_grad_pathlen")
+        return False
+
+
+def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=None, lengths_d=None,
+                          pathlen=None, return_dg: bool = False):
     """fr_iss_backward_weighted: the gradient ``(N, D, T)`` of weighted Reals iterated sums with
     respect to ``Xd``, the lookup being a constant.  ``prefix_plan``: the weighted plan of the
     distinct (letters, alphas) prefixes, each with depth 1; ``lookup_d`` ``(1 | N, T)`` the
     weighting's device lookup; ``G`` and ``row_prefix`` as in ``iss_backward``.  The entry forms
     the carried sums itself: it takes no output of the plan.  ``work``: a scratch of
     ``2 V N T + 2 alphas rows T`` doubles if the caller keeps one.  ``lengths_d`` as in
-    ``iss_backward``; row n of an ``(N, T)`` lookup is then the row of a series of that length."""
+    ``iss_backward``; row n of an ``(N, T)`` lookup is then the row of a series of that length.
+
+    ``pathlen=(norm, scale)``: ``lookup_d`` ``(N, T)`` is the path-length lookup of ``Xd`` itself -
+    ``pathlen_lookup(Xd, norm, relative, scale)`` - and the gradient flows through it into
+    dimension 0 too (fr_plan_set_grad_pathlen around the call).  The ``(N, T)``
+    scratch ``dg = dL/dg`` is allocated here and a non-total plan's ``work`` holds ``V N T`` more
+    doubles; ``return_dg=True`` hands back ``(dX, dg)``."""
     t = torch()
     (N, D, T, K, V), rp, (sn, sk, st) = _backward_args(prefix_plan, Xd, G, row_prefix)
     if (lookup_d is None or lookup_d.dtype != t.float64 or lookup_d.dim() != 2
@@ -1295,15 +1331,26 @@ def iss_backward_weighted(prefix_plan: Plan, Xd, lookup_d, G, row_prefix, work=N
         raise TypeError("the lookup must be a contiguous float64 (1 | N, T) tensor on the input's device")
     rows = int(lookup_d.shape[0])
     cells, aux = V * N * T, 2 * prefix_plan.info(FR_INFO_ALPHAS) * rows * T
-    work = _backward_scratch(work, 2 * cells + aux, "2 V N T + 2 alphas rows T", Xd).view(-1)
+    dg = R = None
+    need, what = 2 * cells + aux, "2 V N T + 2 alphas rows T"
+    keeps_r = pathlen is not None and prefix_plan.weighting != FR_W_TOTAL
+    if keeps_r:
+        # (+ 1: an empty batch still gets an address, here and for dg)
+        need, what = need + cells + 1, "3 V N T + 2 alphas rows T + 1"
+    work = _backward_scratch(work, need, what, Xd).view(-1)
+    if pathlen is not None:
+        dg = t.empty((N * T + 1,), dtype=t.float64, device=Xd.device)
+        R = work[2 * cells + aux:] if keeps_r else None
     dX = t.empty((N, D, T), dtype=t.float64, device=Xd.device)
     # (the scratch in three parts; an empty part still gets a distinct address)
     parts = [C.c_void_p(work.data_ptr() + 8 * o) for o in (0, cells, 2 * cells)]
-    with _grad_lengths(prefix_plan, lengths_d, Xd):
+    with _grad_lengths(prefix_plan, lengths_d, Xd), _grad_pathlen(prefix_plan, pathlen, N, dg, R):
         check(lib().fr_iss_backward_weighted(
             prefix_plan._h, dptr(Xd), C.c_int64(N), C.c_int64(D), C.c_int64(T), dptr(lookup_d),
             C.c_int64(rows), dptr(G), C.c_int64(K), sn, sk, st,
             _i32p(rp), parts[0], parts[1], parts[2], dptr(dX), stream_ptr()), "fr_iss_backward_weighted")
+    if pathlen is not None and return_dg:
+        return dX, dg[:N * T].view(N, T)
     return dX
 
 

@@ -4,7 +4,9 @@
 // fr_iss_backward_picked: any of the three with the sparse upstream of picked features.  The trie -
 // parents, children, letters, exp tables - is read off the plan the plan compiler built (plan.cpp);
 // the kernels are those of kernels_grad.hip.  One body (run_backward) serves the four entries.
-// fr_plan_set_grad_lengths arms a plan with per-series lengths for the backward passes that follow.
+// fr_plan_set_grad_lengths arms a plan with per-series lengths for the backward passes that follow,
+// fr_plan_set_grad_pathlen a weighted plan with a path-length lookup (L1 / L2): the armed
+// fr_iss_backward_weighted adds the gradient through the lookup.
 // fr_iss_backward handed a CosWISS plan runs the adjoint of the factorised CosWISS kernels
 // (run_backward_cos, kernels_grad_cos.hip): the plan itself, no prefix plan and no trie.
 #include <algorithm>
@@ -37,6 +39,10 @@ struct GradTables {
   // a weighted plan's: per node the exp tables {own E+, own E-, parent's E-} (-1: unused), the
   // nodes that have children by rising depth, and the bits of the plan's distinct alphas
   Table tab, inner_nodes, alpha_bits;
+  // ... and, for a plan armed with a path-length lookup, the nodes whose carried sums the lookup
+  // gather reads: those that have children or are an output row, by rising depth
+  Table carried_nodes;
+  std::vector<int32_t> carried_begin;
   int64_t dims = 0;        // dimensions dim_begin covers (the D of the call it was built for)
   void *d_blob = nullptr;
 };
@@ -62,6 +68,7 @@ const TableSlot kDeviceTables[] = {
     {&GradTables::tab, &fr::GradArgs::tab},
     {&GradTables::inner_nodes, &fr::GradArgs::inner_nodes},
     {&GradTables::alpha_bits, nullptr},
+    {&GradTables::carried_nodes, nullptr},
 };
 
 const char *const kNotWeighted = "the exp factors of a node are not those of a weighted prefix plan";
@@ -185,6 +192,14 @@ void build_level_orders(const Trie &t, bool weighted, GradTables &g) {
     for (int i = 0; i < V; ++i)
       if (t.depth[i] == dep && !t.kids[i].empty()) g.inner_nodes.h.push_back(i);
     g.inner_begin.push_back((int32_t)g.inner_nodes.h.size());
+  }
+  g.carried_nodes.h.clear();
+  g.carried_begin.assign(1, 0);
+  for (int dep = 1; weighted && dep <= t.deepest; ++dep) {
+    for (int i = 0; i < V; ++i)
+      if (t.depth[i] == dep && (!t.kids[i].empty() || g.g_begin.h[i + 1] > g.g_begin.h[i]))
+        g.carried_nodes.h.push_back(i);
+    g.carried_begin.push_back((int32_t)g.carried_nodes.h.size());
   }
 }
 
@@ -465,6 +480,29 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
   if (lengths && p.grad_lengths_n != N)
     return fail(FR_E_ARG, who + ": the lengths were set for " + std::to_string(p.grad_lengths_n) +
                               " series (fr_plan_set_grad_lengths), the call brings " + std::to_string(N));
+  // (the same for the path-length lookup: the scratches, the norm and the scale)
+  double *const dg = p.grad_pathlen_dg, *const pathlen_r = p.grad_pathlen_r;
+  const int pathlen_norm = p.grad_pathlen_norm;
+  const double pathlen_scale = p.grad_pathlen_scale;
+  if (dg) {
+    const std::string armed = who + ": the plan is armed with a path-length lookup (fr_plan_set_grad_pathlen)";
+    if (!weighted || call.picked)
+      return fail(FR_E_ARG, armed + " - only fr_iss_backward_weighted carries a gradient through it");
+    if (lengths)
+      return fail(FR_E_ARG, armed + " and with per-series lengths (fr_plan_set_grad_lengths) - the path "
+                                    "length of a truncated series is another lookup: clear one of them");
+    if (p.grad_pathlen_n != N)
+      return fail(FR_E_ARG, who + ": the path-length lookup was set for " + std::to_string(p.grad_pathlen_n) +
+                                " series (fr_plan_set_grad_pathlen), the call brings " + std::to_string(N));
+    if (call.lookup_rows != N)
+      return fail(FR_E_ARG, armed + " - the lookup has to have N rows, one per series, not " +
+                                std::to_string(call.lookup_rows));
+    const void *others[] = {d_X, d_dX, call.lookup, d_G, call.C, d_A, call.aux};
+    for (const void *o : others)
+      if (N > 0 && T > 0 && (o == dg || (pathlen_r && o == pathlen_r)))
+        return fail(FR_E_ARG, who + ": the path-length scratches (fr_plan_set_grad_pathlen) must be "
+                                    "distinct from the call's buffers");
+  }
   GradTables *g = nullptr;
   int rc = ensure_tables(p, who, h_row_prefix, K, D, N == 0 || T == 0, st, g);
   if (rc != FR_OK || N == 0 || T == 0) return rc;
@@ -505,8 +543,23 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
                                         (int)p.alphas.size(), call.aux, false, st),
                   "exp_tables launch");
     if (rc != FR_OK) return rc;
-    for (size_t l = 0; l + 1 < g->inner_begin.size(); ++l) {
-      const int first = g->inner_begin[l], count = g->inner_begin[l + 1] - first;
+    // (armed, total: the lookup gather reads S_v = C_v E-_v of every row - the longer node list)
+    const std::vector<int32_t> *carried = &g->inner_begin;
+    if (dg) {
+      a.R = kind == fr::kGradNonTotal ? pathlen_r : nullptr;
+      a.dg = dg;
+      a.lookup = call.lookup;
+      a.alphas = reinterpret_cast<const float *>(g->alpha_bits.d);
+      a.V = (int)V;
+      a.norm = pathlen_norm;
+      a.scale = pathlen_scale;
+      if (kind == fr::kGradTotal) {
+        a.inner_nodes = g->carried_nodes.d;
+        carried = &g->carried_begin;
+      }
+    }
+    for (size_t l = 0; l + 1 < carried->size(); ++l) {
+      const int first = (*carried)[l], count = (*carried)[l + 1] - first;
       rc = launched(fr::launch_grad_prefix(a, kind, first, count, st), "backward prefix launch", limit);
       if (rc != FR_OK) return rc;
     }
@@ -518,7 +571,13 @@ int run_backward(const BackwardCall &call, fr_plan_t *prefix_plan, const double 
                   "backward suffix launch", limit);
     if (rc != FR_OK) return rc;
   }
-  return launched(fr::launch_grad_input(a, kind, st), "backward input launch", limit);
+  rc = launched(fr::launch_grad_input(a, kind, st), "backward input launch", limit);
+  if (rc != FR_OK || !dg) return rc;
+  // the gradient through the lookup: dg over the nodes, then through the path length into
+  // dX[:, 0, :] - behind the input gather on this stream, so the two additions keep their order
+  rc = launched(fr::launch_grad_lookup(a, kind, st), "backward lookup launch", limit);
+  if (rc != FR_OK) return rc;
+  return launched(fr::launch_grad_pathlen(a, st), "backward path-length launch", limit);
 }
 
 // fr_iss_backward with a CosWISS plan: the checks in run_backward's order, the
@@ -608,6 +667,32 @@ int fr_plan_set_grad_lengths(fr_plan_t *prefix_plan, const int32_t *d_lengths, i
   std::lock_guard<std::mutex> lock(p.mu);
   p.grad_lengths = d_lengths;
   p.grad_lengths_n = d_lengths ? N : 0;
+  return FR_OK;
+}
+
+int fr_plan_set_grad_pathlen(fr_plan_t *prefix_plan, int64_t N, int32_t norm, double scale, double *d_dg,
+                             double *d_R) {
+  const std::string who = "fr_plan_set_grad_pathlen";
+  if (!prefix_plan || !prefix_plan->p) return fail(FR_E_ARG, who + ": null plan");
+  fr::Plan &p = *prefix_plan->p;
+  if (d_dg) {
+    if (N < 0) return fail(FR_E_ARG, who + ": bad shape");
+    if (norm != 1 && norm != 2)
+      return fail(FR_E_ARG, who + ": the norm has to be 1 (L1) or 2 (L2), not " + std::to_string(norm));
+    if (!(scale == scale) || scale - scale != 0.0) return fail(FR_E_ARG, who + ": the scale has to be finite");
+    if (p.cos || p.semiring != fr::kSemiReals || p.weighting == 0)
+      return fail(FR_E_ARG, who + ": the plan is not a weighted Reals trie plan - only fr_iss_backward_weighted "
+                                  "carries a gradient through a lookup");
+    if (p.weighting != FR_W_TOTAL && !d_R)
+      return fail(FR_E_ARG, who + ": a non-total plan needs the scratch d_R (V, N, T)");
+    if (d_R == d_dg) return fail(FR_E_ARG, who + ": the scratches must be distinct buffers");
+  }
+  std::lock_guard<std::mutex> lock(p.mu);
+  p.grad_pathlen_dg = d_dg;
+  p.grad_pathlen_r = d_dg ? d_R : nullptr;
+  p.grad_pathlen_n = d_dg ? N : 0;
+  p.grad_pathlen_norm = d_dg ? norm : 0;
+  p.grad_pathlen_scale = d_dg ? scale : 0.0;
   return FR_OK;
 }
 

@@ -192,6 +192,16 @@ struct GradArgs {
   // len[n] <= T.  T stays the row stride of every buffer; the kernels walk, read and write A, S
   // and C below len[n] alone, and dX behind it is +0.0.
   const int32_t *len;           // (N)
+  // the gradient through a path-length lookup: g = scale r / r[T-1], r the
+  // cumulative |dx_0| (norm 1) or dx_0^2 (norm 2) of the series itself.  Null or 0 unless the plan
+  // is armed (fr_plan_set_grad_pathlen); `len` is null then and the lookup has N rows.
+  double *R;              // (V, N, T) scratch, non-total: R_v = suffix(Q_v) of the nodes that have children
+  double *dg;             // (N, T) scratch: dL/dg
+  const double *lookup;   // (N, T): g
+  const float *alphas;    // the plan's distinct alphas: the exp tables 2a and 2a + 1 are alpha a's
+  int V;                  // nodes of the trie
+  int norm;
+  double scale;
 };
 constexpr int kPickMaxFeatures = 256;   // features of a row of fr_sieve_pick, pairs of a row of the sparse upstream
 constexpr int kGradChunk = 1024;   // time steps a workgroup scans at once (256 lanes x 4)
@@ -207,6 +217,11 @@ hipError_t launch_grad_max_suffix(const GradArgs &a, int kind, int first, int co
 hipError_t launch_grad_prefix(const GradArgs &a, int kind, int first, int count, hipStream_t st);
 // dX from the finished A (every kind)
 hipError_t launch_grad_input(const GradArgs &a, int kind, hipStream_t st);
+// dg from the finished A, C and - non-total - R (kGradTotal, kGradNonTotal; a.dg, a.alphas, a.V set)
+hipError_t launch_grad_lookup(const GradArgs &a, int kind, hipStream_t st);
+// dg through the normalised cumulative path length, ADDED into dX[:, 0, :]: behind launch_grad_input
+// and launch_grad_lookup on the same stream (a.dg, a.lookup, a.norm, a.scale set)
+hipError_t launch_grad_pathlen(const GradArgs &a, hipStream_t st);
 
 // The backward pass of the factorised CosWISS kernels (kernels_grad_cos.hip).
 // Unit j = w * F + f is (word w, frequency f); letter g is a letter of the whole program,

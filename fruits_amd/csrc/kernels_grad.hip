@@ -59,6 +59,12 @@
 // grad_prefix_kernel forms C of the nodes that have children, root first, with the forward lane
 // map; the exp tables are read from global memory (launch_exp_tables filled them on the stream).
 //
+// A lookup that is a function of the input (L1 / L2): a plan armed with
+// fr_plan_set_grad_pathlen makes the prefix kernel form C of the output rows without children too
+// (total) and the suffix kernel keep R_v = suffix(Q_v) (non-total); grad_lookup_kernel then
+// gathers dL/dg over the nodes and grad_pathlen_kernel carries it through the normalised
+// cumulative path length into dimension 0 of dX, behind the input kernel.
+//
 // Arctic (max, +) and Bayesian (max, x), semiring.py:282-309 and :461-493: per node
 //     z_v = m_v (x) S_p (no shift; m_v alone at depth 1),   S_v = running maximum of z_v
 // with m_v[t] = sum_d e_vd x_d[t] (Arctic) or prod_d x_d[t]^e_vd (Bayesian).  A HEAD of v is a
@@ -245,7 +251,9 @@ __global__ __launch_bounds__(256) void grad_suffix_kernel(GradArgs a, int first)
       if (t0 + j >= Tn) continue;
       double out = scan0 ? off0 + b[j] : 0.0;
       if (scan1) {
-        const double sq = (off1 + q[j]) * exp_factor(en, a.aux_tab, t_plus, t0 + j);
+        const double r = off1 + q[j];   // R_v = dL/dy_v, kept for the gradient through the lookup
+        if (a.R) a.R[((int64_t)v * N + n) * T + t0 + j] = r;
+        const double sq = r * exp_factor(en, a.aux_tab, t_plus, t0 + j);
         out = scan0 ? out + sq : sq;
       }
       av[t0 + j] = out;
@@ -524,6 +532,155 @@ hipError_t launch_grad_input(const GradArgs &a, int kind, hipStream_t st) {
   const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
   if (a.N * a.D > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kernel, dim3((unsigned)(a.N * a.D), (unsigned)tiles), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the gradient through the lookup
+// (L1 / L2, whose g is a function of the series itself)
+// dg[n, t] = dL/dg: g reaches L through the exp factors alone, and every term is a product of what
+// the pass holds by now - one thread per (series, step), the nodes in the table's order.
+//     total:      sum_v (alpha_v - alpha_p) dm_v m_v  -  sum over rows v of alpha_v G_v (C_v E-_v)
+//     non-total:  sum over v with children of alpha_v R_v y_v  -  sum over v below depth 1 of alpha_p dm_v m_v
+// dm_v is input_dm, y_v = m_v E-_p E+_v shift(C_p); nothing is divided by an exp factor.  C_v of the
+// rows without children (total) and R_v (non-total) exist because the plan is armed.
+template <int KIND>
+__global__ __launch_bounds__(256) void grad_lookup_kernel(GradArgs a) {
+  constexpr bool TOTAL = KIND == kGradTotal;
+  const int64_t n = blockIdx.x;
+  const int64_t N = a.N, T = a.T;
+  const double *__restrict__ xn = a.X + n * a.D * T;
+  const double *__restrict__ en = a.aux + n * a.aux_n;
+  const double *__restrict__ gn = a.G + n * a.g_n;
+#pragma unroll
+  for (int e = 0; e < kGradTile / 256; ++e) {
+    const int64_t t = (int64_t)blockIdx.y * kGradTile + e * 256 + (int)threadIdx.x;
+    if (t >= T) continue;
+    double acc = 0.0;
+    for (int v = 0; v < a.V; ++v) {
+      const int t_plus = as_const(a.tab)[3 * v], t_minus = as_const(a.tab)[3 * v + 1];
+      const int t_pminus = as_const(a.tab)[3 * v + 2];
+      const int ps = as_const(a.parent_srow)[v];
+      const int fb = as_const(a.fac_begin)[v], fe = as_const(a.fac_begin)[v + 1];
+      const double alpha_p = t_pminus >= 0 ? (double)as_const(a.alphas)[t_pminus >> 1] : 0.0;
+      if constexpr (TOTAL) {
+        const double alpha_v = (double)as_const(a.alphas)[t_plus >> 1];
+        const double m = letter_value(a, xn, fb, fe, t, -1);
+        acc += (alpha_v - alpha_p) * (input_dm<KIND>(a, en, v, n, t) * m);
+        const int gb = as_const(a.g_begin)[v], ge = as_const(a.g_begin)[v + 1];
+        if (ge > gb) {
+          double gv = 0.0;
+          for (int g = gb; g < ge; ++g) gv += gn[(int64_t)as_const(a.g_row)[g] * a.g_k + t * a.g_t];
+          const double s = a.C[((int64_t)as_const(a.self_srow)[v] * N + n) * T + t] *
+                           exp_factor(en, a.aux_tab, t_minus, t);
+          acc -= alpha_v * (gv * s);
+        }
+      } else {
+        if (as_const(a.child_begin)[v + 1] > as_const(a.child_begin)[v]) {
+          const double alpha_v = (double)as_const(a.alphas)[t_plus >> 1];
+          double y = letter_value(a, xn, fb, fe, t, -1) * exp_factor(en, a.aux_tab, t_plus, t);
+          if (ps >= 0)
+            y = t > 0 ? y * exp_factor(en, a.aux_tab, t_pminus, t) * a.C[((int64_t)ps * N + n) * T + t - 1] : 0.0;
+          acc += alpha_v * (a.R[((int64_t)v * N + n) * T + t] * y);
+        }
+        if (ps >= 0) acc -= alpha_p * (input_dm<KIND>(a, en, v, n, t) * letter_value(a, xn, fb, fe, t, -1));
+      }
+    }
+    a.dg[n * T + t] = acc;
+  }
+}
+
+hipError_t launch_grad_lookup(const GradArgs &a, int kind, hipStream_t st) {
+  if (!grad_weighted(kind) || !a.dg || !a.alphas || (kind == kGradNonTotal && !a.R)) return hipErrorInvalidValue;
+  if (a.N <= 0 || a.T <= 0) return hipSuccess;
+  const int64_t tiles = (a.T + kGradTile - 1) / kGradTile;
+  if (a.N > 0x7fffffffLL || tiles > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kind == kGradTotal ? grad_lookup_kernel<kGradTotal> : grad_lookup_kernel<kGradNonTotal>,
+                     dim3((unsigned)a.N, (unsigned)tiles), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// f'(dx_t) of the path length's summand at step t of dimension 0 `x`: sign(dx_t) (norm 1;
+// sign(0) = 0, the subgradient of torch.abs) or 2 dx_t (norm 2); 0 at t = 0 and at t = T.
+__device__ __forceinline__ double pathlen_weight(const double *__restrict__ x, int64_t t, int64_t T, int norm) {
+  if (t < 1 || t >= T) return 0.0;
+  const double d = x[t] - x[t - 1];
+  if (norm == 1) return d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : 0.0);
+  return 2.0 * d;
+}
+
+// dg through g = scale r / r_L, r = cumsum(f(dx_0)), r_L = r[T-1], into dimension 0 of dX: one
+// workgroup per series.
+//     dr[t] = scale dg[t] / r_L,   dr[T-1] -= (sum_s dg[s] g[s]) / r_L,   D[t] = sum over s >= t of dr[s]
+//     dX_0[t] += w_t D[t] - w_(t+1) D[t+1]
+// The two sums are block reductions - a lane's steps in rising order, the lanes by the wave scan,
+// the four wave totals in wave order -; r_L is recomputed from X.  D is the suffix scan of the
+// frame, chunks from the last to the first with a carry; D[t+1] of a lane's last step is what lies
+// in front of the lane - scan_offset's value, chunk boundary included - so nothing is exchanged.
+// A series with r_L = 0 (a constant dimension 0; T = 1) has g = 0 whatever the input does nearby
+// as the forward pass defines it: it gets nothing, no 0 / 0.
+__global__ __launch_bounds__(256) void grad_pathlen_kernel(GradArgs a) {
+  __shared__ double total[2][4];
+  __shared__ double wave_total[2][4];
+  const int64_t n = blockIdx.x;
+  const int64_t T = a.T;
+  const double *__restrict__ x = a.X + n * a.D * T;
+  const double *__restrict__ dgn = a.dg + n * T;
+  const double *__restrict__ gn = a.lookup + n * T;
+  double *__restrict__ dx = a.dX + n * a.D * T;
+  const int64_t chunks = grad_chunks(T);
+
+  double rl = 0.0, p = 0.0;
+  for (int64_t c = 0; c < chunks; ++c) {
+    const int64_t t0 = forward_t0(c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t t = t0 + j;
+      if (t >= T) continue;
+      if (t >= 1) {
+        const double d = x[t] - x[t - 1];
+        rl += a.norm == 1 ? fabs(d) : d * d;
+      }
+      p += dgn[t] * gn[t];
+    }
+  }
+  (void)scan_publish(rl, total[0]);
+  (void)scan_publish(p, total[1]);
+  __syncthreads();
+  rl = ((total[0][0] + total[0][1]) + total[0][2]) + total[0][3];
+  p = ((total[1][0] + total[1][1]) + total[1][2]) + total[1][3];
+  if (rl == 0.0) return;   // (workgroup-uniform)
+  const double tail = p / rl;
+
+  double carry = 0.0;   // the sum of dr over the chunks to the right
+  for (int64_t c = chunks - 1; c >= 0; --c) {
+    const int64_t t0 = reversed_t0(c);
+    double b[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t t = t0 + j;
+      if (t >= T) continue;
+      b[j] = a.scale * dgn[t] / rl;
+      if (t == T - 1) b[j] -= tail;
+    }
+    lane_suffix(b);
+    const double excl = scan_publish(b[0], wave_total[c & 1]);
+    __syncthreads();
+    const double off = scan_offset(wave_total[c & 1], excl, carry);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t t = t0 + j;
+      if (t >= T) continue;
+      const double d_here = off + b[j], d_next = j < 3 ? off + b[j + 1] : off;
+      dx[t] += pathlen_weight(x, t, T, a.norm) * d_here - pathlen_weight(x, t + 1, T, a.norm) * d_next;
+    }
+  }
+}
+
+hipError_t launch_grad_pathlen(const GradArgs &a, hipStream_t st) {
+  if (!a.dg || !a.lookup || (a.norm != 1 && a.norm != 2)) return hipErrorInvalidValue;
+  if (a.N <= 0 || a.T <= 0) return hipSuccess;
+  if (a.N > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grad_pathlen_kernel, dim3((unsigned)a.N), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

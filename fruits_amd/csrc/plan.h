@@ -187,6 +187,12 @@ struct Plan {
   // device table, or nullptr (under mu)
   const int32_t *grad_lengths = nullptr;
   int64_t grad_lengths_n = 0;
+  // the path-length lookup of the following weighted backward passes (fr_plan_set_grad_pathlen):
+  // the caller's scratches dg (N, T) and R (V, N, T; non-total plans), or nullptr (under mu)
+  double *grad_pathlen_dg = nullptr, *grad_pathlen_r = nullptr;
+  int64_t grad_pathlen_n = 0;
+  int grad_pathlen_norm = 0;
+  double grad_pathlen_scale = 0.0;
   int device = -1;     // HIP device the uploaded tables live on (-1: nothing uploaded yet)
   std::mutex mu;       // guards `programs`, `cos->d_blob` and `device` (uploads at run time)
 

@@ -21,6 +21,12 @@ backward pass forms the sums the forward pass carries from letter to letter itse
 scan per inner node of the trie, instead of a second walk (DESIGN.md 4.14.2,
 ``fr_iss_backward_weighted``).
 
+``pathlen_iss(X, words, mode, weighting=...)`` and ``PathLengthISSLayer`` are the same for ``L1``
+and ``L2``, whose lookup is the normalised cumulative path length of ``X`` itself: the backward
+pass arms the weighted entry (``fr_plan_set_grad_pathlen``), which then gathers the derivative
+with respect to the lookup over the trie and carries it through the path length into dimension 0
+(DESIGN.md 4.14.8).  No ``lengths=``.
+
 ``iss_features(X, words, mode, sieves, semiring=..., weighting=...)`` and ``FeatureLayer`` return
 what a classifier is fed instead of the rows: the ``END`` / ``MAX`` / ``MIN`` features of every
 iterated sum, ``(N, K * F)`` in ``Fruit``'s column order, for any of the three configurations
@@ -65,7 +71,8 @@ from .lengths import check_lengths
 from .sieving import END, MAX, MIN
 
 __all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "weighted_iss", "WeightedISSLayer",
-           "cos_iss", "CosWISSLayer", "iss_features", "iss_features_ragged", "FeatureLayer",
+           "pathlen_iss", "PathLengthISSLayer", "cos_iss", "CosWISSLayer",
+           "iss_features", "iss_features_ragged", "FeatureLayer",
            "backward_calls"]
 
 _calls = {"backward": 0}
@@ -457,6 +464,115 @@ class WeightedISSLayer(_Layer):
     @property
     def weighting(self):
         return self.op.weighting
+
+    def extra_repr(self) -> str:
+        return (f"{super().extra_repr()}, "
+                f"{type(self.op.weighting).__name__}{' total' if self.op.weighting.total else ''}")
+
+
+# ----------------------------------------------------------------------- weighted with the path length
+_PATHLEN_NO_LENGTHS = ("lengths= is not taken here: the forward L1 / L2 lookup takes no lengths - the path "
+                       "length of a truncated series is normalised by another total")
+
+
+def _check_pathlen_config(op: ISS) -> None:
+    """``_check_config`` for ``pathlen_iss``: raised before any launch."""
+    from .iss.weighting import _PathLength
+    if isinstance(op, CosWISS):
+        raise NotImplementedError("CosWISS has no backward pass here: only the trie walk's ISS has "
+                                  "(the cosine weighted sums are nn.cos_iss / nn.CosWISSLayer)")
+    w = op.weighting
+    if w is None:
+        raise NotImplementedError(
+            "pathlen_iss differentiates an ISS weighted with L1 or L2: the unweighted iterated sums are "
+            "nn.iss / nn.ISSLayer")
+    if w._supports_lengths():
+        raise NotImplementedError(
+            f"the lookup of the weighting {type(w).__name__} is a function of the time step alone: its "
+            "backward pass is nn.weighted_iss / nn.WeightedISSLayer")
+    if not isinstance(w, _PathLength):
+        raise NotImplementedError(
+            f"the lookup of the weighting {type(w).__name__} is an arbitrary callable of the input, which "
+            "has no derivative here: only L1 and L2 have a gradient through the lookup")
+    if w._transform is not None:
+        raise NotImplementedError(
+            f"{type(w).__name__}(transform=...) applies a Python callable to the path length, which has no "
+            "derivative here: only the plain L1 and L2 have a gradient through the lookup")
+    if not isinstance(op.semiring, Reals):
+        raise NotImplementedError(
+            f"the semiring {type(op.semiring).__name__} has no weighted backward pass: only "
+            "Reals has")
+    _check_words(op)
+
+
+def _pathlen_lookup(op: ISS, Xc):
+    """The ``(N, T)`` lookup of ``Xc`` itself, as the Reals forward pass forms it: here the one
+    tensor is the raw and the prepared input, so ``on_prepared`` changes nothing."""
+    w = op.weighting
+    return nat.pathlen_lookup(Xc, w._norm, 1 if w._relative else 0, float(w._scale), exact=False)
+
+
+class _PathLengthFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, op):
+        Xc = X.contiguous()
+        Y = op.transform_device(Xc, lookup_d=_pathlen_lookup(op, Xc))          # (K, N, T)
+        ctx.op = op
+        ctx.save_for_backward(Xc)
+        return Y.permute(1, 0, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        (Xc,) = ctx.saved_tensors
+        op = ctx.op
+        plan, row_prefix = _prefix_program(op)
+        with torch.cuda.device(Xc.device):
+            # (the lookup is formed again, not kept; the armed entry carries the gradient through it)
+            lookup = _pathlen_lookup(op, Xc)
+            _calls["backward"] += 1
+            return nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix,
+                                             pathlen=(op.weighting._norm, float(op.weighting._scale))), None
+
+
+def _apply_pathlen(op: ISS, X, lengths=None):
+    if lengths is not None:
+        raise NotImplementedError(_PATHLEN_NO_LENGTHS)
+    _check_input(op, X)
+    with torch.cuda.device(X.device):
+        return _PathLengthFunction.apply(X, op)
+
+
+def pathlen_iss(X, words, mode: ISSMode = ISSMode.SINGLE, *, weighting=None, lengths=None):
+    """Reals iterated sums ``(N, K, T)`` of the device tensor ``X`` ``(N, D, T)`` weighted with the
+    path length of ``X`` itself, in the row order of ``ISS(words, mode, weighting=weighting)
+    .transform(X)`` and with its bits; differentiable with respect to ``X``.  ``weighting``: an
+    ``L1`` or an ``L2``, total or not, ``relative`` either way, any ``scale``; or ``words`` is an
+    ``ISS`` that carries one.  The lookup ``g = scale r / r[T-1]``, ``r`` the cumulative ``|dx_0|`` or
+    ``dx_0^2`` of dimension 0, is a function of ``X``: ``X.grad`` is the full derivative, the part that
+    flows through ``g`` into dimension 0 included (``fr_plan_set_grad_pathlen``
+    around ``fr_iss_backward_weighted``).  Where an increment of dimension 0 is exactly 0 the ``L1``
+    gradient takes ``sign(0) = 0``, the subgradient of ``torch.abs``; a series whose dimension 0 is
+    constant has ``g = 0`` and gets no gradient through the lookup.  ``transform=`` on the
+    weighting, ``Indices`` / ``Plateaus`` / ``Custom``, a non-Reals semiring, ``CosWISS``, generic
+    words and ``lengths=`` raise NotImplementedError."""
+    op = _cached_weighted_op(X, words, mode, weighting)
+    _check_pathlen_config(op)
+    return _apply_pathlen(op, X, lengths)
+
+
+class PathLengthISSLayer(_Layer):
+    """``pathlen_iss`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, *, weighting=None) -> None:
+        super().__init__(_weighted_op(words, mode, weighting), _check_pathlen_config)
+
+    @property
+    def weighting(self):
+        return self.op.weighting
+
+    def forward(self, X, lengths=None):
+        return _apply_pathlen(self.op, X, lengths)
 
     def extra_repr(self) -> str:
         return (f"{super().extra_repr()}, "

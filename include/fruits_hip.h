@@ -871,6 +871,38 @@ int fr_iss_backward_picked(fr_plan_t *prefix_plan, const double *d_X, int64_t N,
  * launch, when its N is not the N the lengths were set for (the text names both). */
 int fr_plan_set_grad_lengths(fr_plan_t *prefix_plan, const int32_t *d_lengths, int64_t N);
 
+/* fr_plan_set_grad_pathlen: the gradient THROUGH the lookup for the fr_iss_backward_weighted calls
+ * that follow on this plan with exactly N series - the weightings L1 and L2
+ * (fruits/iss/weighting.py:113-210), whose g is the normalised cumulative path length of dimension
+ * 0 of the input itself: g[t] = scale r[t] / r[T-1], r = cumsum(|dx_0|) (norm 1) or cumsum(dx_0^2)
+ * (norm 2), r[0] = 0 - what fr_pathlen_lookup forms with `relative` 0 or 1 alike (the + 1e-5
+ * cancels in the min-max normalisation).  Not in the reference.
+ *   d_dg (N, T)     scratch: dL/dg, left there for the caller to read.  NULL clears the plan.
+ *   d_R  (V, N, T)  scratch of a non-total plan (R_v below); ignored for a total one
+ * It takes no stream and is delivered exactly like fr_plan_set_grad_lengths: stored under the
+ * plan's mutex, read once by the entry under the same mutex and handed to its kernels by value.
+ * A plan that was never armed, or is cleared, behaves exactly as before, bit for bit.
+ * An armed fr_iss_backward_weighted wants lookup_rows == N, forms C_v of the output rows without
+ * children too (total) or keeps R_v = suffix(Q_v) = dL/dy_v of the nodes with children (non-total),
+ * and behind the input gather enqueues two more kernels on its stream.  With alpha_v the float32
+ * alpha of node v's last letter, alpha_p its parent's (0 at depth 1), dm_v and m_v as above:
+ *   total:      dg[t] = sum_v (alpha_v - alpha_p) dm_v[t] m_v[t]
+ *                       - sum over output rows v of alpha_v G_v[t] S_v[t],   S_v = C_v E-_v
+ *   non-total:  dg[t] = sum over v with children of alpha_v R_v[t] y_v[t]
+ *                       - sum over v of depth >= 2 of alpha_p dm_v[t] m_v[t],   y_v = z_v E+_v
+ *   dr[t] = scale dg[t] / r_L,   dr[T-1] -= sum_s dg[s] g[s] / r_L,   r_L = r[T-1]
+ *   D[t] = sum over s >= t of dr[s]
+ *   dX_0[t] += w_t D[t] - w_(t+1) D[t+1],   w_t = sign(dx_t) (norm 1) | 2 dx_t (norm 2), w_0 = w_T = 0
+ * sign(0) = 0; a series with r_L = 0 (a constant dimension 0, T = 1) has g = 0 and gets nothing
+ * from the lookup.  Nothing is divided by an exp factor; one association per sum whatever the grid.
+ * FR_E_ARG, on the host: a null plan; with a d_dg, N < 0, a norm that is not 1 or 2, a scale that
+ * is not finite, a plan that is not a weighted Reals trie plan, a non-total plan without d_R,
+ * d_R == d_dg.  From an armed fr_iss_backward_weighted, before any launch: another N, lookup_rows
+ * != N, a plan armed with fr_plan_set_grad_lengths too, a scratch that is one of the call's
+ * buffers.  fr_iss_backward_picked refuses an armed plan. */
+int fr_plan_set_grad_pathlen(fr_plan_t *prefix_plan, int64_t N, int32_t norm, double scale, double *d_dg,
+                             double *d_R);
+
 /* ------------------------------------------------------------------ Fruit.transform epilogue
  * np.nan_to_num(result, copy=False, nan=0.0) of Fruit.transform (fruits/fruit.py:172) on the
  * device-resident feature matrix, in place: NaN -> 0, +inf / -inf -> the largest / lowest

@@ -1,5 +1,5 @@
 """`python tools/grad_bench.py [reps] [launches] [--semiring=reals|arctic|bayesian]
-[--weighting=indices[,total]] [--lengths] [--coswiss]` from the root of the tree: what the backward pass of the
+[--weighting=indices[,total]|l1[,total]] [--lengths] [--coswiss]` from the root of the tree: what the backward pass of the
 differentiable ISS costs (fruits_amd.nn).  `of_weight(2, 3)` EXTENDED on a (2048, 3, 1024) batch that lives on the device - standard
 normal, uniform in [0.25, 1] for Bayesian -: the forward pass alone (under `torch.no_grad()`) and
 forward plus backward (`layer(X).backward(G)` with a dense upstream gradient), `launches`
@@ -9,7 +9,9 @@ warm-up round; the medians per call, the smallest and largest round of forward p
 the ratio of the medians as one JSON line.  With a max semiring, or with `--weighting` (the
 weighted Reals sums of `nn.WeightedISSLayer`, `Indices()` with the words' default alphas, total or
 not), the unweighted Reals pair (`nn.ISSLayer`) runs interleaved in the same rounds, for
-comparison.
+comparison.  `--weighting=l1[,total]` measures the path-length weighting whose gradient flows
+through the lookup too (`nn.PathLengthISSLayer`, `L1()`); its yardstick, interleaved
+in the same rounds, is the `Indices` pair of the same body (the keys `indices_...`).
 
 `--features[=dense|picked]` measures a training step on FEATURES instead: the
 last value and the maximum of every iterated sum, forward plus backward with an `(N, 2 K)`
@@ -50,8 +52,10 @@ for a in sys.argv[1:]:
         weighting = a.split("=", 1)[1].lower()
 if semiring not in ("reals", "arctic", "bayesian"):
     sys.exit("--semiring: reals, arctic or bayesian")
-if weighting not in ("", "indices", "indices,total") or (weighting and semiring != "reals"):
-    sys.exit("--weighting: indices or indices,total, with the Reals semiring")
+if weighting not in ("", "indices", "indices,total", "l1", "l1,total") or (weighting and semiring != "reals"):
+    sys.exit("--weighting: indices, indices,total, l1 or l1,total, with the Reals semiring")
+if weighting.startswith("l1") and "--lengths" in sys.argv[1:]:
+    sys.exit("--weighting=l1: the path-length weighting takes no lengths")
 if features is not None and (semiring != "reals" or weighting or set(features) - {"dense", "picked"}):
     sys.exit("--features: dense, picked or both, with the unweighted Reals semiring")
 coswiss = "--coswiss" in sys.argv[1:]
@@ -190,9 +194,14 @@ if semiring != "reals":
            "reals_": fns[""]}
 if weighting:
     w = fr.iss.weighting.Indices(total=weighting.endswith(",total"))
-    fns = {"": pair(nn.WeightedISSLayer(words, fr.ISSMode.EXTENDED, weighting=w),
-                    X.detach().clone().requires_grad_(True)),
-           "reals_": fns[""]}
+    indices = pair(nn.WeightedISSLayer(words, fr.ISSMode.EXTENDED, weighting=w),
+                   X.detach().clone().requires_grad_(True))
+    fns = {"": indices, "reals_": fns[""]}
+    if weighting.startswith("l1"):
+        w = fr.iss.weighting.L1(total=weighting.endswith(",total"))
+        fns = {"": pair(nn.PathLengthISSLayer(words, fr.ISSMode.EXTENDED, weighting=w),
+                        X.detach().clone().requires_grad_(True)),
+               "indices_": indices}
 
 
 times = {(k, i): [] for k in fns for i in (0, 1)}
