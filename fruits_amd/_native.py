@@ -23,6 +23,7 @@ FR_SIEVE_NPI, FR_SIEVE_MPI, FR_SIEVE_END = 0, 1, 2
 FR_SIEVE_MAX, FR_SIEVE_MIN, FR_SIEVE_XPI, FR_SIEVE_LPI, FR_SIEVE_CUR = 3, 4, 5, 6, 7
 FR_SIEVE_PPV, FR_SIEVE_CPV = 16, 17   # numbers of their own: fr_sieve_implicit only
 FR_SIEVE_SEGMENTS = 0x200   # OR-ed into PPV / CPV at fr_pipeline_create: bands q_j <= v < q_(j+1)
+MAX_INC = 8   # the largest differencing order of a sieve's rows (csrc/kernels.h, kMaxInc)
 FR_SIEVE_SERIES_CUTS = 0x100   # OR-ed into a kind: the sieve's cuts are slots of a per-series table
 (FR_INFO_ROWS, FR_INFO_NODES, FR_INFO_LEVELS, FR_INFO_DIMS_USED, FR_INFO_MAX_DIM,
  FR_INFO_ALPHAS, FR_INFO_GROUPS, FR_INFO_SHARED, FR_INFO_STAGED_ROWS, FR_INFO_JIT_PROGRAMS,
@@ -51,7 +52,7 @@ EXPORTS = [
     "fr_pipeline_set_lengths", "fr_sieve_implicit_lengths", "fr_standardize_lengths",
     "fr_iss_backward", "fr_iss_backward_max", "fr_iss_backward_weighted",
     "fr_sieve_pick", "fr_iss_backward_picked", "fr_plan_set_grad_lengths",
-    "fr_plan_set_grad_pathlen",
+    "fr_plan_set_grad_pathlen", "fr_sieve_heads", "fr_sieve_heads_adjoint",
 ]
 FR_ROW_DIM, FR_ROW_ABS, FR_ROW_EXT, FR_ROW_ONE = range(4)
 FR_PW_MUL, FR_PW_ADD, FR_PW_ROTATE, FR_PW_POW, FR_PW_SHIFT, FR_PW_CLIP = range(6)
@@ -1383,6 +1384,23 @@ def iss_backward_cos(plan: "CosPlan", Xd, G, row_unit, work=None):
 
 
 # ----------------------------------------------------------------------- differentiable features
+def _head_tables(spec, spec_d, cuts_d, q_d, N: int, cols: int = 7):
+    """The spec table ``(n_sieves, cols)`` of fr_sieve_pick (6) or fr_sieve_heads (7) as a
+    contiguous int32 host array, after the checks of its device tables."""
+    t = torch()
+    sp = np.ascontiguousarray(spec, dtype=np.int32)
+    if sp.ndim != 2 or sp.shape[1] != cols:
+        raise ValueError(f"the spec table is (n_sieves, {cols})")
+    if (spec_d.dtype != t.int32 or tuple(spec_d.shape) != sp.shape or not spec_d.is_contiguous()
+            or cuts_d.dtype != t.int64 or not cuts_d.is_contiguous()
+            or (sp.shape[0] > 0 and (sp[0, 0] & FR_SIEVE_SERIES_CUTS)
+                and (cuts_d.dim() != 2 or int(cuts_d.shape[0]) != N))
+            or (q_d is not None and (q_d.dtype != t.float64 or not q_d.is_contiguous()))):
+        raise TypeError("the device tables must be contiguous: spec int32 like the host table, "
+                        "cuts int64 (per-series cuts: (N, row)), thresholds float64")
+    return sp
+
+
 def sieve_pick(Ad, spec, spec_d, cuts_d, q_d, F: int):
     """fr_sieve_pick: the selecting sieves END / MAX / MIN over every row of the contiguous
     ``(K, N, T)`` device tensor ``Ad`` in one launch.  ``spec`` ``(n_sieves, 6)`` int32 host
@@ -1396,16 +1414,7 @@ def sieve_pick(Ad, spec, spec_d, cuts_d, q_d, F: int):
     if Ad.dtype != t.float64 or Ad.dim() != 3 or not Ad.is_contiguous():
         raise TypeError("A must be a contiguous float64 (K, N, T) device tensor")
     K, N, T = (int(v) for v in Ad.shape)
-    sp = np.ascontiguousarray(spec, dtype=np.int32)
-    if sp.ndim != 2 or sp.shape[1] != 6:
-        raise ValueError("the spec table is (n_sieves, 6)")
-    if (spec_d.dtype != t.int32 or tuple(spec_d.shape) != sp.shape or not spec_d.is_contiguous()
-            or cuts_d.dtype != t.int64 or not cuts_d.is_contiguous()
-            or (sp.shape[0] > 0 and (sp[0, 0] & FR_SIEVE_SERIES_CUTS)
-                and (cuts_d.dim() != 2 or int(cuts_d.shape[0]) != N))
-            or (q_d is not None and (q_d.dtype != t.float64 or not q_d.is_contiguous()))):
-        raise TypeError("the device tables must be contiguous: spec int32 like the host table, "
-                        "cuts int64 (per-series cuts: (N, row)), thresholds float64")
+    sp = _head_tables(spec, spec_d, cuts_d, q_d, N, 6)
     feat = t.empty((N, K, int(F)), dtype=t.float64, device=Ad.device)
     pos = t.empty((N, K, int(F)), dtype=t.int32, device=Ad.device)
     check(lib().fr_sieve_pick(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(spec_d),
@@ -1461,3 +1470,66 @@ def iss_backward_picked(prefix_plan: Plan, Xd, pos_d, w_d, row_prefix, Sd=None, 
             dptr(pos_d), dptr(w_d), C.c_int64(K), C.c_int32(F), _i32p(rp), Cs, A, ax, dptr(dX),
             stream_ptr()), "fr_iss_backward_picked")
     return dX
+
+
+def sieve_heads(Ad, spec, spec_d, cuts_d, q_d, F: int):
+    """fr_sieve_heads: the heads END / MAX / MIN / MPI / CUR over every row of the contiguous
+    ``(K, N, T)`` device tensor ``Ad`` in one launch.  The tables are ``sieve_pick``'s with a
+    seventh spec column, the differencing order ``{kind, cut_begin, C1, q_begin, Q1, feat_begin,
+    inc}``.  Returns ``(features (N, K, F) float64, companion (N, K, F) int32)``: the position of
+    a selecting feature, the in-band count of an ``MPI`` / ``CUR`` one."""
+    t = torch()
+    if Ad.dtype != t.float64 or Ad.dim() != 3 or not Ad.is_contiguous():
+        raise TypeError("A must be a contiguous float64 (K, N, T) device tensor")
+    K, N, T = (int(v) for v in Ad.shape)
+    sp = _head_tables(spec, spec_d, cuts_d, q_d, N)
+    feat = t.empty((N, K, int(F)), dtype=t.float64, device=Ad.device)
+    comp = t.empty((N, K, int(F)), dtype=t.int32, device=Ad.device)
+    check(lib().fr_sieve_heads(dptr(Ad), C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(spec_d),
+                               _i32p(sp), C.c_int32(sp.shape[0]), dptr(cuts_d),
+                               C.c_int64(int(cuts_d.numel())), dptr(q_d),
+                               C.c_int64(int(q_d.numel()) if q_d is not None else 0),
+                               C.c_int32(int(F)), dptr(feat), dptr(comp), stream_ptr()),
+          "fr_sieve_heads")
+    return feat, comp
+
+
+def sieve_heads_adjoint(rows_d, spec, spec_d, cuts_d, q_d, comp_d, g_d, row_map=None, row_map_d=None,
+                        lengths_d=None):
+    """fr_sieve_heads_adjoint: the dense gradient ``(N, K, T)`` of the rows that the feature
+    gradients ``g_d`` ``(N, K, F)`` float64 are, every element written.  ``rows_d``: the
+    contiguous ``(V, N, T)`` device tensor that holds the rows ``sieve_heads`` saw; ``row_map``
+    ``(K)`` int32 host array with its device copy ``row_map_d``: row k of the features is row
+    ``row_map[k]`` of ``rows_d`` (neither: ``V == K``, row k).  ``comp_d``: the companion
+    ``sieve_heads`` returned; the tables as there.  ``lengths_d``: the ``(N,)`` int32 device
+    lengths of a ragged batch, or None."""
+    t = torch()
+    if rows_d.dtype != t.float64 or rows_d.dim() != 3 or not rows_d.is_contiguous():
+        raise TypeError("the rows must be a contiguous float64 (V, N, T) device tensor")
+    V, N, T = (int(v) for v in rows_d.shape)
+    sp = _head_tables(spec, spec_d, cuts_d, q_d, N)
+    if (comp_d.dtype != t.int32 or comp_d.dim() != 3 or int(comp_d.shape[0]) != N
+            or not comp_d.is_contiguous() or comp_d.device != rows_d.device):
+        raise TypeError("the companion must be a contiguous int32 (N, K, F) tensor on the rows' device")
+    K, F = int(comp_d.shape[1]), int(comp_d.shape[2])
+    if (g_d.dtype != t.float64 or tuple(g_d.shape) != (N, K, F) or not g_d.is_contiguous()
+            or g_d.device != rows_d.device):
+        raise TypeError("the feature gradients must be a contiguous float64 (N, K, F) tensor on the rows' device")
+    rm = None
+    if row_map is not None:
+        rm = np.ascontiguousarray(row_map, dtype=np.int32)
+        if (rm.shape != (K,) or row_map_d is None or row_map_d.dtype != t.int32
+                or tuple(row_map_d.shape) != (K,) or not row_map_d.is_contiguous()):
+            raise TypeError("the row map is a (K,) int32 host array with a contiguous device copy")
+    if lengths_d is not None and (lengths_d.dtype != t.int32 or tuple(lengths_d.shape) != (N,)
+                                  or not lengths_d.is_contiguous() or lengths_d.device != rows_d.device):
+        raise TypeError("the lengths must be a contiguous int32 (N,) tensor on the rows' device")
+    G = t.empty((N, K, T), dtype=t.float64, device=rows_d.device)
+    check(lib().fr_sieve_heads_adjoint(
+        dptr(rows_d), C.c_int64(V), dptr(row_map_d) if rm is not None else None,
+        _i32p(rm) if rm is not None else None, C.c_int64(K), C.c_int64(N), C.c_int64(T), dptr(spec_d),
+        _i32p(sp), C.c_int32(sp.shape[0]), dptr(cuts_d), C.c_int64(int(cuts_d.numel())), dptr(q_d),
+        C.c_int64(int(q_d.numel()) if q_d is not None else 0), C.c_int32(F), dptr(comp_d), dptr(g_d),
+        dptr(lengths_d) if lengths_d is not None else None, dptr(G), stream_ptr()),
+        "fr_sieve_heads_adjoint")
+    return G

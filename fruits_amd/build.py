@@ -26,6 +26,7 @@ HEADERS = ["kernels.h", "plan.h", "jit.h", "walk.h", "walk_device.h", "walk_fuse
 CAPI = ("capi_core", "capi_plan", "capi_walk", "capi_pipeline", "capi_select", "capi_kernels",
         "capi_grad")
 LOCAL_HEADERS = {"pairwise.h": ("kernels_misc", "kernels_prep"),
+                 "sieve_rows.h": ("kernels_sieve", "kernels_pick", "kernels_heads"),
                  "select_partition.h": ("kernels_select",),
                  "capi_common.h": CAPI,
                  "capi_plan.h": ("capi_plan", "capi_walk", "capi_pipeline", "capi_grad"),
@@ -50,6 +51,9 @@ def units():
            ("kernels_grad_cos", "kernels_grad_cos.hip", ["-ffp-contract=off"]),
            # the selecting sieves of the differentiable features: comparisons and moves alone
            ("kernels_pick", "kernels_pick.hip", []),
+           # the band heads and the expansion of their gradients: the product of a CUR weight is
+           # rounded before it is added, as the numpy reference of its tests rounds it
+           ("kernels_heads", "kernels_heads.hip", ["-ffp-contract=off"]),
            ("jit", "jit.cpp", []),
            # (the registry also holds the mixed kernels of the one-group programs and their
            # tail programs: no contraction, like the programs' own units below)

@@ -462,4 +462,105 @@ int fr_sieve_pick(const double *d_A, int64_t K, int64_t N, int64_t T, const int3
   return launched(e, "sieve pick launch", "fr_sieve_pick: grid too large (K * N)");
 }
 
+// ---------------------------------------------------------------- band heads (kernels_heads.hip)
+namespace {
+// The shapes and every entry of the (n_sieves, 7) spec table of fr_sieve_heads[_adjoint], before
+// a kernel reads the device copy: FR_OK, or the failure.  *cut_stride: the cut table's row per
+// series with per-series cuts, else 0.
+int check_heads(const std::string &who, int64_t K, int64_t N, int64_t T, const int32_t *h_spec,
+                int32_t n_sieves, int64_t n_cuts, int64_t n_q, int32_t F, int64_t *cut_stride) {
+  if (K < 0 || N < 0 || T < 1 || n_sieves < 1 || n_cuts < 0 || n_q < 0 || F < 1)
+    return fail(FR_E_ARG, who + ": bad shape");
+  if (F > fr::kPickMaxFeatures)
+    return fail(FR_E_LIMIT, who + ": at most 256 features per row, not " + std::to_string(F));
+  if (T > 0x7fffffffLL) return fail(FR_E_LIMIT, who + ": positions and counts are 32-bit, T is not");
+  if (!h_spec) return fail(FR_E_ARG, who + ": null host table");
+  const bool series_cuts = (h_spec[0] & FR_SIEVE_SERIES_CUTS) != 0;
+  for (int32_t s = 1; s < n_sieves; ++s)
+    if (((h_spec[7 * (int64_t)s] & FR_SIEVE_SERIES_CUTS) != 0) != series_cuts)
+      return fail(FR_E_ARG, who + ": sieve " + std::to_string(s) + " and sieve 0 differ in FR_SIEVE_SERIES_CUTS: "
+                                  "either every sieve reads per-series cuts or none does");
+  if (series_cuts && N > 0 && n_cuts % N != 0)
+    return fail(FR_E_ARG, who + ": per-series cuts are an (N, row) table, but n_cuts = " +
+                              std::to_string(n_cuts) + " is no multiple of N = " + std::to_string(N));
+  const int64_t cut_row = series_cuts && N > 0 ? n_cuts / N : n_cuts;
+  int64_t features = 0;
+  for (int32_t s = 0; s < n_sieves; ++s) {
+    const int32_t *sp = h_spec + 7 * (int64_t)s;
+    const std::string sieve = who + ": sieve " + std::to_string(s);
+    const int32_t kind = sp[0] & ~FR_SIEVE_SERIES_CUTS, cut_begin = sp[1], C1 = sp[2], q_begin = sp[3], Q1 = sp[4];
+    const bool selects = kind == FR_SIEVE_END || kind == FR_SIEVE_MAX || kind == FR_SIEVE_MIN;
+    if (!selects && kind != FR_SIEVE_MPI && kind != FR_SIEVE_CUR)
+      return fail(FR_E_ARG, sieve + " is no head (END, MAX, MIN, MPI, CUR): kind " + std::to_string(kind));
+    const int32_t lo = kind == FR_SIEVE_CUR ? 2 : 0,
+                  hi = kind == FR_SIEVE_CUR ? 2 : (kind == FR_SIEVE_MPI ? fr::kMaxInc : 0);
+    if (sp[6] < lo || sp[6] > hi)
+      return fail(FR_E_ARG, sieve + " has the differencing order " + std::to_string(sp[6]) + ", not " +
+                                (lo == hi ? std::to_string(lo) : "0 ... 8"));
+    if (C1 < 2 || cut_begin < 0 || (int64_t)cut_begin + C1 > cut_row)
+      return fail(FR_E_ARG, sieve + (series_cuts ? " has a cut row outside a series' row of the cut table"
+                                                 : " has a cut row outside the cut table"));
+    if (kind != FR_SIEVE_END && (Q1 < 2 || q_begin < 0 || (int64_t)q_begin + Q1 > n_q))
+      return fail(FR_E_ARG, sieve + " has thresholds outside the threshold table");
+    if (sp[5] != features)
+      return fail(FR_E_ARG, sieve + " begins at feature " + std::to_string(sp[5]) + ", not at " +
+                                std::to_string(features));
+    features += (int64_t)(C1 - 1) * (kind == FR_SIEVE_END ? 1 : Q1 - 1);
+    if (features > F) break;
+  }
+  if (features != F)
+    return fail(FR_E_ARG, who + ": the sieves have " + std::string(features > F ? "more than " : "") +
+                              std::to_string(features > F ? F : features) + " features, not F = " + std::to_string(F));
+  *cut_stride = series_cuts ? cut_row : 0;
+  return FR_OK;
+}
+}  // namespace
+
+int fr_sieve_heads(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_spec,
+                   const int32_t *h_spec, int32_t n_sieves, const int64_t *d_cuts, int64_t n_cuts,
+                   const double *d_q, int64_t n_q, int32_t F, double *d_feat, int32_t *d_comp,
+                   void *hip_stream) {
+  const std::string who = "fr_sieve_heads";
+  int64_t cut_stride = 0;
+  if (int rc = check_heads(who, K, N, T, h_spec, n_sieves, n_cuts, n_q, F, &cut_stride)) return rc;
+  if (K == 0 || N == 0) return FR_OK;
+  if (!d_A || !d_spec || !d_cuts || !d_feat || !d_comp || (n_q > 0 && !d_q))
+    return fail(FR_E_ARG, who + ": null device pointer");
+  hipError_t e = fr::launch_sieve_heads(d_A, K, N, T, reinterpret_cast<const fr::HeadSieve *>(d_spec), n_sieves,
+                                        d_cuts, cut_stride, d_q, F, d_feat, d_comp, (hipStream_t)hip_stream);
+  return launched(e, "sieve heads launch", "fr_sieve_heads: grid too large (K * N)");
+}
+
+int fr_sieve_heads_adjoint(const double *d_rows, int64_t V, const int32_t *d_row_map,
+                           const int32_t *h_row_map, int64_t K, int64_t N, int64_t T,
+                           const int32_t *d_spec, const int32_t *h_spec, int32_t n_sieves,
+                           const int64_t *d_cuts, int64_t n_cuts, const double *d_q, int64_t n_q, int32_t F,
+                           const int32_t *d_comp, const double *d_g, const int32_t *d_lengths, double *d_G,
+                           void *hip_stream) {
+  const std::string who = "fr_sieve_heads_adjoint";
+  int64_t cut_stride = 0;
+  if (V < 0) return fail(FR_E_ARG, who + ": bad shape");
+  if (int rc = check_heads(who, K, N, T, h_spec, n_sieves, n_cuts, n_q, F, &cut_stride)) return rc;
+  // the row map: both copies or neither; without one the buffer holds the K rows themselves
+  if ((d_row_map != nullptr) != (h_row_map != nullptr))
+    return fail(FR_E_ARG, who + ": the row map needs its host and its device copy");
+  if (!h_row_map && V != K)
+    return fail(FR_E_ARG, who + ": without a row map the buffer holds the K = " + std::to_string(K) +
+                              " rows, not V = " + std::to_string(V));
+  for (int64_t k = 0; h_row_map && k < K; ++k)
+    if (h_row_map[k] < 0 || h_row_map[k] >= V)
+      return fail(FR_E_ARG, who + ": row " + std::to_string(k) + " names row " + std::to_string(h_row_map[k]) +
+                                " of " + std::to_string(V));
+  if (K == 0 || N == 0) return FR_OK;
+  if (!d_rows || !d_spec || !d_cuts || !d_comp || !d_g || !d_G || (n_q > 0 && !d_q))
+    return fail(FR_E_ARG, who + ": null device pointer");
+  if (overlap(d_rows, V * N * T, d_G, K * N * T) || overlap(d_g, K * N * F, d_G, K * N * T))
+    return fail(FR_E_ARG, who + ": d_G must not alias the rows or the feature gradients");
+  hipError_t e = fr::launch_sieve_heads_adjoint(d_rows, d_row_map, K, N, T,
+                                                reinterpret_cast<const fr::HeadSieve *>(d_spec), n_sieves, d_cuts,
+                                                cut_stride, d_q, F, d_comp, d_g, d_lengths, d_G,
+                                                (hipStream_t)hip_stream);
+  return launched(e, "sieve heads adjoint launch", "fr_sieve_heads_adjoint: grid too large (K * N)");
+}
+
 }  // extern "C"

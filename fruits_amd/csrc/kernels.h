@@ -148,6 +148,26 @@ struct PickSieve {
 hipError_t launch_sieve_pick(const double *A, int64_t K, int64_t N, int64_t T, const PickSieve *spec,
                              int n_sieves, const int64_t *cuts, int64_t cut_stride, const double *q,
                              int F, double *feat, int32_t *pos, hipStream_t st);
+// The heads END / MAX / MIN / MPI / CUR over every row of a (K, N, T) buffer at once and the
+// expansion of their feature gradients into the rows' dense gradient (kernels_heads.hip, DESIGN.md
+// 4.14.9).  One sieve of the spec table: a PickSieve and the differencing order.
+struct HeadSieve {
+  int32_t kind;         // FR_SIEVE_END, _MAX, _MIN, _MPI or _CUR
+  int32_t cut_begin, C1, q_begin, Q1, feat_begin;   // as in PickSieve
+  int32_t inc;          // D = E^inc row: MPI 0 ... kMaxInc, CUR 2, the selecting sieves 0
+};
+constexpr int kHeadsTile = 1024;   // time steps a workgroup of the expansion forms at once (256 lanes x 4)
+// feat, comp: (N, K, F), row (k, n) of A at (n * K + k) * F; comp: the position of a selecting
+// feature, the in-band count of an MPI / CUR one.  cut_stride as in launch_sieve_pick.
+hipError_t launch_sieve_heads(const double *A, int64_t K, int64_t N, int64_t T, const HeadSieve *spec,
+                              int n_sieves, const int64_t *cuts, int64_t cut_stride, const double *q,
+                              int F, double *feat, int32_t *comp, hipStream_t st);
+// G (N, K, T) contiguous, every element written.  Row (n, k) is rows[(row_map[k] * N + n) * T ...],
+// row_map null: row k.  comp, g: (N, K, F); len: (N) int32 or null, clamped to [0, T].
+hipError_t launch_sieve_heads_adjoint(const double *rows, const int32_t *row_map, int64_t K, int64_t N,
+                                      int64_t T, const HeadSieve *spec, int n_sieves, const int64_t *cuts,
+                                      int64_t cut_stride, const double *q, int F, const int32_t *comp,
+                                      const double *g, const int32_t *len, double *G, hipStream_t st);
 // the backward pass of the trie walk (kernels_grad.hip): which adjoint, and the
 // tables of the prefix trie, all on the device.  Node v is the plan's node v (DFS preorder); CSR
 // tables have V + 1 (D + 1) offsets.

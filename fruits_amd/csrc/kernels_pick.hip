@@ -3,13 +3,13 @@
 // each feature the value and the position of the element it selects: a backward pass needs
 // nothing else of it.
 //
-// One workgroup of 256 lanes per row (k, n), every sieve, segment and band in turn.  The value
-// path is that of band_sieve_kernel / sieve_kernel (kernels_sieve.hip): MAX / MIN reduce
-// band_key()s - 0 is the empty band and gives 0.0 -, END reads the element at cut - 1 with
-// numpy's wrap of -1.  The position of a MAX / MIN is reduced in a second pass over the segment,
-// once the whole workgroup knows the value: the smallest in-band t whose element EQUALS it as a
-// double - np.argmax's rule, under which -0.0 and +0.0 tie (their keys differ).  The row was
-// written by the walk just before: both passes read it from the cache.
+// One workgroup of 256 lanes per row (k, n), every sieve, segment and band in turn (pick_end,
+// pick_extreme of sieve_rows.h).  The value path is that of band_sieve_kernel / sieve_kernel
+// (kernels_sieve.hip): MAX / MIN reduce band_key()s - 0 is the empty band and gives 0.0 -, END
+// reads the element at cut - 1 with numpy's wrap of -1.  The position of a MAX / MIN is reduced in
+// a second pass over the segment, once the whole workgroup knows the value: the smallest in-band t
+// whose element EQUALS it as a double - np.argmax's rule, under which -0.0 and +0.0 tie (their
+// keys differ).  The row was written by the walk just before: both passes read it from the cache.
 // Plain loads and stores; all offsets are 64-bit; every access is guarded by 0 <= t < T.  The
 // spec table is workgroup-uniform and read through the constant address space (scalar loads).
 // PER-SERIES CUTS (FR_SIEVE_SERIES_CUTS on every kind): series n reads the cut
@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "sieve_rows.h"
 #include "walk_scan.h"
 
 namespace fr {
@@ -37,7 +38,7 @@ __global__ __launch_bounds__(256) void sieve_pick_kernel(const double *__restric
   const int64_t k = r / N, n = r - k * N;
   const double *__restrict__ row = A + r * T;
   const int64_t out = (n * K + k) * (int64_t)F;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int32_t *__restrict__ sp = reinterpret_cast<const int32_t *>(spec);
   for (int s = 0; s < n_sieves; ++s) {
     const int kind = as_const(sp)[6 * s] & 0xff, cut_begin = as_const(sp)[6 * s + 1], C1 = as_const(sp)[6 * s + 2];
@@ -45,14 +46,7 @@ __global__ __launch_bounds__(256) void sieve_pick_kernel(const double *__restric
     const int64_t f0 = out + as_const(sp)[6 * s + 5];
     const int64_t *__restrict__ cut = cuts + n * cut_stride + cut_begin;
     if (kind == FR_SIEVE_END_K) {
-      for (int j = tid; j < C1 - 1; j += 256) {
-        int64_t idx = cut[j + 1] - 1;
-        if (idx < 0) idx += T;
-        // out of range: NaN as in sieve_kernel (the host validates integer cuts), and no position
-        const bool in = idx >= 0 && idx < T;
-        feat[f0 + j] = in ? row[idx] : __builtin_nan("");
-        pos[f0 + j] = in ? (int32_t)idx : -1;
-      }
+      pick_end(row, T, cut, C1, feat + f0, pos + f0, tid);
       continue;
     }
     const bool is_min = kind == FR_SIEVE_MIN_K;
@@ -60,49 +54,9 @@ __global__ __launch_bounds__(256) void sieve_pick_kernel(const double *__restric
       int64_t lo = cut[j], hi = cut[j + 1];
       if (lo < 0) lo = 0;
       if (hi > T) hi = T;
-      for (int b = 0; b < Q; ++b) {
-        const double qlo = q[q_begin + b], qhi = q[q_begin + b + 1];
-        // the value: the largest key of the band, as band_sieve_kernel reduces it
-        unsigned long long key = 0;
-        for (int64_t t = lo + tid; t < hi; t += 256) {
-          const double v = row[t];
-          if (qlo < v && v <= qhi) {
-            const unsigned long long kv = band_key(v, is_min);
-            key = kv > key ? kv : key;
-          }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-          const unsigned long long w = __shfl_xor(key, o);
-          key = w > key ? w : key;
-        }
-        __syncthreads();   // (the slots are reused band after band)
-        if (lane == 0) sm_key[wave] = key;
-        __syncthreads();
-        for (int w = 0; w < 4; ++w) key = sm_key[w] > key ? sm_key[w] : key;
-        const double res = band_key_value(key, is_min);
-        // the position: the first in-band step that attains it (an empty band has none)
-        int first = 0x7fffffff;
-        if (key != 0) {
-          for (int64_t t = lo + tid; t < hi; t += 256) {
-            const double v = row[t];
-            if (qlo < v && v <= qhi && v == res) {
-              first = (int)t;
-              break;   // (a lane's steps rise)
-            }
-          }
-        }
-        for (int o = 32; o > 0; o >>= 1) {
-          const int w = __shfl_xor(first, o);
-          first = w < first ? w : first;
-        }
-        if (lane == 0) sm_pos[wave] = first;
-        __syncthreads();
-        if (tid == 0) {
-          for (int w = 0; w < 4; ++w) first = sm_pos[w] < first ? sm_pos[w] : first;
-          feat[f0 + (int64_t)j * Q + b] = res;
-          pos[f0 + (int64_t)j * Q + b] = first == 0x7fffffff ? -1 : first;
-        }
-      }
+      for (int b = 0; b < Q; ++b)
+        pick_extreme(row, lo, hi, q[q_begin + b], q[q_begin + b + 1], is_min, sm_key, sm_pos,
+                     feat + f0 + (int64_t)j * Q + b, pos + f0 + (int64_t)j * Q + b, tid);
     }
   }
 }

@@ -3,28 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "sieve_rows.h"
 
 namespace fr {
 
 // ---------------------------------------------------------------- sieves on (N,T)
-// value of the inc-times differenced series at t (IncrementSieve._pre_transform,
-// fruits/sieving/increment.py:63-71 with _increments of fruits/cache.py:8-13):
-// D_0 = A, D_k[t] = D_{k-1}[t] - D_{k-1}[t-1] for t >= 1, D_k[0] = 0.
-__device__ __forceinline__ double diff_at(const double *__restrict__ row, int64_t t, int inc) {
-  double v[kMaxInc + 1];
-#pragma unroll
-  for (int j = 0; j <= kMaxInc; ++j) v[j] = (j <= inc && t - j >= 0) ? row[t - j] : 0.0;
-#pragma unroll
-  for (int lvl = 1; lvl <= kMaxInc; ++lvl) {
-    if (lvl <= inc) {
-#pragma unroll
-      for (int j = 0; j + lvl <= kMaxInc; ++j)
-        if (j <= inc - lvl) v[j] = (t - j >= 1) ? v[j] - v[j + 1] : 0.0;
-    }
-  }
-  return v[0];
-}
-
+// (diff_at, the value of the inc-times differenced series at t: sieve_rows.h)
 __global__ __launch_bounds__(256) void sieve_kernel(int kind, const double *__restrict__ A,
                                                      int64_t T, int64_t a_stride, int inc,
                                                      const int64_t *__restrict__ cuts,

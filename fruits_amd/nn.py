@@ -34,6 +34,13 @@ above.  Each such feature is one element of one row, so the backward pass is han
 of that element and the feature's gradient - a sparse upstream (DESIGN.md 4.14.4,
 ``fr_sieve_pick``, ``fr_iss_backward_picked``) - and no ``(N, K, T)`` tensor outlives the call.
 
+``iss_band_features(X, words, mode, sieves, semiring=..., weighting=...)`` and ``BandFeatureLayer``
+are the same for the heads that are no selection: ``MPI`` (``inc`` 0 ... 8) and ``CUR`` / ``AVG`` /
+``STD``, beside ``END`` / ``MAX`` / ``MIN``.  Their upstream with respect to a row is dense, but a
+closed-form function of the row: one kernel forms every head (``fr_sieve_heads``), one expands
+the feature gradients into the rows' gradient just before the dense adjoint reads it
+(``fr_sieve_heads_adjoint``); only ``X`` and an int32 per feature are kept.
+
 ``cos_iss(X, words, freqs, exponent, total_weighting)`` and ``CosWISSLayer`` are the cosine
 weighted sums of ``CosWISS``, ``(N, W * F, T)`` with the bits of ``CosWISS.transform_device``.
 Their backward pass hands the CosWISS plan itself to ``fr_iss_backward`` (DESIGN.md 4.14.7,
@@ -49,8 +56,9 @@ are those of the call on the truncated series, a weighted call with the ``Indice
 row of length ``L_n``; ``Y[n, :, L_n:]`` is unspecified finite data that carries no gradient - the
 upstream gradient there is never read - and ``X.grad[n, :, L_n:]`` is ``+0.0``.  The features of
 series ``n`` are those of the truncated series (``END`` wraps by ``L_n``, ``MAX`` / ``MIN``
-segments end at ``L_n``); their functional form is ``iss_features_ragged``, their layer takes
-the lengths in ``forward`` - lengths belong to a batch, not to a module.  The lengths are
+segments end at ``L_n``); their functional form is ``iss_features_ragged`` (the band features':
+``iss_band_features_ragged``), their layer takes the lengths in ``forward`` - lengths belong to
+a batch, not to a module.  The lengths are
 validated on the host: a device tensor costs one download (and a synchronisation) per call.
 Lengths that all equal ``T`` take the dense path, ``lengths=None`` is untouched.
 """
@@ -68,11 +76,12 @@ from .iss.iss import ISS, ISSMode, _device_budget_bytes
 from .iss.semiring import Arctic, Bayesian, Reals
 from .iss.words.word import SimpleWord
 from .lengths import check_lengths
-from .sieving import END, MAX, MIN
+from .sieving import AVG, CUR, END, MAX, MIN, MPI, STD
 
 __all__ = ["iss", "ISSLayer", "max_iss", "MaxISSLayer", "weighted_iss", "WeightedISSLayer",
            "pathlen_iss", "PathLengthISSLayer", "cos_iss", "CosWISSLayer",
            "iss_features", "iss_features_ragged", "FeatureLayer",
+           "iss_band_features", "iss_band_features_ragged", "BandFeatureLayer",
            "backward_calls"]
 
 _calls = {"backward": 0}
@@ -82,8 +91,9 @@ _OPS_KEPT = 8
 
 def backward_calls() -> int:
     """Backward passes launched by this process so far (one ``fr_iss_backward``,
-    ``fr_iss_backward_max``, ``fr_iss_backward_weighted`` or ``fr_iss_backward_picked`` each; a
-    ``cos_iss`` backward pass counts once however many series blocks it ran in)."""
+    ``fr_iss_backward_max``, ``fr_iss_backward_weighted`` or ``fr_iss_backward_picked`` each - the
+    band features run one of the first three -; a ``cos_iss`` backward pass counts once however
+    many series blocks it ran in)."""
     return _calls["backward"]
 
 
@@ -708,15 +718,17 @@ class CosWISSLayer(_Layer):
 _PICK_MAX_FEATURES = 256      # features of a row (csrc/kernels.h, kPickMaxFeatures)
 
 
-def _check_sieves(sieves) -> list:
+def _check_sieves(sieves, band: bool = False) -> list:
     """The refusals that depend on the sieves alone: raised before any launch.  What remains is
-    END, MAX and MIN with integer cuts - the sieves whose feature is ONE element of the row."""
+    END, MAX and MIN with integer cuts - the sieves whose feature is ONE element of the row - and,
+    for the band features (``band``), MPI with inc 0 ... 8 and CUR / AVG / STD beside them."""
     from .sieving.abstract import FeatureSieve
     if isinstance(sieves, FeatureSieve) or not isinstance(sieves, Sequence):
         raise TypeError("sieves has to be a sequence of sieves")
     sieves = list(sieves)
     if not sieves:
         raise ValueError("sieves has to name at least one sieve")
+    have = "MPI, CUR, AVG, STD, END, MAX and MIN" if band else "END, MAX and MIN"
     for sieve in sieves:
         name = type(sieve).__name__
         if not isinstance(sieve, FeatureSieve):
@@ -724,26 +736,32 @@ def _check_sieves(sieves) -> list:
         if name in ("INC", "INT"):
             raise NotImplementedError(
                 f"the sieve {sieve} has no backward pass here: the wrappers INC / INT sieve "
-                "increments or sums of the row, not the row - only END, MAX and MIN themselves have")
+                f"increments or sums of the row, not the row - only {have} themselves have")
         if name in ("NPI", "XPI", "LPI", "PPV", "CPV"):
             raise NotImplementedError(
                 f"the sieve {sieve} has no backward pass: {name} counts, and the gradient of a "
                 "count is zero almost everywhere")
-        if name in ("MPI", "CUR", "AVG", "STD"):
+        if not band and name in ("MPI", "CUR", "AVG", "STD"):
             raise NotImplementedError(
                 f"the sieve {sieve} has no backward pass here: {name} is no selection of one "
                 "element of the row - only END, MAX and MIN have")
-        if type(sieve) not in (END, MAX, MIN):
+        if type(sieve) not in ((END, MAX, MIN, MPI, CUR, AVG, STD) if band else (END, MAX, MIN)):
             raise NotImplementedError(
-                f"the sieve {sieve} has no backward pass: only END, MAX and MIN have")
+                f"the sieve {sieve} has no backward pass: only {have} have")
+        if type(sieve) is MPI and not 0 <= sieve._inc <= nat.MAX_INC:
+            raise NotImplementedError(
+                f"the sieve {sieve} has no backward pass: " +
+                ("inc < 0 sieves cumulated rows, whose adjoint is not built - " if sieve._inc < 0 else "") +
+                f"only inc 0 ... {nat.MAX_INC} has")
         if sieve._has_float_cuts():
+            what = "segments depend" if name in ("MPI", "CUR", "AVG", "STD") else "position depends"
             raise NotImplementedError(
-                f"the sieve {sieve} has a float (coquantile) cut: its position depends on the "
+                f"the sieve {sieve} has a float (coquantile) cut: its {what} on the "
                 "input's path length, which has no backward pass - only integer cuts have")
     F = sum(sieve.nfeatures() for sieve in sieves)
     if F > _PICK_MAX_FEATURES:
         raise ValueError(f"the sieves have {F} features per iterated sum: at most "
-                         f"{_PICK_MAX_FEATURES} are picked in one launch")
+                         f"{_PICK_MAX_FEATURES} are {'formed' if band else 'picked'} in one launch")
     return sieves
 
 
@@ -761,8 +779,10 @@ class _Head:
     """The sieves of an ``iss_features`` call and their device tables (fr_sieve_pick), kept by
     what they are a function of: the length of the series, the thresholds, the device."""
 
+    _check = staticmethod(_check_sieves)
+
     def __init__(self, sieves) -> None:
-        self.sieves = _check_sieves(sieves)
+        self.sieves = self._check(sieves)
         self.F = sum(sieve.nfeatures() for sieve in self.sieves)
         self._tables: dict = {}
 
@@ -891,7 +911,7 @@ _LENGTHS_ELSEWHERE = ("lengths= is not taken here: lengths belong to a batch - p
                       "FeatureLayer(...)(X, lengths=...), or to nn.iss_features_ragged(X, lengths, ...)")
 
 
-def _apply_features(op: ISS, head: _Head, X, lengths=None):
+def _apply_features(op: ISS, head: _Head, X, lengths=None, function=_FeatureFunction):
     for sieve in head.sieves:
         if not isinstance(sieve, END):
             _thresholds(sieve)           # (an unfitted sieve: before the input is looked at)
@@ -902,7 +922,7 @@ def _apply_features(op: ISS, head: _Head, X, lengths=None):
         raise ValueError("the features of series without a time step are undefined")
     lengths = _ragged_lengths(lengths, int(X.shape[0]), int(X.shape[2]))
     with torch.cuda.device(X.device):
-        return _FeatureFunction.apply(X, op, head, lengths)
+        return function.apply(X, op, head, lengths)
 
 
 def iss_features(X, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
@@ -968,6 +988,155 @@ class FeatureLayer(_Layer):
 
     def forward(self, X, lengths=None):
         return _apply_features(self.op, self.head, X, lengths)
+
+    def extra_repr(self) -> str:
+        return f"{super().extra_repr()}, {self.head.F} features per iterated sum"
+
+
+# ----------------------------------------------------------------------- band features of the rows
+class _BandHead(_Head):
+    """``_Head`` for fr_sieve_heads: the same tables, and the differencing order of each sieve's
+    rows as a seventh spec column."""
+
+    _check = staticmethod(lambda sieves: _check_sieves(sieves, band=True))
+
+    def _with_orders(self, spec):
+        orders = np.asarray([[sieve._inc] for sieve in self.sieves], dtype=np.int32)
+        return np.ascontiguousarray(np.concatenate([spec, orders], axis=1))
+
+    def host_tables(self, T: int):
+        spec, cuts, q = super().host_tables(T)
+        return self._with_orders(spec), cuts, q
+
+    def host_series_tables(self, lengths):
+        spec, cuts, q = super().host_series_tables(lengths)
+        return self._with_orders(spec), cuts, q
+
+
+def _row_map_device(op: ISS, row_prefix, device):
+    """The device copy of the prefix program's ``row_prefix``, kept beside the program."""
+    key = ("heads_row_map", op.mode, str(device))
+    hit = op._plans.get(key)
+    if hit is None or hit[0] is not row_prefix:
+        with torch.cuda.device(device):
+            hit = op._plans[key] = (row_prefix, nat.to_device(row_prefix, dtype=np.int32))
+    return hit[1]
+
+
+class _BandFeatureFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, op, head, lengths=None):
+        Xc = X.contiguous()
+        N, T = int(Xc.shape[0]), int(Xc.shape[2])
+        if lengths is None:
+            spec, spec_d, cuts_d, q_d = head.tables(T, Xc.device)
+        else:
+            # (an END cut outside a series: IndexError here, before any launch)
+            spec, spec_d, cuts_d, q_d = head.series_tables(lengths, Xc.device)
+        if lengths is not None and op.weighting is not None:
+            Y = op.transform_device(Xc, lookup_d=op.lookup_device(Xc, lengths))
+        else:
+            Y = op.transform_device(Xc)          # (K, N, T): dies with this call
+        feat, comp = nat.sieve_heads(Y, spec, spec_d, cuts_d, q_d, head.F)
+        ctx.op, ctx.head = op, head
+        ctx.lengths = lengths                # (host; None: dense)
+        ctx.save_for_backward(Xc, comp, *(() if lengths is None else (nat.to_device(lengths, dtype=np.int32),)))
+        return feat.view(N, -1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        Xc, comp, len_d = (*ctx.saved_tensors, None)[:3]
+        op, head = ctx.op, ctx.head
+        plan, row_prefix = _prefix_program(op)
+        w = g.to(device=Xc.device, dtype=torch.float64).contiguous().view(comp.shape)
+        with torch.cuda.device(Xc.device):
+            # (the tables are kept by the head, a ragged batch's cut rows formed again)
+            if ctx.lengths is None:
+                tables = head.tables(int(Xc.shape[2]), Xc.device)
+            else:
+                tables = head.series_tables(ctx.lengths, Xc.device)
+            if op.weighting is not None:
+                # (the rows again, as the forward pass formed them: the same walk, the same bits)
+                lookup = op.lookup_device(Xc, ctx.lengths)
+                Y = op.transform_device(Xc, lookup_d=lookup)
+                G = nat.sieve_heads_adjoint(Y, *tables, comp, w, lengths_d=len_d)
+                del Y
+                _calls["backward"] += 1
+                return (nat.iss_backward_weighted(plan, Xc, lookup, G, row_prefix, lengths_d=len_d),
+                        None, None, None)
+            # (the backward pass's own prefix sums hold every row: read through row_prefix)
+            S = plan.run(Xc, None, layout="KNT")          # (prefixes, N, T), dies with this call
+            G = nat.sieve_heads_adjoint(S, *tables, comp, w, row_map=row_prefix,
+                                        row_map_d=_row_map_device(op, row_prefix, Xc.device), lengths_d=len_d)
+            _calls["backward"] += 1
+            entry = nat.iss_backward if isinstance(op.semiring, Reals) else nat.iss_backward_max
+            return entry(plan, Xc, S, G, row_prefix, lengths_d=len_d), None, None, None
+
+
+_BAND_LENGTHS_ELSEWHERE = ("lengths= is not taken here: lengths belong to a batch - pass them to the layer's call, "
+                           "BandFeatureLayer(...)(X, lengths=...), or to nn.iss_band_features_ragged(X, lengths, ...)")
+
+
+def iss_band_features(X, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
+                      weighting=None, lengths=None):
+    """The features ``(N, K * F)`` of the iterated sums of the device tensor ``X`` ``(N, D, T)``
+    that the heads ``sieves`` return: what ``sieve.transform_device`` returns on each row of
+    ``ISS(words, mode, ...).transform_device(X)`` - ``END`` / ``MAX`` / ``MIN`` / ``MPI`` with its
+    bits, ``CUR`` / ``AVG`` / ``STD`` with every square rounded -, in ``Fruit``'s column order;
+    differentiable with respect to ``X``.
+
+    ``sieves``: ``MPI`` with ``inc`` 0 ... 8, ``CUR`` / ``AVG`` / ``STD``, ``END``, ``MAX``, ``MIN``, with
+    integer cuts and thresholds q in {-1, 0, 1} or fitted already - cuts and thresholds are
+    constants of the adjoint.  ``semiring`` / ``weighting`` choose the iterated sums as in
+    ``iss_features``.
+
+    With ``D = E^inc row`` (``inc`` 2 for ``CUR``), an ``MPI`` feature is the mean of the ``c`` elements
+    of ``D`` in its segment and band and gives each of them ``g / c``; a ``CUR`` feature is the sum of
+    their squares and gives ``D[t]`` the gradient ``2 g D[t]``; both reach the row through the
+    transposed differencing.  An empty band is the feature 0 and carries no gradient.  Only ``X`` and
+    one int32 per feature are kept; the dense ``(N, K, T)`` gradient of the rows exists inside the
+    backward call alone.
+
+    Series of unequal lengths: ``iss_band_features_ragged``, or ``BandFeatureLayer(...)(X,
+    lengths=...)``; ``lengths=`` here raises NotImplementedError."""
+    if lengths is not None:
+        raise NotImplementedError(_BAND_LENGTHS_ELSEWHERE)
+    head = _BandHead(sieves)
+    op, check = _feature_op(X, words, mode, semiring, weighting)
+    check(op)
+    return _apply_features(op, head, X, None, _BandFeatureFunction)
+
+
+def iss_band_features_ragged(X, lengths, words, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
+                             weighting=None):
+    """``iss_band_features`` of series of unequal lengths, as ``iss_features_ragged``: row ``n`` of
+    the result is ``iss_band_features`` of ``X[n, :, :lengths[n]]``, and ``X.grad[n, :, L_n:]`` is
+    ``+0.0``.  Lengths that all equal ``T`` take the dense path."""
+    head = _BandHead(sieves)
+    op, check = _feature_op(X, words, mode, semiring, weighting)
+    check(op)
+    return _apply_features(op, head, X, lengths, _BandFeatureFunction)
+
+
+class BandFeatureLayer(_Layer):
+    """``iss_band_features`` as a module without parameters; keeps its device programs between calls."""
+
+    def __init__(self, words: Sequence, mode: ISSMode = ISSMode.SINGLE, sieves=(), *, semiring=None,
+                 weighting=None, lengths=None) -> None:
+        if lengths is not None:
+            raise NotImplementedError(_BAND_LENGTHS_ELSEWHERE)
+        head = _BandHead(sieves)
+        op, check = _feature_op(None, words, mode, semiring, weighting)
+        super().__init__(op, check)
+        self.head = head
+
+    @property
+    def sieves(self):
+        return self.head.sieves
+
+    def forward(self, X, lengths=None):
+        return _apply_features(self.op, self.head, X, lengths, _BandFeatureFunction)
 
     def extra_repr(self) -> str:
         return f"{super().extra_repr()}, {self.head.F} features per iterated sum"

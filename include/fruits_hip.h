@@ -858,6 +858,58 @@ int fr_iss_backward_picked(fr_plan_t *prefix_plan, const double *d_X, int64_t N,
                            const int32_t *h_row_prefix, double *d_C, double *d_A, double *d_aux,
                            double *d_dX, void *stream);
 
+/* fr_sieve_heads: the heads a classifier is fed - END, MAX, MIN (as fr_sieve_pick) and the band
+ * sieves MPI (fruits/sieving/increment.py:132-163) and CUR (fruits/sieving/segment.py:228-272; AVG
+ * and STD return its numbers) - over every row of a materialised (K, N, T) buffer in ONE launch.
+ * Not in the reference.  Everything is as in fr_sieve_pick except:
+ *   h_spec, d_spec  (n_sieves, 7) i32: {kind, cut_begin, C1, q_begin, Q1, feat_begin, inc} per
+ *            sieve.  inc: the differencing order of the rows the sieve looks at, D = E^inc row with
+ *            (E a)[t] = a[t] - a[t-1], (E a)[0] = 0: 0 ... 8 for FR_SIEVE_MPI, 2 for FR_SIEVE_CUR,
+ *            0 for the selecting sieves (anything else: FR_E_ARG).  MPI / CUR have
+ *            (C1 - 1) * (Q1 - 1) features in (segment, band) order.
+ *   d_comp   (N, K, F) i32, the companion of d_feat: the position of a selecting feature, the
+ *            number of in-band elements c of an MPI / CUR feature.
+ * MPI: the mean of the D[t] of the segment with q_k < D[t] <= q_(k+1), 0 for none - the bits
+ * fr_sieve returns for that row.  CUR: the sum of their squares, each product rounded.
+ *   hip_stream   the hipStream_t the launch is enqueued on, what the other entries call `stream`
+ *            (here and in fr_sieve_heads_adjoint; both are run on a side stream behind an
+ *            unfinished producer by tests/test_heads_gpu.py) */
+int fr_sieve_heads(const double *d_A, int64_t K, int64_t N, int64_t T, const int32_t *d_spec,
+                   const int32_t *h_spec, int32_t n_sieves, const int64_t *d_cuts, int64_t n_cuts,
+                   const double *d_q, int64_t n_q, int32_t F, double *d_feat, int32_t *d_comp,
+                   void *hip_stream);
+
+/* fr_sieve_heads_adjoint: the gradient of the features of fr_sieve_heads with respect to the
+ * rows: d_G (N, K, T) f64 contiguous, EVERY element written once (no memset, no atomics), to be
+ * handed to fr_iss_backward / _max / _weighted as their upstream.  Thresholds and cuts are
+ * constants.  With L = T, or d_lengths[n] clamped to [0, T]:
+ *   MPI feature f:  weight w_f = d_g[f] / (double)c_f on D[t] for the t of its segment and band
+ *   CUR feature f:  weight (2.0 * d_g[f]) * D[t]
+ *   per sieve       u[t] = +0.0 plus the weights of the features that hold t, in column order;
+ *                   its contribution is (E^T)^inc u,
+ *                   (E^T u)[s] = (s >= 1 ? u[s] : 0.0) - (s + 1 < L ? u[s + 1] : 0.0)
+ *   END, MAX, MIN   the pairs (position d_comp[f], d_g[f]) as fr_iss_backward_picked adds them
+ *   d_G[s]          +0.0 plus the sieves' contributions in the order of the spec; +0.0 at s >= L
+ * The band test runs on the rows again, which have to be the bits fr_sieve_heads saw: the elements
+ * that receive weight are then exactly the c_f it counted.
+ *   d_rows   (V, N, T) f64 contiguous; row (n, k) of the features is row h_row_map[k] of it
+ *   h_row_map, d_row_map   (K) i32 in [0, V) on the host (checked) and on the device - the
+ *            `h_row_prefix` of a backward entry, so that its prefix sums d_S serve as the rows; both
+ *            NULL: V == K and row k is row k
+ *   d_comp, d_g   (N, K, F): the companion fr_sieve_heads wrote and the feature gradients
+ *   d_lengths     (N) i32 per-series lengths or NULL; the tables are then those of
+ *                 fr_sieve_heads' call with per-series cuts
+ *   the rest      as in fr_sieve_heads
+ * FR_E_ARG / FR_E_LIMIT for what fr_sieve_heads refuses, a row map with one copy, an entry outside
+ * [0, V), V != K without a map, a null pointer, d_G aliasing d_rows or d_g: on the host, before the
+ * launch. */
+int fr_sieve_heads_adjoint(const double *d_rows, int64_t V, const int32_t *d_row_map,
+                           const int32_t *h_row_map, int64_t K, int64_t N, int64_t T,
+                           const int32_t *d_spec, const int32_t *h_spec, int32_t n_sieves,
+                           const int64_t *d_cuts, int64_t n_cuts, const double *d_q, int64_t n_q, int32_t F,
+                           const int32_t *d_comp, const double *d_g, const int32_t *d_lengths, double *d_G,
+                           void *hip_stream);
+
 /* fr_plan_set_grad_lengths: per-series lengths for the backward passes that follow on this plan
  * - fr_iss_backward, fr_iss_backward_max, fr_iss_backward_weighted, fr_iss_backward_picked - with
  * exactly N series.  d_lengths: device (N) int32, 1 <= d_lengths[n] <= T (not checked); NULL

@@ -1,5 +1,5 @@
 """`python tools/grad_bench.py [reps] [launches] [--semiring=reals|arctic|bayesian]
-[--weighting=indices[,total]|l1[,total]] [--lengths] [--coswiss]` from the root of the tree: what the backward pass of the
+[--weighting=indices[,total]|l1[,total]] [--lengths] [--coswiss] [--features] [--band-features]` from the root of the tree: what the backward pass of the
 differentiable ISS costs (fruits_amd.nn).  `of_weight(2, 3)` EXTENDED on a (2048, 3, 1024) batch that lives on the device - standard
 normal, uniform in [0.25, 1] for Bayesian -: the forward pass alone (under `torch.no_grad()`) and
 forward plus backward (`layer(X).backward(G)` with a dense upstream gradient), `launches`
@@ -20,6 +20,12 @@ same loss through the rows - `nn.ISSLayer`, then `Y[..., -1]` and `Y.amax(-1)` b
 needs nothing of this option's own code and so also runs on a tree without `nn.FeatureLayer`.
 Without a value both run interleaved.  The JSON line carries the medians, the smallest and largest
 round and `torch.cuda.max_memory_allocated()` of each route, measured over a step of its own.
+
+`--band-features[=dense|banded]` is the same for the band heads: the mean
+increment and the last value of every iterated sum.  `banded` is `nn.BandFeatureLayer` with
+`[MPI([-1], inc=1), END([-1])]`; `dense` composes the two from torch ops on the rows of
+`nn.ISSLayer` - `torch.diff` with the first step prepended, `mean(-1)`, `Y[..., -1]` - and runs on
+a tree without `nn.BandFeatureLayer`.
 
 `--lengths` makes the batch ragged: per-series lengths uniform on [T / 2, T]
 (seeded), passed as `lengths=` to every layer call - the same padded batch, so the line compares
@@ -42,10 +48,12 @@ from fruits_amd import _native as nat
 from fruits_amd import nn
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
-semiring, weighting, features = "reals", "", None
+semiring, weighting, features, band = "reals", "", None, False
 for a in sys.argv[1:]:
     if a == "--features" or a.startswith("--features="):
         features = a.split("=", 1)[1].lower().split(",") if "=" in a else ["dense", "picked"]
+    if a == "--band-features" or a.startswith("--band-features="):
+        features, band = a.split("=", 1)[1].lower().split(",") if "=" in a else ["dense", "banded"], True
     if a.startswith("--semiring="):
         semiring = a.split("=", 1)[1].lower()
     if a.startswith("--weighting="):
@@ -56,8 +64,12 @@ if weighting not in ("", "indices", "indices,total", "l1", "l1,total") or (weigh
     sys.exit("--weighting: indices, indices,total, l1 or l1,total, with the Reals semiring")
 if weighting.startswith("l1") and "--lengths" in sys.argv[1:]:
     sys.exit("--weighting=l1: the path-length weighting takes no lengths")
-if features is not None and (semiring != "reals" or weighting or set(features) - {"dense", "picked"}):
-    sys.exit("--features: dense, picked or both, with the unweighted Reals semiring")
+if features is not None and (semiring != "reals" or weighting
+                             or set(features) - {"dense", "banded" if band else "picked"}):
+    sys.exit("--features: dense, picked or both, --band-features: dense, banded or both, with the unweighted "
+             "Reals semiring")
+if band and "--lengths" in sys.argv[1:]:
+    sys.exit("--band-features: the dense route has no ragged form; on its own")
 coswiss = "--coswiss" in sys.argv[1:]
 if coswiss and (semiring != "reals" or weighting or features is not None or "--lengths" in sys.argv[1:]):
     sys.exit("--coswiss: on its own")
@@ -103,6 +115,23 @@ def feature_routes():
             layer(X, **kw).backward(g)
 
         routes["picked"] = picked
+    if band:
+        def dense_band():
+            X.grad = None
+            Y = rows(X)                                                       # (N, K, T)
+            D1 = t.diff(Y, dim=-1, prepend=Y[..., :1])                        # (the first increment is 0)
+            t.stack((D1.mean(-1), Y[..., -1]), dim=-1).reshape(N, 2 * K).backward(g)
+
+        routes["dense"] = dense_band
+        if "banded" in features:
+            layer = nn.BandFeatureLayer(words, fr.ISSMode.EXTENDED,
+                                        [fr.sieving.MPI([-1], inc=1), fr.sieving.END([-1])])
+
+            def banded():
+                X.grad = None
+                layer(X).backward(g)
+
+            routes["banded"] = banded
     return {k: routes[k] for k in features}
 
 
@@ -122,7 +151,7 @@ if features is not None:
         t.cuda.synchronize()
         peak[k] = [t.cuda.max_memory_allocated() - base, t.cuda.max_memory_allocated()]
     out = {"shape": [N, D, T], "words": "of_weight(2, 3) EXTENDED", "rows": K, "reps": reps,
-           "launches": launches, "features": "END([-1]), MAX([-1])"}
+           "launches": launches, "features": "MPI([-1], inc=1), END([-1])" if band else "END([-1]), MAX([-1])"}
     if ragged:
         out["lengths"] = [T // 2, T, round(float(lengths.mean()), 1)]
     for k in routes:
@@ -130,7 +159,8 @@ if features is not None:
                     k + "_step_minmax_ms": [round(min(times[k]), 4), round(max(times[k]), 4)],
                     k + "_peak_bytes_above_start": peak[k][0], k + "_max_memory_allocated": peak[k][1]})
     if len(routes) == 2:
-        out["picked_over_dense"] = round(out["picked_step_ms"] / out["dense_step_ms"], 3)
+        new = "banded" if band else "picked"
+        out[new + "_over_dense"] = round(out[new + "_step_ms"] / out["dense_step_ms"], 3)
     print(json.dumps(out))
     sys.exit(0)
 
